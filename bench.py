@@ -13,15 +13,22 @@ collective is issued (weak scaling: pixels per GPU are fixed); the only
 collectives are the timing barrier and the max-over-ranks of the elapsed time.
 `--scaling strong` renders config 4 instead (chess @ 16384^2, total work fixed).
 
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` writes what the last
+timed step computed (dump_outputs below).  Everything else in the line is measured with `--full` only and is null
+without it.
+
 Rank 0 prints ONE JSON line:
   value / ms_per_step   SURVEY 8(d) metric (i): kernel-side throughput, outputs in HBM
-  roofline              the dominant kernel against the HBM roof (3 B/pixel written), HIP events on the launch stream
-  end_to_end            SURVEY 8(d) metric (ii): the same frame into a pinned host raster through the host entry
+  long_loop             (--full) the same step 2,000 times between two fences
+  roofline              (--full) the dominant kernel against the HBM roof (3 B/pixel written), HIP events on the launch
+                        stream; beside it this box's fill rate, and config.bit_exact_vs_golden checks the timed output
+  end_to_end            (--full) SURVEY 8(d) metric (ii): the same frame into a pinned host raster through the host entry
                         point (device -> host DMA included), against the PCIe roof; and into pageable memory
-  cold_first_render_ms  context creation + first frame: cold code cache (hiprtc builds both kernels), warm cache
+  config4_strong        (--full, N > 1) config 4 beside the weak-scaling headline
+  cold_first_render_ms  (--full) context creation + first frame: cold code cache (hiprtc builds both kernels), warm cache
                         (a fresh process loads the code objects), and the interpreter (no build at all)
-  cpu_baseline          B1: the oracle = restated Rayon interpreter, on this host's cores (N = 1 only)
-  cpu_baseline_jit      B2: stand-in for the reference's wasmer JIT (scene emitted as straight-line C, cc -O2)
+  cpu_baseline          (--full) B1: the oracle = restated Rayon interpreter, on this host's cores (N = 1 only)
+  cpu_baseline_jit      (--full) B2: stand-in for the reference's wasmer JIT (scene emitted as straight-line C, cc -O2)
 
 Roofline: SURVEY.md 8(d) gives two per-pixel figures for this path, 3 bytes of
 mandatory HBM traffic (the RGB8 pixel written) and 10,241 f64 ops (the census of
@@ -47,6 +54,7 @@ PEAK_F64_TOPS = 39.3               # MI355X f64 VALU, non-FMA instr/s: 256 CU x 
 PEAK_HBM_GBS = 8000.0
 PEAK_PCIE_GBS = 63.0               # PCIe Gen5 x16 (MI355X_MICROARCH.md)
 BLOCK_ROWS = 64                    # rows are dealt to the ranks in blocks of this many (a multiple of the 32-row guard groups)
+DUMP_BYTES = 48 << 20              # --dump-outputs: float32 bytes written at most (1,024 of the 4,096 rows at 4096 wide)
 
 _FIRST_RENDER = r'''
 import json, os, sys, time
@@ -79,6 +87,44 @@ def first_render(backend, env):
     return json.loads(out.stdout.strip().splitlines()[-1])
 
 
+def dump_outputs(path, out8, blocks):
+    """What the last timed step computed, as a caller of the path receives it: this rank's RGB8 rows (out8, rows in the
+    order of `blocks`).  Written as float32, so a fixed sample of whole rows (seed 0, at most DUMP_BYTES) stands for a
+    raster too large to write whole: rgb8.npy (rows, width, 3) and rgb8_rows.npy, the image row of each (float64)."""
+    import numpy as np
+    rows_mine, w = out8.shape[0], out8.shape[1]
+    n = min(rows_mine, max(1, DUMP_BYTES // (w * 3 * 4)))
+    pick = np.sort(np.random.default_rng(0).choice(rows_mine, n, replace=False))
+    image_rows = np.concatenate([np.arange(a, b) for a, b in blocks])[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'rgb8.npy'), out8.cpu().numpy()[pick].astype(np.float32))
+    np.save(os.path.join(path, 'rgb8_rows.npy'), image_rows.astype(np.float64))
+
+
+def result_line(args, value, dt, n_gpus, w_img, h_total, px_per_step, backend_name, ctx, tape, rehearsal_note):
+    """The JSON line with the headline filled in; what --full measures besides it is null here."""
+    return {
+        'metric': 'Mpixels/s on chess.maray @4096x4096',
+        'value': value, 'unit': 'Mpixels/s', 'n_gpus': n_gpus, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
+        'dtype': 'f64', 'data': 'synthetic',
+        'config': {'workload': 'data/chess.maray rescaled to %d x %d (%s), rows dealt to the ranks in interleaved 64-row blocks'
+                               % (w_img, h_total, 'SURVEY.md 8(d) config 3 at N=1; N x 4096^2 pixels of the same scene at N>1'
+                                  if args.scaling == 'weak' else 'SURVEY.md 8(d) config 4: total work fixed'),
+                   'backend': backend_name, 'kernel': ctx.kernel_name, 'pixels_per_step': px_per_step,
+                   'tape_ops_per_pixel': tape.info['n_pix_ops'], 'parallelism': 'row tiles, no collective',
+                   'bit_exact_vs_golden': None, 'code_key': tape.jit_code_key if backend_name == 'jit' else None},
+        'roofline': None,
+        'long_loop': None,
+        'rehearsal': rehearsal_note,
+        'end_to_end': None,
+        'config4_strong': None,
+        'cold_first_render_ms': None,
+        'cpu_baseline': None,
+        'cpu_baseline_jit': None,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -87,6 +133,11 @@ def main():
     ap.add_argument('--backend', default=os.environ.get('MARAY_BENCH_BACKEND', 'auto'))
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help='weak (default): N x 4096^2 pixels; strong: config 4, chess @ 16384^2 shared by the N ranks')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline (long loop, roofline and fill rate, golden '
+                         'parity, end to end, config 4 at N > 1, cold start, CPU baselines); the options below apply to it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/*.npy (see dump_outputs)')
     ap.add_argument('--cpu-seconds', type=float, default=10.0, help='budget of each CPU baseline sample (0 = skip both)')
     ap.add_argument('--no-cpu-jit', action='store_true', help='skip the JIT stand-in (B2)')
     ap.add_argument('--no-cold', action='store_true', help='skip the cold / warm first-render measurement')
@@ -94,6 +145,8 @@ def main():
     ap.add_argument('--long-steps', type=int, default=2000, help='steps of the long loop between two fences (0 = skip)')
     ap.add_argument('--rank-timeout', type=float, default=1500.0, help='seconds the launcher waits for its ranks')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     fake_world = os.environ.get('MARAY_BENCH_FAKE_WORLD')
     # (an environment that exports WORLD_SIZE=1 to everything it starts is not a launcher either; our own ranks carry a mark)
@@ -168,7 +221,7 @@ def main():
     # objects the cold one left), interpreter.  Processes of their own, without PyTorch: a process that imported PyTorch
     # compiles with PyTorch's bundled hiprtc, another compiler version and so another code key than a plain one.
     cold = None
-    if solo and not args.no_cold and args.backend in ('auto', 'jit') and args.scaling == 'weak':
+    if args.full and solo and not args.no_cold and args.backend in ('auto', 'jit') and args.scaling == 'weak':
         scratch = tempfile.mkdtemp(prefix='maray_bench_')
         env = {'MARAY_CACHE_DIR': os.path.join(scratch, 'maray'), 'AMD_COMGR_CACHE_DIR': os.path.join(scratch, 'comgr')}      # comgr keeps a cache of its own
         cold = {'cold_cache': first_render(M.BACKEND_JIT, env)}
@@ -236,7 +289,22 @@ def main():
 
     px_per_step = w_img * h_total
     value = px_per_step * args.steps / dt / 1e6
+    rehearsal_note = ('%d ranks share %d visible device(s): sharding, launches and timing discipline are the real ones, '
+                      'the ranks queue for one GPU, so this is not a scaling figure (gloo for the barrier / max)' % (world, n_dev)
+                      if rehearsal else None)
+    prints_line = rank == 0 or (world == 1 and n_gpus > 1)
+    if args.dump_outputs and prints_line:
+        dump_outputs(args.dump_outputs, out8, blocks)
 
+    if not args.full:
+        if prints_line:
+            line = result_line(args, value, dt, n_gpus, w_img, h_total, px_per_step, backend_name, ctx, tape, rehearsal_note)
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: everything beside the headline ----------------------------------------------------
     # the same step frame after frame for long enough that one fence is < 0.1 % of the region and a once-a-second utilisation
     # sampler sees the GPU busy: `value` above is --steps steps between two fences, i.e. 0.7 ms at the driver's 20 x 36 us
     long_loop = None
@@ -480,18 +548,10 @@ def main():
                                  'recip/step/sin), cc -O2, build %.1f s, run %.1f s; the reference README.md:47-48 puts its JIT at '
                                  '10-20x its interpreter: over_cpu_baseline is that ratio here' % (rows, W, y_first, build_s, ct)}
 
-    if rank == 0 or (world == 1 and n_gpus > 1):
-        line = {
-            'metric': 'Mpixels/s on chess.maray @4096x4096',
-            'value': value, 'unit': 'Mpixels/s', 'n_gpus': n_gpus, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-            'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'data/chess.maray rescaled to %d x %d (%s), rows dealt to the ranks in interleaved 64-row blocks'
-                                   % (w_img, h_total, 'SURVEY.md 8(d) config 3 at N=1; N x 4096^2 pixels of the same scene at N>1'
-                                      if args.scaling == 'weak' else 'SURVEY.md 8(d) config 4: total work fixed'),
-                       'backend': backend_name, 'kernel': ctx.kernel_name, 'pixels_per_step': px_per_step,
-                       'tape_ops_per_pixel': tape.info['n_pix_ops'], 'parallelism': 'row tiles, no collective',
-                       'bit_exact_vs_golden': parity, 'code_key': tape.jit_code_key if backend_name == 'jit' else None},
+    if prints_line:
+        line = result_line(args, value, dt, n_gpus, w_img, h_total, px_per_step, backend_name, ctx, tape, rehearsal_note)
+        line['config']['bit_exact_vs_golden'] = parity
+        line.update({
             'roofline': {'bound': 'hbm', 'achieved': hbm_gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
                          'frac': hbm_gbs / PEAK_HBM_GBS, 'traffic': traffic, 'traffic_profile': traffic_profile,
                          'attainable_peak': attainable,
@@ -508,15 +568,12 @@ def main():
                                                      'boolean algebra on lane masks (scalar unit)'},
                          'executed': executed},
             'long_loop': long_loop,
-            'rehearsal': ('%d ranks share %d visible device(s): sharding, launches and timing discipline are the real ones, '
-                          'the ranks queue for one GPU, so this is not a scaling figure (gloo for the barrier / max)' % (world, n_dev))
-                         if rehearsal else None,
             'end_to_end': e2e,
             'config4_strong': config4,
             'cold_first_render_ms': cold,
             'cpu_baseline': cpu,
             'cpu_baseline_jit': cpu_jit,
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -483,7 +483,35 @@ def test_gen_to_image_keeps_contexts_per_device_and_rechooses_under_auto(chess_b
     M.gen_cache_clear()
 
 
-_BENCH_TWO_RANKS = ['--gpus', '2', '--steps', '5', '--warmup', '2', '--long-steps', '100', '--no-cold', '--cpu-seconds', '0']
+_BENCH_TWO_RANKS = ['--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--long-steps', '100', '--no-cold', '--cpu-seconds', '0']
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path, chess_bytes):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as the driver issues it: the headline alone (what
+    --full measures beside it is null), K timed steps, and a fixed sample of the timed raster's rows in DIR.  Pixel
+    (4i, 4j) of the 4x rescaled scene is pixel (i, j) of the stored one: sampled rows are held against the oracle."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MARAY_BENCH_FAKE_WORLD')}
+    out = str(tmp_path / 'outputs')
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', out], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j['steps'] == 3 and j['value'] > 0 and j['ms_per_step'] > 0 and j['unit'] == 'Mpixels/s'
+    assert j['higher_is_better'] is True and j['dtype'] == 'f64' and j['metric'] == 'Mpixels/s on chess.maray @4096x4096'
+    assert all(j[k] is None for k in ('roofline', 'long_loop', 'end_to_end', 'cold_first_render_ms', 'cpu_baseline'))
+    rgb = np.load(os.path.join(out, 'rgb8.npy'))
+    rows = np.load(os.path.join(out, 'rgb8_rows.npy'))
+    assert rgb.dtype == np.float32 and rows.dtype == np.float64 and rgb.shape == (1024, 4096, 3) and rows.shape == (1024,)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 4096
+    o = OScene(chess_bytes)
+    for k in np.flatnonzero(rows % 4 == 0)[::48]:         # six rows from top to bottom
+        want8, _ = o.render_rows(1024, 1024, int(rows[k]) // 4, int(rows[k]) // 4 + 1, want_f64=False)
+        assert np.array_equal(rgb[k, ::4], want8[0].astype(np.float32)), int(rows[k])
 
 
 def test_bench_starts_two_ranks_on_the_devices_present():

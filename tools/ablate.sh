@@ -5,7 +5,7 @@ out=$root/gpurun_out/ablate.log
 : > "$out"
 run() {
   echo "== $*" >> "$out"
-  env "$@" timeout -k 10 200 python "$root/bench.py" --cpu-seconds 0 --steps 30 --warmup 5 2>/dev/null | tail -n 1 |
+  env "$@" timeout -k 10 200 python "$root/bench.py" --full --cpu-seconds 0 --steps 30 --warmup 5 2>/dev/null | tail -n 1 |
     python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%s: %.0f Mpx/s, step %.4f ms, dominant kernel %.4f ms, parity %s' % (d['config']['backend'], d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['bit_exact_vs_golden']))" >> "$out" 2>&1 || echo "failed" >> "$out"
 }
 run MARAY_X=default

@@ -3,10 +3,11 @@
 # there (tools/summarize_profile.py, by hand) into profiles/r2_*.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
+out=${OUT_DIR:?set OUT_DIR to the folder the results go to}
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { tail -20 gpurun_out/build.log; exit 1; }
 echo "== bench (driver's command)"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_r2.json 2> gpurun_out/bench_r2.err || { tail -5 gpurun_out/bench_r2.err; exit 1; }
-tail -c 1500 gpurun_out/bench_r2.json
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out"/bench_r2.json 2> "$out"/bench_r2.err || { tail -5 "$out"/bench_r2.err; exit 1; }
+tail -c 1500 "$out"/bench_r2.json
 export MARAY_CACHE_DIR=/tmp/maray_cache
 echo "== profile jit"
 bash tools/profile_bench.sh jit --cpu-seconds 0 --no-cold --no-e2e --steps 30 --warmup 5 > gpurun_out/profile_jit.log 2>&1 || { tail -5 gpurun_out/profile_jit.log; exit 1; }

@@ -3,10 +3,11 @@
 # and from there (tools/summarize_profile.py --round r3, tools/collect_r3.py) into profiles/r3_*.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
+out=${OUT_DIR:?set OUT_DIR to the folder the results go to}
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { tail -20 gpurun_out/build.log; exit 1; }
 echo "== bench (driver's command)"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_r3.json 2> gpurun_out/bench_r3.err || { tail -5 gpurun_out/bench_r3.err; exit 1; }
-tail -c 600 gpurun_out/bench_r3.json
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out"/bench_r3.json 2> "$out"/bench_r3.err || { tail -5 "$out"/bench_r3.err; exit 1; }
+tail -c 600 "$out"/bench_r3.json
 export MARAY_CACHE_DIR=/tmp/maray_cache
 echo "== profile jit"
 bash tools/profile_bench.sh jit --cpu-seconds 0 --no-cold --no-e2e --steps 30 --warmup 5 > gpurun_out/profile_jit.log 2>&1 || { tail -5 gpurun_out/profile_jit.log; exit 1; }
@@ -23,7 +24,7 @@ echo "== soups"
 (for a in "300" "300 colours" "1000"; do timeout -k 10 200 python tools/bench_soup.py $a; MARAY_JIT_REDUCE=0 timeout -k 10 200 python tools/bench_soup.py $a; done) > gpurun_out/soups_r3.jsonl 2>&1; cat gpurun_out/soups_r3.jsonl
 echo "== config 4 on one GPU"
 timeout -k 10 400 python tools/exp_strong.py "default:" "tree walked as written:MARAY_JIT_REDUCE=0" "default again:" > gpurun_out/strong_r3.jsonl 2>&1; cat gpurun_out/strong_r3.jsonl
-timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --cpu-seconds 0 --no-cold --no-e2e > gpurun_out/bench_strong_r3.json 2>/dev/null; tail -c 300 gpurun_out/bench_strong_r3.json
+timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --full --cpu-seconds 0 --no-cold --no-e2e > "$out"/bench_strong_r3.json 2>/dev/null; tail -c 300 "$out"/bench_strong_r3.json
 echo "== sizes"
 timeout -k 10 300 python tools/exp_sizes.py > gpurun_out/sizes_r3.jsonl 2>&1; cat gpurun_out/sizes_r3.jsonl
 echo "== interpreters"

@@ -3,13 +3,14 @@
 # and from there (tools/collect_r4.py) into profiles/r4_*.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
+out=${OUT_DIR:?set OUT_DIR to the folder the results go to}
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { tail -20 gpurun_out/build.log; exit 1; }
 echo "== bench (driver's command)"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_r4.json 2> gpurun_out/bench_r4.err || { tail -5 gpurun_out/bench_r4.err; exit 1; }
-tail -c 400 gpurun_out/bench_r4.json
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out"/bench_r4.json 2> "$out"/bench_r4.err || { tail -5 "$out"/bench_r4.err; exit 1; }
+tail -c 400 "$out"/bench_r4.json
 echo "== bench --gpus 2 (its own ranks; a rehearsal when one GPU is visible)"
-timeout -k 10 400 python bench.py --gpus 2 --steps 20 --warmup 5 > gpurun_out/bench_r4_n2.json 2> gpurun_out/bench_r4_n2.err || tail -5 gpurun_out/bench_r4_n2.err
-tail -c 300 gpurun_out/bench_r4_n2.json
+timeout -k 10 400 python bench.py --gpus 2 --steps 20 --warmup 5 --full > "$out"/bench_r4_n2.json 2> "$out"/bench_r4_n2.err || tail -5 "$out"/bench_r4_n2.err
+tail -c 300 "$out"/bench_r4_n2.json
 export MARAY_CACHE_DIR=/tmp/maray_cache
 echo "== profile jit"
 bash tools/profile_bench.sh jit --cpu-seconds 0 --no-cold --no-e2e --steps 30 --warmup 5 --long-steps 0 > gpurun_out/profile_jit.log 2>&1 || { tail -5 gpurun_out/profile_jit.log; exit 1; }
@@ -26,7 +27,7 @@ MARAY_JIT_TEXEL_ONCE=0 python tools/bench_configs.py > gpurun_out/other_configs_
 echo "== soups"
 (for a in "300" "300 colours" "1000"; do timeout -k 10 200 python tools/bench_soup.py $a; done) > gpurun_out/soups_r4.jsonl 2>&1; cat gpurun_out/soups_r4.jsonl | cut -c1-300
 echo "== config 4 on one GPU"
-timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --cpu-seconds 0 --no-cold --no-e2e > gpurun_out/bench_strong_r4.json 2>/dev/null; tail -c 300 gpurun_out/bench_strong_r4.json
+timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --full --cpu-seconds 0 --no-cold --no-e2e > "$out"/bench_strong_r4.json 2>/dev/null; tail -c 300 "$out"/bench_strong_r4.json
 echo "== sizes"
 timeout -k 10 300 python tools/exp_sizes.py > gpurun_out/sizes_r4.jsonl 2>&1; cat gpurun_out/sizes_r4.jsonl | cut -c1-200
 echo "== first call"

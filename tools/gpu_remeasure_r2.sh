@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 export MARAY_CACHE_DIR=/tmp/mc
-echo "== strong"; timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --cpu-seconds 0 --no-cpu-jit 2>/dev/null | tail -1 | python -c "
+echo "== strong"; timeout -k 10 300 python bench.py --scaling strong --steps 20 --warmup 5 --full --cpu-seconds 0 --no-cpu-jit 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print({k:d.get(k) for k in ('value','ms_per_step')}, d.get('end_to_end',{}).get('value'), d['roofline']['frac'], d['roofline']['kernel_ms'])"
 echo "== launch overhead"; timeout -k 10 120 python tools/exp_launch_overhead.py

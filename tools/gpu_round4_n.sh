@@ -13,7 +13,7 @@ for v in 0 1 0 1; do
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('QUICK_SIN=$v', j['crop'], j['pixel_kernel_us'])" || exit 1
   done
 done
-MARAY_JIT_QUICK_SIN=0 timeout -k 10 200 python bench.py --steps 20 --warmup 5 2>/dev/null | python -c "
+MARAY_JIT_QUICK_SIN=0 timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('QUICK_SIN=0 bench', j['value'], j['ms_per_step'], j.get('ctx_ms'), j.get('long_loop'))"
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 2>/dev/null | python -c "
+timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('QUICK_SIN=1 bench', j['value'], j['ms_per_step'], j.get('ctx_ms'), j.get('long_loop'))"

@@ -18,6 +18,6 @@ done
 done
 for cfg in "0 0" "1 1"; do
   set -- $cfg
-  MARAY_JIT_SKY_ROWS=$1 MARAY_JIT_ARGS_UPFRONT=$2 timeout -k 10 200 python bench.py --steps 20 --warmup 5 2>/dev/null | python -c "
+  MARAY_JIT_SKY_ROWS=$1 MARAY_JIT_ARGS_UPFRONT=$2 timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('SKY_ROWS=$1 ARGS_UPFRONT=$2 bench', j['value'], j['ms_per_step'], j['long_loop']['value'], j['roofline']['frac'])"
 done

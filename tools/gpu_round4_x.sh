@@ -16,6 +16,6 @@ for v in 0 1 0 1; do
 done
 cd $GRAFT_REPO_ROOT
 for v in 0 1 0 1; do
-  MARAY_JIT_ROW_BLOCKS=$v timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-cold --no-e2e 2>/dev/null | python -c "
+  MARAY_JIT_ROW_BLOCKS=$v timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --cpu-seconds 0 --no-cold --no-e2e 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ROW_BLOCKS=$v bench', round(j['value']), j['ms_per_step'], round(j['long_loop']['value']), j['long_loop']['ms_per_step'])"
 done
