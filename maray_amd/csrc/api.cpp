@@ -321,9 +321,17 @@ int maray_scene_rescale(maray_scene *s, uint32_t sx, uint32_t sy)
 {
     return guard([&] {
         REQUIRE(s, "null argument");
+        // the name is dropped while the scene changes and folded forward only once the rescale has succeeded: a rescale that
+        // throws must not leave a name that a cached tape of another program answers to
+        bool named;
+        {
+            std::lock_guard<std::mutex> lk(s->key_mutex);
+            named = s->key_valid;
+            s->key_valid = false;
+        }
         scene_rescale(s->s, sx, sy);
         std::lock_guard<std::mutex> lk(s->key_mutex);
-        if (s->key_valid) { const uint32_t step[3] = {0x52455343u, sx, sy}; hash128(step, sizeof step, s->key); }      // "RESC", factors
+        if (named) { const uint32_t step[3] = {0x52455343u, sx, sy}; hash128(step, sizeof step, s->key); s->key_valid = true; }      // "RESC", factors
     });
 }
 

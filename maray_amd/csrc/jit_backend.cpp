@@ -199,8 +199,13 @@ struct JitBackend final : Backend {
         }
         // launch order of the PIXEL kernel (maray_jit_order): once per geometry, from the guard bits the ROW kernel just wrote;
         // a cached order is used by every launch of that geometry, with or without a ROW pass (time_rows)
+        // two rows per wavefront: when the launch's guard groups have an even number of rows (a pair then lies inside one group)
+        const unsigned rpw = (rows2 && yrows >= 2 && yrows % 2 == 0) ? 2u : 1u;
+        const uint32_t rows_per_grid = 65534u * rpw;                   // gridDim.y limit (an even number of rows either way: pairs, 32-row groups)
+        // the order is a permutation of the launch's rows and every grid reads it from its first entry: a launch of more
+        // than one grid takes none
         const unsigned *row_order = nullptr;
-        if (f_order && n_gwords && rows_total <= 65535 && n_groups <= 4096 && n_groups > 1) {
+        if (f_order && n_gwords && rows_total <= rows_per_grid && n_groups <= 4096 && n_groups > 1) {
             const uint64_t key[3] = {((uint64_t)w << 32) | rows_total, ((uint64_t)y0 << 32) | blk_rows, ((uint64_t)blk_stride << 32) | yrows};
             const bool cached = key[0] == order_key[0] && key[1] == order_key[1] && key[2] == order_key[2];
             // The order costs one 43 us kernel per geometry and saves ~2.6 us per launch: it is computed when a geometry
@@ -234,9 +239,7 @@ struct JitBackend final : Backend {
         const uint64_t device_slots = (uint64_t)n_cu * 4 * 7;
         unsigned tiles = wide_all ? (n_tiles <= device_slots ? 1 : n_tiles <= 4 * device_slots ? 2 : n_tiles <= 16 * device_slots ? 4 : 8)
                                   : (n_tiles <= 4 * device_slots ? 1 : n_tiles <= 16 * device_slots ? 2 : 4);
-        // two rows per wavefront: when the launch's guard groups have an even number of rows (a pair then lies inside one group);
-        // the strip is half as long, so that a wavefront owns as many pixels as it would with one row
-        const unsigned rpw = (rows2 && yrows >= 2 && yrows % 2 == 0) ? 2u : 1u;
+        // two rows per wavefront: the strip is half as long, so that a wavefront owns as many pixels as it would with one row
         if (rpw == 2 && tiles > 1) tiles /= 2;
         if (k_tiles) tiles = std::min(64u, k_tiles);
         if (n_gwords && n_gwords <= GW_INLINE_MAX) tiles = std::min(tiles, 64u / (n_gwords * guard_sub));      // a strip's guard words: one per lane
@@ -247,7 +250,6 @@ struct JitBackend final : Backend {
             ensure(d_flags, flags_cap, (size_t)n_tiles + 1);                // work list {count, tile, ...} of deferred tiles
             HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(unsigned), st));
         }
-        const uint32_t rows_per_grid = 65534u * rpw;                   // gridDim.y limit (an even number of rows either way: pairs, 32-row groups)
         for (uint32_t r0 = 0; r0 < rows_total; r0 += rows_per_grid) {
             uint32_t rows = std::min<uint32_t>(rows_per_grid, rows_total - r0);
             unsigned char *p8 = d8 ? d8 + (size_t)r0 * w * 3 : nullptr;

@@ -357,6 +357,9 @@ void scene_fix_color(Scene &s)
 void scene_rescale(Scene &s, uint32_t sx, uint32_t sy)
 {
     if (sx == 0 || sy == 0) throw Error{MARAY_E_ARG, "scale factors must be non-zero"};
+    // every check before the first change: a rescale that fails leaves the scene as it was
+    const uint64_t w = (uint64_t)s.w * sx, h = (uint64_t)s.h * sy;
+    if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "rescaled size overflows u32"};
     auto scaled = [&](uint8_t leaf, uint32_t k) {   // div(x(), nat(k)) = Mul(X, Recip(Nat k)), src/lib.rs:950-952
         Node l; l.tag = leaf;
         Node nat; nat.tag = T_NAT; nat.u = k;
@@ -375,8 +378,6 @@ void scene_rescale(Scene &s, uint32_t sx, uint32_t sy)
     for (Ctx &c : s.ctxs) for (int32_t &d : c.defs) remap(d);
     for (auto &tl : s.toklists) for (Token &t : tl) if (t.kind == 0) remap(t.expr);
     for (int c = 0; c < 3; c++) remap(s.color[c]);
-    uint64_t w = (uint64_t)s.w * sx, h = (uint64_t)s.h * sy;
-    if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "rescaled size overflows u32"};
     s.w = (uint32_t)w; s.h = (uint32_t)h;
 }
 

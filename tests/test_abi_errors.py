@@ -95,3 +95,18 @@ def test_null_arguments_are_errors_not_crashes():
     assert L.maray_hip_render_rows(None, 4, 4, 0, 4, None, None) == -1
     assert L.maray_png_write(None, None, 0, 0) == -1
     L.maray_scene_free(None); L.maray_tape_free(None); L.maray_hip_ctx_free(None); L.maray_free(None)
+
+
+def test_a_rescale_that_overflows_leaves_the_scene_unchanged(tmp_path):
+    """65536 x 65537 does not fit u32: the rescale is an error, and the scene is the one it was before the call, byte for
+    byte as `save` writes it -- no X reference rewritten on the way to the error."""
+    from marayb import encode, mul, nat, step, sub, x, y
+    data = encode((65536, 1), [mul(step(sub(x(), nat(32))), nat(200)), mul(y(), nat(3)), x()])
+    s = M.Scene(data)
+    s.save(str(tmp_path / 'before.maray'))
+    assert (tmp_path / 'before.maray').read_bytes() == data
+    with pytest.raises(M.MarayError):
+        s.rescale(65537, 1)
+    s.save(str(tmp_path / 'after.maray'))
+    assert (tmp_path / 'after.maray').read_bytes() == data
+    assert s.size == (65536, 1)
