@@ -108,12 +108,13 @@ def transforms(size):
     return [r, g, body]
 
 
-def ops_on_a_guarded_mask(w, h):
+def ops_on_a_guarded_mask(w, h, edge=None):
     """Every kind of op fed with the VALUE of guarded shapes (textured triangles, each behind a rectangle guard), directly and
     through arithmetic with constants: in the specialised kernel's variant for tiles without a guard bit those values are the
     literal 0.0, so every op there meets operands that are numbers, not vector values — texture coordinates included (a
     random scene of round 4's second GPU sweep, seed 6462, was the first to do that to an App: its four-wide form did not
-    compile).  Two textures (ids 0..4 and 5..9)."""
+    compile).  Two textures (ids 0..4 and 5..9).  edge: three exprs (tests/edge_values.py) added to the three shapes'
+    values, so that every op meets an edge value there (outside the guards: that value alone)."""
     from fuzz_scenes import subst_xy
     from marayb import chess, inside_triangle, min_, recip, step, to_uv
     p = [x(), y()]
@@ -124,6 +125,8 @@ def ops_on_a_guarded_mask(w, h):
         uv = to_uv(pts, [(nat(0), nat(0)), (nat(1), nat(0)), (nat(0), nat(1))], p)
         masks.append(min_(inside_triangle(pts, p), subst_xy(chess(4), uv[0], uv[1])))
     m0, m1, m2 = masks
+    if edge is not None:
+        m0, m1, m2 = (add(m, e) for m, e in zip(masks, edge))
     c0 = add(add(abs_(sub(m0, div(nat(1), nat(2)))), recip(add(m1, nat(1)))), add(sqrt(m2), mul(sin(m0), exp(m1))))
     c0 = add(c0, add(ln(add(m2, nat(1))), add(step(sub(m0, div(nat(1), nat(2)))), step(sin(mul(m1, nat(3)))))))
     c1 = add(app(channel(0, 1), mul(m0, nat(20)), y()), add(app(channel(1, 0), x(), mul(m1, nat(9))), app(channel(0, 2), m2, mul(m0, nat(3)))))

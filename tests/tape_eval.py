@@ -15,7 +15,16 @@ K_SLOT, K_CONST, K_YVAL, K_SPEC = 0, 1, 2, 3
 DST_NONE = 0xFFF
 
 _vsin = np.vectorize(math.sin, otypes=[np.float64])
-_vexp = np.vectorize(lambda v: math.exp(v) if v < 709.782712893384 else (math.inf if v == v else v), otypes=[np.float64])
+
+
+def _exp1(v):
+    try:
+        return math.exp(v)
+    except OverflowError:      # (709.782712893384 itself is finite: 0x1.fffffffffff2ap+1023)
+        return math.inf
+
+
+_vexp = np.vectorize(_exp1, otypes=[np.float64])
 
 
 def _vlog(a):
