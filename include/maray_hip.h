@@ -151,7 +151,8 @@ enum {
     MARAY_BACKEND_JIT = 2,       /* tape specialised to straight-line HIP via hiprtc (GPU analogue of src/wasm.rs) */
     MARAY_BACKEND_AUTO = 3       /* the specialised kernels when their code objects are in the cache (MARAY_CACHE_DIR) or when
                                     building them (estimated from the tape's size) costs less than what they save over
-                                    hint_mpixels of rendering; else the scalar-cache tape interpreter, which needs no build */
+                                    hint_mpixels of rendering; else the scalar-cache tape interpreter, which needs no build.
+                                   (for a supersampling context hint_mpixels counts samples) */
 };
 
 typedef struct maray_ctx_opts {
@@ -159,8 +160,25 @@ typedef struct maray_ctx_opts {
     uint32_t hint_mpixels;  /* MARAY_BACKEND_AUTO: how many megapixels (2^20 pixels, rounded up) the caller is about to render with
                                this context; 0 = unknown / many.  The specialised kernels are worth their hiprtc build only
                                when that time is earned back (or when the code object cache already holds them). */
-    uint32_t reserved[6];
+    uint32_t samples;       /* k x k samples per output pixel, k in {0, 1, 2, 4, 8} (0 = 1); see "supersampling" below */
+    uint32_t reserved[5];
 } maray_ctx_opts;
+
+/* ---- supersampling (anti-aliasing with an in-kernel box filter) ---------------------------------------------------
+ * Supersampling is two steps.  maray_scene_supersample(s, k) (below) moves the scene onto a k x k finer grid, and a
+ * context created with samples = k renders that program's raster in k x k blocks and writes only their means:
+ *   - sample points: output pixel (px, py) has the samples x = px + (2i + 1 - k) / (2k), y = py + (2j + 1 - k) / (2k),
+ *     i, j = 0 .. k-1 (centred on the point the plain render evaluates; exact in f64 for k a power of two);
+ *   - each sample's channel is cast like a plain pixel (Rust `as u8`: saturating, NaN -> 0);
+ *   - each output channel is the integer mean of its k^2 cast samples, rounding half up: (S + k^2/2) >> log2(k^2).
+ *     An integer sum: the same result in any order, on any device split.
+ * With samples = k every render entry point takes OUTPUT geometry (w, h, y0 / y1, blocks, tiles in output pixels and
+ * rows; the program is evaluated at sample indices 0 .. k w - 1 and 0 .. k h - 1).  This is well-defined for any
+ * program ("reduce the sample grid"); maray_gen_to_image with maray_gen_opts.samples pairs the two steps itself.
+ * Limits: k outside {0, 1, 2, 4, 8}: MARAY_E_ARG; f64 planes with k > 1: MARAY_E_ARG; k w or k h above
+ * MARAY_DOMAIN_MAX: MARAY_E_LIMIT.  Every back-end has a supersampling kernel (maray_tape_pixels_ss, maray_jit_pixels_ss);
+ * AUTO chooses between them as for a plain render.  k = 0 or 1 is the plain render, unchanged. */
+int maray_scene_supersample(maray_scene *s, uint32_t k);   /* X -> X/k - (k-1)/(2k), Y alike, size * k; k = 0 or 1: no change */
 
 int maray_hip_device_count(int *n);
 /* Uploads tape, constants and textures to HBM once. */
@@ -221,6 +239,11 @@ int maray_jit_source(const maray_program *prog, char **src_out);
  * ROW section was cut into, evaluated side by side as blockIdx.y; may be NULL). */
 int maray_jit_source_rows(const maray_program *prog, char **src_out, uint32_t *n_chunks);
 int maray_jit_build(const maray_program *prog, void **code_out, size_t *len_out);
+/* The supersampling PIXEL kernel (maray_jit_pixels_ss, k = 2, 4, 8: see "supersampling"): its source, and its gfx950 code
+ * object (built once per program and k, kept like the others under a key of its own that contains k).  Needs no GPU.  The
+ * plain sources above and their key do not depend on it. */
+int maray_jit_source_samples(const maray_program *prog, uint32_t k, char **src_out);
+int maray_jit_build_samples(const maray_program *prog, uint32_t k, void **code_out, size_t *len_out);
 /* The specialised kernels of a program are built once and kept, in the process and under MARAY_CACHE_DIR (default
  * $XDG_CACHE_HOME/maray_amd or ~/.cache/maray_amd; "off" disables): the reference's JIT compiles its modules again on
  * every thread of every render (src/render.rs:158-165).  The key is a 128-bit hash of the generated sources, the
@@ -249,7 +272,9 @@ typedef struct maray_gen_opts {
     uint32_t backend;        /* MARAY_BACKEND_* */
     uint32_t n_devices;      /* 0 = all visible devices; image rows are tiled across them */
     uint32_t tile_rows;      /* rows per launch (0 = default) */
-    uint32_t reserved[5];
+    uint32_t samples;        /* k x k samples per pixel (0 = 1): the scene is supersampled privately and rendered by
+                                contexts with samples = k; programs are kept per k */
+    uint32_t reserved[4];
 } maray_gen_opts;
 
 /* gen_to_image: fills the caller's w*h*3 RGB8 buffer. */

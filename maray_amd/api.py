@@ -44,12 +44,12 @@ class LowerOpts(C.Structure):
 
 
 class CtxOpts(C.Structure):
-    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('samples', C.c_uint32), ('reserved', C.c_uint32 * 5)]
 
 
 class GenOpts(C.Structure):
-    _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32),
-                ('reserved', C.c_uint32 * 5)]
+    _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32), ('samples', C.c_uint32),
+                ('reserved', C.c_uint32 * 4)]
 
 
 class Report(C.Structure):
@@ -90,6 +90,7 @@ def lib():
         'maray_scene_save': (C.c_int, [vp, C.c_char_p]),
         'maray_scene_fix_color': (C.c_int, [vp]),
         'maray_scene_rescale': (C.c_int, [vp, u32, u32]),
+        'maray_scene_supersample': (C.c_int, [vp, u32]),
         'maray_scene_simplify': (C.c_int, [vp]),
         'maray_scene_simplify_ex': (C.c_int, [vp, C.c_uint32]),
         'maray_scene_compress': (C.c_int, [vp, C.POINTER(u32)]),
@@ -238,6 +239,11 @@ class Scene:
     def rescale(self, sx, sy):
         _check(lib().maray_scene_rescale(self._h, sx, sy))
 
+    def supersample(self, k):
+        """The scene on a k x k finer grid, centred on the plain one (k = 1, 2, 4, 8; 0 and 1 change nothing): what a
+        Context(..., samples=k) reduces."""
+        _check(lib().maray_scene_supersample(self._h, k))
+
     def lower(self, hoist_rows=True, plain_cse=False, fuse=True, skips=True, row_guards=True, private_regions=True, rebalance=True,
               y_spans=True):
         return Tape(self, hoist_rows, plain_cse, fuse, skips, row_guards, private_regions, rebalance, y_spans)
@@ -321,13 +327,15 @@ class PinnedRaster:
 
 
 class Context:
-    """Device context: tape + constants + textures resident in HBM."""
+    """Device context: tape + constants + textures resident in HBM.  samples=k > 1: renders the program's raster in k x k
+    blocks and writes their means (RGB8 only); every render call then takes output geometry."""
 
-    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0):
+    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0):
         arr, n, keep = _textures(textures)
         o = CtxOpts()
         o.backend = backend
         o.hint_mpixels = hint_mpixels
+        o.samples = samples
         h = C.c_void_p()
         _check(lib().maray_hip_ctx_create(device, C.byref(tape.program), arr, n, C.byref(o), C.byref(h)))
         self._h = h
@@ -387,14 +395,15 @@ class Context:
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,
-                 report_kind=REPORT_NONE, report_value=0, out=None):
-    """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given)."""
+                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0):
+    """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
+    samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling)."""
     w, h = size if size else scene.size
     img = np.zeros((h, w, 3), np.uint8) if out is None else out
     assert img.shape == (h, w, 3) and img.dtype == np.uint8 and img.flags['C_CONTIGUOUS']
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.tile_rows = backend, n_devices, tile_rows
+    go.backend, go.n_devices, go.tile_rows, go.samples = backend, n_devices, tile_rows, samples
 
     def _cb(user, p, cw, ch, progress):
         if report:
@@ -405,11 +414,11 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     return img
 
 
-def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0):
-    """`gen` (src/lib.rs:1199-1213): render and write a PNG."""
+def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0):
+    """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased, as gen_to_image)."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices = backend, n_devices
+    go.backend, go.n_devices, go.samples = backend, n_devices, samples
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
 
 

@@ -139,6 +139,20 @@ void scene_cache_key(const maray_scene *cs, uint64_t out[2])
     out[0] = s->key[0]; out[1] = s->key[1];
 }
 
+// gen_to_image with samples = k: a private copy of the scene, supersampled (named after the scene and k)
+maray_scene *scene_supersampled_copy(const maray_scene *cs, uint32_t k)
+{
+    std::unique_ptr<maray_scene> c(new maray_scene());
+    {
+        maray_scene *s = const_cast<maray_scene *>(cs);
+        std::lock_guard<std::mutex> lk(s->key_mutex);
+        c->s = s->s;
+        c->key_valid = s->key_valid; c->key[0] = s->key[0]; c->key[1] = s->key[1];
+    }
+    if (const int rc = maray_scene_supersample(c.get(), k)) throw Error{rc, maray_last_error()};
+    return c.release();
+}
+
 void validate_program(const maray_program &p)
 {
     if (p.version != MARAY_TAPE_VERSION) throw Error{MARAY_E_ARG, "tape version mismatch"};
@@ -335,6 +349,25 @@ int maray_scene_rescale(maray_scene *s, uint32_t sx, uint32_t sy)
     });
 }
 
+int maray_scene_supersample(maray_scene *s, uint32_t k)
+{
+    return guard([&] {
+        REQUIRE(s, "null argument");
+        if (k == 0) k = 1;
+        bool named;         // dropped while the scene changes, folded forward after success (as in maray_scene_rescale)
+        {
+            std::lock_guard<std::mutex> lk(s->key_mutex);
+            named = s->key_valid;
+            s->key_valid = false;
+        }
+        try { scene_supersample(s->s, k); }
+        catch (...) { std::lock_guard<std::mutex> lk(s->key_mutex); s->key_valid = named; throw; }     // unchanged: so is its name
+        std::lock_guard<std::mutex> lk(s->key_mutex);
+        if (named && k > 1) { const uint32_t step[2] = {0x53555053u, k}; hash128(step, sizeof step, s->key); }      // "SUPS", k
+        s->key_valid = named;
+    });
+}
+
 int maray_scene_simplify(maray_scene *s)
 {
     return guard([&] { REQUIRE(s, "null argument"); s->key_valid = false; run_big_stack([&] { scene_simplify(s->s); }); });
@@ -412,11 +445,13 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
                         std::to_string(5u * n_tex) + " texture functions exist"};
         for (uint32_t i = 0; i < n_tex; i++) REQUIRE(tex[i].rgb || (uint64_t)tex[i].w * tex[i].h == 0, "null texture raster");
         const uint32_t backend = opts ? opts->backend : MARAY_BACKEND_TAPE;
+        const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
+        REQUIRE(samples == 1 || samples == 2 || samples == 4 || samples == 8, "samples must be 0, 1, 2, 4 or 8");
         Backend *b = nullptr;
         switch (backend) {
-        case MARAY_BACKEND_TAPE: b = make_tape_backend(device, *prog, tex, n_tex, true); break;
-        case MARAY_BACKEND_TAPE_SMEM: b = make_tape_backend(device, *prog, tex, n_tex, false); break;
-        case MARAY_BACKEND_JIT: b = make_jit_backend(device, *prog, tex, n_tex); break;
+        case MARAY_BACKEND_TAPE: b = make_tape_backend(device, *prog, tex, n_tex, true, samples); break;
+        case MARAY_BACKEND_TAPE_SMEM: b = make_tape_backend(device, *prog, tex, n_tex, false, samples); break;
+        case MARAY_BACKEND_JIT: b = make_jit_backend(device, *prog, tex, n_tex, samples); break;
         case MARAY_BACKEND_AUTO: {
             // One-shot economics.  The specialised kernels render a frame tens of times faster than the interpreter, but
             // hiprtc needs seconds to build them (chess: 9 k pixel + 17 k row ops -> 1.6 s with the two modules built side
@@ -438,11 +473,11 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
             }
             if (force && !strcmp(force, "jit")) want_jit = true;
             if (force && !strcmp(force, "tape")) want_jit = false;
-            if (!want_jit) { b = make_tape_backend(device, *prog, tex, n_tex, false); break; }
-            try { b = make_jit_backend(device, *prog, tex, n_tex); }
+            if (!want_jit) { b = make_tape_backend(device, *prog, tex, n_tex, false, samples); break; }
+            try { b = make_jit_backend(device, *prog, tex, n_tex, samples); }
             catch (const Error &e) {
                 if (e.code == MARAY_E_NO_DEVICE) throw;
-                b = make_tape_backend(device, *prog, tex, n_tex, false);   // still the HIP path, never a CPU fallback
+                b = make_tape_backend(device, *prog, tex, n_tex, false, samples);   // still the HIP path, never a CPU fallback
             }
             break;
         }
@@ -451,6 +486,7 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         maray_ctx *c = new maray_ctx();
         c->backend = b;
         c->n_tex = n_tex;
+        c->samples = samples;
         *out = c;
     });
 }
@@ -470,11 +506,22 @@ static void check_rows(uint32_t w, uint32_t h, uint32_t y0, uint32_t y1)
         throw Error{MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y"};
 }
 
+// A supersampling context evaluates k w x k h samples: the lowering's analysis covers sample indices below
+// MARAY_DOMAIN_MAX.  It writes RGB8 only.
+static void check_samples(const maray_ctx *c, uint32_t w, uint32_t h, bool want64)
+{
+    if (c->samples <= 1) return;
+    if (want64) throw Error{MARAY_E_ARG, "a supersampling context renders RGB8 only (no f64 planes)"};
+    if ((uint64_t)w * c->samples > MARAY_DOMAIN_MAX || (uint64_t)h * c->samples > MARAY_DOMAIN_MAX)
+        throw Error{MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y"};
+}
+
 int maray_hip_render_rows(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint32_t y1, uint8_t *rgb8, double *rgb64)
 {
     return guard([&] {
         REQUIRE(c && c->backend, "null context");
         check_rows(w, h, y0, y1);
+        check_samples(c, w, h, rgb64 != nullptr);
         if (y0 == y1 || w == 0 || (!rgb8 && !rgb64)) return;
         c->backend->render_host_tiles(w, h, cut_row_tiles(w, y0, y1, rgb8 != nullptr, rgb64 != nullptr), y0, rgb8, rgb64, nullptr);
     });
@@ -493,6 +540,7 @@ int maray_hip_render_tiles(maray_ctx *c, uint32_t w, uint32_t h, const uint32_t 
             check_rows(w, h, tiles[i].y0, tiles[i].y1);
             REQUIRE(tiles[i].y1 > tiles[i].y0, "empty tile");
         }
+        check_samples(c, w, h, false);
         std::function<void(uint32_t, uint32_t)> done;
         if (fn) done = [&](uint32_t a, uint32_t b) { fn(user, a, b); };
         c->backend->render_host_tiles(w, h, tiles, 0, rgb8_image, nullptr, done);
@@ -525,6 +573,7 @@ int maray_hip_render_rows_device(maray_ctx *c, uint32_t w, uint32_t h, uint32_t 
     return guard([&] {
         REQUIRE(c && c->backend, "null context");
         check_rows(w, h, y0, y1);
+        check_samples(c, w, h, d_rgb64 != nullptr);
         if (y0 == y1 || w == 0) return;
         c->backend->render_device(w, h, RowBlocks::range(y0, y1), d_rgb8, d_rgb64, stream);
     });
@@ -540,6 +589,7 @@ int maray_hip_render_blocks_device(maray_ctx *c, uint32_t w, uint32_t h, uint32_
         const uint64_t last = (uint64_t)y0 + (uint64_t)(n_blocks - 1) * block_stride + block_rows;       // one past the last row
         REQUIRE(last <= 0xFFFFFFFFull && (uint64_t)n_blocks * block_rows <= 0xFFFFFFFFull, "row blocks out of range");
         check_rows(w, h, y0, (uint32_t)last);
+        check_samples(c, w, h, d_rgb64 != nullptr);
         c->backend->render_device(w, h, RowBlocks{y0, n_blocks * block_rows, block_rows, n_blocks == 1 ? 0u : block_stride}, d_rgb8, d_rgb64, stream);
     });
 }
@@ -550,6 +600,7 @@ int maray_hip_time_rows(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint3
     return guard([&] {
         REQUIRE(c && c->backend && ms_avg, "null argument");
         check_rows(w, h, y0, y1);
+        check_samples(c, w, h, d_rgb64 != nullptr);
         REQUIRE(y1 > y0 && w > 0 && reps > 0, "empty launch");
         *ms_avg = c->backend->time_rows(w, h, RowBlocks::range(y0, y1), d_rgb8, d_rgb64, reps);
     });
@@ -565,6 +616,7 @@ int maray_hip_time_blocks(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uin
         const uint64_t last = (uint64_t)y0 + (uint64_t)(n_blocks - 1) * block_stride + block_rows;
         REQUIRE(last <= 0xFFFFFFFFull && (uint64_t)n_blocks * block_rows <= 0xFFFFFFFFull, "row blocks out of range");
         check_rows(w, h, y0, (uint32_t)last);
+        check_samples(c, w, h, d_rgb64 != nullptr);
         *ms_avg = c->backend->time_rows(w, h, RowBlocks{y0, n_blocks * block_rows, block_rows, n_blocks == 1 ? 0u : block_stride}, d_rgb8, d_rgb64, reps);
     });
 }
@@ -574,6 +626,17 @@ int maray_jit_source(const maray_program *prog, char **src_out)
     return guard([&] {
         REQUIRE(prog && src_out, "null argument");
         const std::string s = jit_source(*prog);
+        *src_out = (char *)malloc(s.size() + 1);
+        if (!*src_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
+int maray_jit_source_samples(const maray_program *prog, uint32_t k, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const std::string s = jit_source_samples(*prog, k);
         *src_out = (char *)malloc(s.size() + 1);
         if (!*src_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
         memcpy(*src_out, s.c_str(), s.size() + 1);
@@ -621,6 +684,18 @@ int maray_jit_build(const maray_program *prog, void **code_out, size_t *len_out)
         if (!*code_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
         memcpy(*code_out, code.data(), code.size());
         *len_out = code.size();
+    });
+}
+
+int maray_jit_build_samples(const maray_program *prog, uint32_t k, void **code_out, size_t *len_out)
+{
+    return guard([&] {
+        REQUIRE(prog && code_out && len_out, "null argument");
+        const std::shared_ptr<const std::vector<char>> code = jit_code_samples(*prog, k);
+        *code_out = malloc(code->size() ? code->size() : 1);
+        if (!*code_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
+        memcpy(*code_out, code->data(), code->size());
+        *len_out = code->size();
     });
 }
 

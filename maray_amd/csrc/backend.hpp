@@ -55,10 +55,13 @@ void set_last_error(const std::string &m);   // thread-local message behind mara
 int read_whole_file(const char *path, std::vector<uint8_t> &b);                                             // png.cpp; MARAY_E_IO + message on failure
 int png_decode(const std::vector<uint8_t> &b, uint8_t **rgb8_out, uint32_t *w_out, uint32_t *h_out);       // png.cpp
 int hip_device_count();
-Backend *make_tape_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant);
-Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex);
+// samples = k > 1: a supersampling context (maray_ctx_opts.samples): renders RGB8 only, geometry in output pixels
+Backend *make_tape_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples = 1);
+Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples = 1);
 std::string jit_source(const maray_program &prog, int min_waves = 0);   // PIXEL kernel source (__launch_bounds__(256, min_waves); 0 = the layout's default); throws Error
 std::string jit_source_rows(const maray_program &prog, uint32_t *n_chunks_out = nullptr, uint32_t *n_gjobs_out = nullptr);   // ROW kernel source (blockIdx.y = chunk)
+std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
+std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error
 // The two code objects of a program (jit_build.cpp): built once per process, kept on disk under MARAY_CACHE_DIR.
 struct JitCode {
@@ -99,4 +102,5 @@ bool any_guard_reads_y(const maray_program &P);
 struct maray_ctx {
     maray::Backend *backend = nullptr;
     uint32_t n_tex = 0;
+    uint32_t samples = 1;       // maray_ctx_opts.samples (0 taken as 1)
 };

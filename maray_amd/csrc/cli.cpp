@@ -1,6 +1,6 @@
 // cli.cpp — `maray` command line (product code).  Mirrors examples/maray.rs:
 //   maray -c N -i in.maray -o out.png [-t tex.png ...]        (:9-47)
-// plus --gpus N, --backend {tape,tape-smem,jit}.  -c/--cpus is parsed and
+// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing).  -c/--cpus is parsed and
 // ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +20,8 @@ static void usage()
             "  -o, --output <output>        Output file `*.png`\n"
             "  -t, --textures <textures>... Texture files (PNG, BMP, PNM, TGA, QOI, farbfeld, GIF, TIFF)\n"
             "      --gpus <n>               Number of MI355X devices (default: all)\n"
-            "      --backend <b>            auto | jit | tape | tape-smem (default: auto)\n");
+            "      --backend <b>            auto | jit | tape | tape-smem (default: auto)\n"
+            "  -s, --samples <k>            Anti-aliasing: k x k samples per pixel, box-filtered; k = 1, 2, 4 or 8 (default: 1)\n");
 }
 
 int main(int argc, char **argv)
@@ -38,6 +39,15 @@ int main(int argc, char **argv)
         else if (a == "-o" || a == "--output") output = val();
         else if (a == "-t" || a == "--textures") { while (i + 1 < argc && argv[i + 1][0] != '-') textures.push_back(argv[++i]); }
         else if (a == "--gpus") go.n_devices = (uint32_t)strtoul(val(), nullptr, 10);
+        else if (a == "-s" || a == "--samples") {
+            const std::string k = val();
+            if (k != "1" && k != "2" && k != "4" && k != "8") {
+                fprintf(stderr, "Error: --samples takes 1, 2, 4 or 8, not `%s`\n", k.c_str());
+                usage();
+                return 2;
+            }
+            go.samples = (uint32_t)(k[0] - '0');
+        }
         else if (a == "--backend") {
             std::string b = val();
             if (b == "tape") go.backend = MARAY_BACKEND_TAPE;

@@ -68,6 +68,7 @@ uint64_t scene_node_count(const Scene &s, int c);
 void scene_fix_color(Scene &s);                                          // var_fixer::fix_color
 Scene scene_fixed(const Scene &s);                                       // the same into a new scene (the lowering's input stays as it is: no copy of an 88,000-node scene first)
 void scene_rescale(Scene &s, uint32_t sx, uint32_t sy);
+void scene_supersample(Scene &s, uint32_t k);
 // simplify.cpp
 void scene_simplify(Scene &s, uint32_t flags = 0);                       // Expr::simplify on each channel (flags: MARAY_SIMPLIFY_*)
 // compress.cpp

@@ -95,6 +95,7 @@ struct IdleCtx {
 };
 struct GenEntry {
     std::string key;
+    uint32_t samples = 1;                     // the program is the scene supersampled k x k (maray_gen_opts.samples)
     maray_tape *tape = nullptr;
     std::multimap<int, IdleCtx> idle;         // per PHYSICAL device: contexts nobody is rendering with
     bool evicted = false;
@@ -184,6 +185,7 @@ int gen_guard(F f)
 extern "C" int maray_lower(const maray_scene *, const maray_lower_opts *, maray_tape **);
 namespace maray {
 void scene_cache_key(const maray_scene *s, uint64_t out[2]);      // api.cpp
+maray_scene *scene_supersampled_copy(const maray_scene *s, uint32_t k);      // api.cpp
 void hash128(const void *data, size_t n, uint64_t h[2]);
 }
 
@@ -206,7 +208,7 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
         for (auto &e : g_gen)
             for (auto &kv : e->idle)
                 t += e->key + " device " + std::to_string(kv.first) + " kernel " + maray_hip_kernel_name(kv.second.ctx) + " hint_mpixels " +
-                     std::to_string(kv.second.hint_mpixels) + "\n";
+                     std::to_string(kv.second.hint_mpixels) + (e->samples > 1 ? " samples " + std::to_string(e->samples) : std::string()) + "\n";
     }
     snprintf(out, cap, "%s", t.c_str());
     return MARAY_OK;
@@ -219,6 +221,11 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     if (!s || !rgb8) return fail_with(MARAY_E_ARG, "null argument");
     return gen_guard([&]() -> int {
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
+    // supersampling (include/maray_hip.h): the program is the scene on a k x k finer grid, its contexts reduce it
+    const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
+    if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail_with(MARAY_E_ARG, "samples must be 0, 1, 2, 4 or 8");
+    if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
+        return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
     if (!w || !h) return MARAY_OK;
     // the program of this call: remembered from an earlier one, or lowered now
     std::string key;
@@ -234,6 +241,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         char buf[64];
         snprintf(buf, sizeof buf, "%016llx%016llx/%u/%u", (unsigned long long)h[0], (unsigned long long)h[1], n_tex, opts ? opts->backend : (uint32_t)MARAY_BACKEND_AUTO);
         key = buf;
+        if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
     }
     int n_dev_avail = 0;
     maray_hip_device_count(&n_dev_avail);
@@ -282,12 +290,17 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
                 warm.emplace_back(host_pipe_prewarm, device_of(d), w, std::min(tile_rows, h), (int)std::min<size_t>(3, share[d].size() / 2));
         }
         maray_tape *tape = nullptr;
-        const int rc = maray_lower(s, nullptr, &tape);
+        int rc;
+        if (samples > 1) {
+            std::unique_ptr<maray_scene, void (*)(maray_scene *)> ss(scene_supersampled_copy(s, samples), maray_scene_free);
+            rc = maray_lower(ss.get(), nullptr, &tape);
+        } else
+            rc = maray_lower(s, nullptr, &tape);
         for (auto &t : warm) t.join();
         warm.clear();
         if (rc) return rc;
         auto fresh = std::make_shared<GenEntry>();
-        fresh->key = key; fresh->tape = tape;
+        fresh->key = key; fresh->tape = tape; fresh->samples = samples;
         entry = gen_cache_insert(fresh);
     } else pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
@@ -296,7 +309,8 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     maray_ctx_opts co;
     memset(&co, 0, sizeof co);
     co.backend = opts ? opts->backend : MARAY_BACKEND_AUTO;
-    co.hint_mpixels = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (((uint64_t)w * h / n_dev) >> 20) + 1);
+    co.samples = samples;
+    co.hint_mpixels = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (((uint64_t)w * h * samples * samples / n_dev) >> 20) + 1);      // samples it evaluates
 
     Progress P;
     struct TileUser { Progress *P; };

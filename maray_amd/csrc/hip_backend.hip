@@ -63,6 +63,13 @@ struct KArgs {
     uint32_t guard_sub;            // guard rectangles per 256-pixel tile (1, 2 or 4: a rectangle is 256 / guard_sub pixels wide)
 };
 
+// maray_tape_pixels_ss: k x k samples per output pixel; A's w, y0, blk_rows, blk_stride and guard_rows count samples.
+// (A struct of its own: the other kernels' arguments, and so their code, stay as they are.)
+struct KArgsSS {
+    KArgs A;
+    uint32_t ss, w_out;
+};
+
 typedef const __attribute__((address_space(4))) uint64_t *k_u64_ptr;   // constant address space: scalar loads
 typedef const __attribute__((address_space(4))) double *k_f64_ptr;
 
@@ -442,6 +449,80 @@ __global__ void __launch_bounds__(BLOCK) maray_tape_pixels(const KArgs A)
     }
 }
 
+// Supersampling PIXEL kernel: k = A.ss samples per output pixel and axis, their integer mean stored as RGB8.  The tiles
+// are those of maray_tape_pixels over the sample grid (w, y0, blk_rows, blk_stride and guard_rows count samples), but a
+// tile is 256 sample columns of one OUTPUT row r, and its wavefronts walk the k sample rows k r .. k r + k - 1 (launch
+// rows of the sample grid).  A pass is still 64 sample columns of one sample row: guard words, y values and SKIP regions
+// are wave-uniform as in the plain kernel, and each sample row takes the guard words of its own group of rows.  Tiles
+// start at multiples of 256 and k divides 64, so a pixel's k columns are k neighbouring lanes: each lane adds its cast
+// samples (R and G packed in one word: a sum is at most 255 k^2 <= 16320), the group adds across its lanes, and its
+// first lane stores (S + k^2 / 2) >> log2(k^2) -- an integer sum, the same in any order.
+template <bool TAPE_LDS>
+__global__ void __launch_bounds__(BLOCK) maray_tape_pixels_ss(const KArgsSS S)
+{
+    const KArgs &A = S.A;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint64_t *tape_lds = nullptr;
+    const double *consts_lds = nullptr;
+    double *slots;
+    if (TAPE_LDS) {
+        uint64_t *tl = (uint64_t *)smem;
+        double *cl = (double *)(smem + (size_t)A.n_ops * 8);
+        const uint64_t *src = A.xtape ? A.xtape : A.tape;
+        for (uint32_t i = threadIdx.x; i < A.n_ops; i += BLOCK) tl[i] = src[i];
+        for (uint32_t i = threadIdx.x; i < A.n_consts; i += BLOCK) cl[i] = A.consts[i];
+        tape_lds = tl; consts_lds = cl;
+        slots = (double *)(smem + ((size_t)A.n_ops + A.n_consts) * 8);
+        __syncthreads();
+    } else {
+        slots = (double *)smem;
+    }
+    const uint32_t spill_stride = gridDim.x * BLOCK;
+    double *spill_base = A.spill ? A.spill + (size_t)blockIdx.x * BLOCK + threadIdx.x : nullptr;
+    const uint32_t k = S.ss, shift = 2u * (uint32_t)__builtin_ctz(k), half = (k * k) >> 1;
+
+    __shared__ uint32_t drawn;
+    for (uint32_t wi = blockIdx.x; wi < A.n_tiles;) {
+        const uint32_t r = wi / A.tiles_per_row;                   // output row within this launch (uniform)
+        const uint32_t tx = wi - r * A.tiles_per_row;
+        const uint32_t x = tx * BLOCK + threadIdx.x;               // sample column
+        uint32_t s01 = 0, s2 = 0;
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t rs = r * k + j;                         // sample row within this launch
+            double o0 = 0.0, o1 = 0.0, o2 = 0.0;
+            uint32_t unused = 0;
+            Item I{};
+            I.yrow = A.yvals + (size_t)rs * A.n_yvals;
+            I.gk = A.guard_w32 ? A.gbits + (((size_t)(rs / A.guard_rows) * A.tiles_per_row + tx) * A.guard_sub +
+                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)((threadIdx.x * A.guard_sub) / BLOCK))) * A.guard_w32 : nullptr;
+            I.X = (double)x; I.Y = (double)(A.y0 + (rs / A.blk_rows) * A.blk_stride + rs % A.blk_rows);
+            if (A.xtape) {
+                slots[A.x_slot * BLOCK + threadIdx.x] = I.X;
+                slots[(A.x_slot + 1) * BLOCK + threadIdx.x] = I.Y;
+                run_xtape<TAPE_LDS, MODE_PIXEL>(A, A.xtape, A.n_ops, tape_lds, consts_lds, slots, I, o0, o1, o2, unused);
+            } else
+                run_tape<TAPE_LDS, MODE_PIXEL>(A, A.tape, A.n_ops, tape_lds, consts_lds, slots, spill_base, spill_stride, I, o0, o1, o2, unused);
+            s01 += mr_cast_u8(o0) | (mr_cast_u8(o1) << 16);
+            s2 += mr_cast_u8(o2);
+        }
+        for (uint32_t m = 1; m < k; m <<= 1) {                     // sums over the pixel's k lanes (cross-lane, no memory)
+            s01 += (uint32_t)__shfl_xor((int)s01, (int)m);
+            s2 += (uint32_t)__shfl_xor((int)s2, (int)m);
+        }
+        const uint32_t xo = x / k;
+        if ((threadIdx.x & (k - 1u)) == 0u && xo < S.w_out) {
+            unsigned char *q = A.rgb8 + ((size_t)r * S.w_out + xo) * 3;
+            q[0] = (unsigned char)(((s01 & 0xFFFFu) + half) >> shift);
+            q[1] = (unsigned char)(((s01 >> 16) + half) >> shift);
+            q[2] = (unsigned char)((s2 + half) >> shift);
+        }
+        __syncthreads();                                           // the previous draw has been read by every wave
+        if (threadIdx.x == 0) drawn = gridDim.x + atomicAdd(A.queue, 1u);
+        __syncthreads();
+        wi = drawn;
+    }
+}
+
 // ROW kernel: one work-item per image row evaluates the ROW section (in guard-bit mode: the part of it that the
 // operand y values depend on) and writes the row's y values.  Guards it evaluates are bounded over the whole row.
 // Tiny (rows x n_row_ops); slots live in LDS or spill.
@@ -620,6 +701,7 @@ struct TapeBackend final : Backend {
     uint32_t n_lds_slots = 0, lds_bytes = 0, blocks_per_cu = 1;
     uint32_t k_guard_h = 32, k_guard_sub = 4;           // MARAY_TAPE_GUARD_H / _W, read once in init()
     uint32_t row_lds_slots = 0, row_lds_bytes = 0;
+    uint32_t ss = 1;                    // samples per output pixel and axis (maray_tape_pixels_ss when > 1)
     std::string kname;
 
     ~TapeBackend() override {
@@ -634,8 +716,9 @@ struct TapeBackend final : Backend {
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
     }
 
-    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant) {
+    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples) {
         device = dev;
+        ss = samples;
         HIP_TRY(hipSetDevice(dev));
         HIP_TRY(hipGetDeviceProperties(&prop, dev));
         if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
@@ -768,7 +851,11 @@ struct TapeBackend final : Backend {
                 up(xb.data(), xb.size() * 8, (void **)&d_xtape_bits);
             }
         }
-        if (lds_variant) {
+        if (ss > 1) {
+            if (lds_variant) HIP_TRY(hipFuncSetAttribute((const void *)maray_tape_pixels_ss<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+            else HIP_TRY(hipFuncSetAttribute((const void *)maray_tape_pixels_ss<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+            kname = lds_variant ? "maray_tape_pixels_ss<true>" : "maray_tape_pixels_ss<false>";
+        } else if (lds_variant) {
             HIP_TRY(hipFuncSetAttribute((const void *)maray_tape_pixels<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
             kname = "maray_tape_pixels<true>";
         } else {
@@ -786,8 +873,13 @@ struct TapeBackend final : Backend {
         cap = n;
     }
 
-    void launch(uint32_t w, const RowBlocks &rb, unsigned char *d8, double *d64, hipStream_t st, bool rows_pass,
+    // w and rb: output pixels and rows.  Supersampling, the ROW and GUARDS passes and the pixel kernel's evaluations cover
+    // the k x k times larger sample grid (launch_geom), and the pixel kernel's tiles are counted in output rows.
+    void launch(uint32_t w_out, const RowBlocks &rb_out, unsigned char *d8, double *d64, hipStream_t st, bool rows_pass,
                 const unsigned *tile_list = nullptr, const double *ext_yvals = nullptr) {
+        if (ss > 1 && (d64 || tile_list || ext_yvals)) throw Error{MARAY_E_INTERNAL, "supersampling renders RGB8 with its own ROW pass only"};
+        const uint32_t w = w_out * ss;
+        const RowBlocks rb{rb_out.y0 * ss, rb_out.n_rows * ss, rb_out.block_rows * ss, rb_out.block_stride * ss};
         const uint32_t rows = rb.n_rows, y0 = rb.y0;
         if (!rows || !w) return;
         // scratch tables and work queues belong to the context: launches are ordered by their stream, and a launch on
@@ -873,7 +965,7 @@ struct TapeBackend final : Backend {
         A.xtape = bits ? d_xtape_bits : d_xtape_rows;
         A.queue = d_queue + 1;
         A.x_slot = x_slot;
-        const uint64_t tiles = (uint64_t)A.tiles_per_row * rows;
+        const uint64_t tiles = (uint64_t)A.tiles_per_row * rb_out.n_rows;
         if (tiles > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
         A.n_tiles = (uint32_t)tiles;
         const uint32_t per_cu = blocks_per_cu;
@@ -882,7 +974,10 @@ struct TapeBackend final : Backend {
             ensure(d_spill, spill_cap, std::max(spill_cap, (size_t)(P.n_pix_slots - n_lds_slots) * grid * BLOCK));
             A.spill = d_spill;
         }
-        if (tape_lds) hipLaunchKernelGGL(maray_tape_pixels<true>, dim3(grid), dim3(BLOCK), lds_bytes, st, A);
+        const KArgsSS S{A, ss, w_out};
+        if (ss > 1 && tape_lds) hipLaunchKernelGGL(maray_tape_pixels_ss<true>, dim3(grid), dim3(BLOCK), lds_bytes, st, S);
+        else if (ss > 1) hipLaunchKernelGGL(maray_tape_pixels_ss<false>, dim3(grid), dim3(BLOCK), lds_bytes, st, S);
+        else if (tape_lds) hipLaunchKernelGGL(maray_tape_pixels<true>, dim3(grid), dim3(BLOCK), lds_bytes, st, A);
         else hipLaunchKernelGGL(maray_tape_pixels<false>, dim3(grid), dim3(BLOCK), lds_bytes, st, A);
         HIP_TRY(hipGetLastError());
     }
@@ -937,12 +1032,12 @@ int hip_device_count()
     return n;
 }
 
-Backend *make_tape_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant)
+Backend *make_tape_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples)
 {
     if (hip_device_count() <= 0) throw Error{MARAY_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)"};
     auto *b = new TapeBackend();
     try {
-        b->init(device, prog, tex, n_tex, lds_variant);
+        b->init(device, prog, tex, n_tex, lds_variant, samples);
     } catch (...) {
         delete b;
         throw;

@@ -44,6 +44,10 @@ struct JitBackend final : Backend {
     std::shared_ptr<const JitCode> code;
     hipModule_t mod = nullptr, mod_rows = nullptr;
     hipFunction_t f_rows = nullptr, f_pix = nullptr, f_order = nullptr;
+    uint32_t ss = 1;                    // samples per output pixel and axis: > 1 launches maray_jit_pixels_ss (launch_ss)
+    std::shared_ptr<const std::vector<char>> code_ss;
+    hipModule_t mod_ss = nullptr;
+    hipFunction_t f_ss = nullptr;
     unsigned *d_order = nullptr; size_t order_cap = 0;
     uint64_t order_key[3] = {0, 0, 0};                     // the geometry d_order was computed for
     uint64_t seen_key[3] = {0, 0, 0};                      // the geometry of the previous launch
@@ -70,6 +74,7 @@ struct JitBackend final : Backend {
         delete slow;
         if (mod) (void)hipModuleUnload(mod);
         if (mod_rows) (void)hipModuleUnload(mod_rows);
+        if (mod_ss) (void)hipModuleUnload(mod_ss);
         (void)hipFree(d_flags);
         (void)hipFree(d_tex);
         for (auto p : d_tex_rgb) (void)hipFree(p);
@@ -79,8 +84,9 @@ struct JitBackend final : Backend {
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
     }
 
-    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex) {
+    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples) {
         device = dev;
+        ss = samples;
         // MARAY_TRACE_INIT=1: where the time of a context's creation goes (stderr)
         const bool trace = getenv("MARAY_TRACE_INIT") && getenv("MARAY_TRACE_INIT")[0] == '1';
         auto t_last = std::chrono::steady_clock::now();
@@ -120,7 +126,12 @@ struct JitBackend final : Backend {
         n_row_chunks = code->n_row_chunks; n_gjobs = code->n_gjobs;
         wide_all = jit_wide_general(prog, code->n_gwords);
         rows2 = code->rows2;
-        if (has_sin) slow = make_tape_backend(dev, prog, tex, n_tex, false);     // drains the tiles the pixel kernel defers; other programs never defer
+        if (ss > 1) {               // the supersampling kernel defers nothing: no interpreter behind it
+            code_ss = jit_code_samples(prog, ss);
+            HIP_TRY(hipModuleLoadData(&mod_ss, code_ss->data()));
+            HIP_TRY(hipModuleGetFunction(&f_ss, mod_ss, "maray_jit_pixels_ss"));
+            lap("load supersampling PIXEL module");
+        } else if (has_sin) slow = make_tape_backend(dev, prog, tex, n_tex, false);     // drains the tiles the pixel kernel defers; other programs never defer
         P = prog;
         P.consts = nullptr; P.row_ops = nullptr; P.pix_ops = nullptr;
         if (prog.n_row_ops) {
@@ -160,7 +171,62 @@ struct JitBackend final : Backend {
         cap = n;
     }
 
+    // Supersampling (maray_jit_pixels_ss): w_out and rb_out are output pixels and rows; the ROW stage covers the k x k times
+    // larger sample grid, the PIXEL kernel's grid counts output rows (65,534 per grid).  No launch order, nothing deferred.
+    void launch_ss(uint32_t w_out, const RowBlocks &rb_out, unsigned char *d8, hipStream_t st, bool rows_pass) {
+        const uint32_t w = w_out * ss;
+        const RowBlocks rb{rb_out.y0 * ss, rb_out.n_rows * ss, rb_out.block_rows * ss, rb_out.block_stride * ss};
+        const uint32_t rows_total = rb.n_rows;
+        unsigned y0 = rb.y0, blk_rows = rb.block_rows, blk_stride = rb.block_stride;
+        if (!rows_total || !w) return;
+        if (have_last && st != last_stream) {
+            HIP_TRY(hipEventRecord(handover, last_stream));
+            HIP_TRY(hipStreamWaitEvent(st, handover, 0));
+        }
+        last_stream = st; have_last = true;
+        unsigned yrows = (guard_rows > 1 && (blk_rows >= rows_total || blk_rows % guard_rows == 0)) ? guard_rows : 1u;
+        const uint32_t n_groups = (rows_total + yrows - 1) / yrows;
+        if (rows_pass) {
+            ensure(d_yvals, yvals_cap, (size_t)rows_total * std::max<uint32_t>(P.n_yvals, 1));
+            const size_t had = gbits_cap;
+            ensure(d_gbits, gbits_cap, (size_t)n_groups * ((w + 255) / 256) * guard_sub * std::max<uint32_t>(n_gwords, 1));
+            if (gbits_cap != had) HIP_TRY(hipMemsetAsync(d_gbits, 0, gbits_cap * sizeof(unsigned long long), st));
+        }
+        if (!d_yvals || !d_gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
+        unsigned n_yvals = P.n_yvals;
+        if (rows_pass && P.n_row_ops) {
+            unsigned rr = rows_total, ww = w;
+            unsigned n_tx_ = (w + 255) / 256 * guard_sub;
+            const uint64_t items = std::max<uint64_t>(n_gwords ? (uint64_t)n_groups * n_tx_ : 0, rows_total);
+            const unsigned bs = ROW_BLOCK;
+            if (items + bs > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
+            void *args[] = {&d_yvals, &d_gbits, &d_tex, &y0, &rr, &n_yvals, &ww, &n_tx_, &blk_rows, &blk_stride, &yrows};
+            unsigned gy = n_row_chunks + n_gjobs;
+            HIP_TRY(hipModuleLaunchKernel(f_rows, (unsigned)((items + bs - 1) / bs), gy, 1, bs, 1, 1, 0, st, args, nullptr));
+        }
+        // tiles per wavefront: the narrow rule of launch(), on the tiles of sample rows a launch evaluates
+        const unsigned n_tx = (w + 255) / 256;
+        const uint64_t n_tiles = (uint64_t)n_tx * rows_total, device_slots = (uint64_t)n_cu * 4 * 7;
+        unsigned tiles = n_tiles <= 4 * device_slots ? 1 : n_tiles <= 16 * device_slots ? 2 : 4;
+        if (k_tiles) tiles = std::min(64u, k_tiles);
+        tiles = std::max(1u, std::min(tiles, n_tx));
+        const unsigned gx = (n_tx + 4 * tiles - 1) / (4 * tiles);
+        for (uint32_t r0 = 0; r0 < rb_out.n_rows; r0 += 65534u) {
+            const uint32_t rows = std::min<uint32_t>(65534u, rb_out.n_rows - r0);
+            unsigned ww = w, row_base = r0, ntx = n_tx, wo = w_out;
+            const double *yv = d_yvals;
+            const unsigned long long *gb = d_gbits;
+            void *args[] = {&d8, &yv, &d_tex, &gb, &ntx, &ww, &y0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &wo};
+            HIP_TRY(hipModuleLaunchKernel(f_ss, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
+        }
+    }
+
     void launch(uint32_t w, const RowBlocks &rb, unsigned char *d8, double *d64, hipStream_t st, bool rows_pass) {
+        if (ss > 1) {
+            if (d64) throw Error{MARAY_E_INTERNAL, "supersampling renders RGB8 only"};
+            launch_ss(w, rb, d8, st, rows_pass);
+            return;
+        }
         const uint32_t rows_total = rb.n_rows, y0 = rb.y0;
         unsigned blk_rows = rb.block_rows, blk_stride = rb.block_stride;
         if (!rows_total || !w) return;
@@ -299,17 +365,17 @@ struct JitBackend final : Backend {
         return ms / (float)(reps > 0 ? reps : 1);
     }
 
-    const char *kernel_name() const override { return "maray_jit_pixels"; }
+    const char *kernel_name() const override { return ss > 1 ? "maray_jit_pixels_ss" : "maray_jit_pixels"; }
 };
 
 }   // namespace
 
-Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex)
+Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples)
 {
     if (hip_device_count() <= 0) throw Error{MARAY_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)"};
     auto *b = new JitBackend();
     try {
-        b->init(device, prog, tex, n_tex);
+        b->init(device, prog, tex, n_tex, samples);
     } catch (...) {
         delete b;
         throw;

@@ -476,4 +476,58 @@ std::shared_ptr<const JitCode> jit_code_for(const maray_program &prog)
     return fut.get();         // the contexts of a multi-GPU render: the first builds, the others wait here
 }
 
+// The supersampling PIXEL kernel of a program (jit_source_samples): built only when a context asks for k > 1, under a key of
+// its own -- the hash of its source (k is a literal of it), the compiler and the headers -- in the process and on disk
+// (<key>.mrss: the code object and a checksum).  The occupancy ladder of build_code: no scratch if any occupancy allows it.
+std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_ptr<const std::vector<char>>> built;
+    const std::string src = jit_source_samples(prog, k);
+    const std::string salt = key_salt() + "|supersampling " + std::to_string(k);
+    uint64_t h1 = fnv1a(salt.data(), salt.size(), 0xcbf29ce484222325ull), h2 = fnv1a(salt.data(), salt.size(), 0x84222325cbf29ce4ull);
+    h1 = fnv1a(src.data(), src.size() + 1, h1); h2 = fnv1a(src.data(), src.size() + 1, h2);
+    for (const char *hd : {maray_embedded_device_math_h, maray_embedded_libm_h, maray_embedded_libm_tables_h}) { h1 = fnv1a(hd, strlen(hd), h1); h2 = fnv1a(hd, strlen(hd), h2); }
+    const std::string key = hex128(h1, h2);
+    std::lock_guard<std::mutex> lk(m);          // (one build at a time: hiprtc serialises its compiles in a process anyway)
+    auto it = built.find(key);
+    if (it != built.end()) return it->second;
+    auto code = std::make_shared<std::vector<char>>();
+    const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrss";
+    bool have = false;
+    if (!path.empty())
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            std::vector<char> b;
+            char buf[65536];
+            for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) b.insert(b.end(), buf, buf + n);
+            fclose(f);
+            uint64_t sum = 0;
+            if (b.size() > 8) {
+                memcpy(&sum, b.data() + b.size() - 8, 8);
+                b.resize(b.size() - 8);
+                if (sum == fnv1a(b.data(), b.size(), 0xcbf29ce484222325ull)) { code->swap(b); have = true; }
+            }
+        }
+    if (!have) {
+        std::string log;
+        const int ladder[] = {0, 6, 4, 2};
+        for (int i = 0; i < 4; i++) {
+            jit_compile(i == 0 ? src : jit_source_samples(prog, k, ladder[i]), *code, log);
+            if (code_meta_uint(*code, ".private_segment_fixed_size") <= 0) break;
+        }
+        if (!path.empty()) {
+            mkdirs(dir);
+            const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
+            if (FILE *f = fopen(tmp.c_str(), "wb")) {
+                const uint64_t sum = fnv1a(code->data(), code->size(), 0xcbf29ce484222325ull);
+                const bool ok = fwrite(code->data(), 1, code->size(), f) == code->size() && fwrite(&sum, 8, 1, f) == 1;
+                if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
+            }
+        }
+    }
+    if (built.size() > 32) built.clear();
+    built[key] = code;
+    return code;
+}
+
 }   // namespace maray

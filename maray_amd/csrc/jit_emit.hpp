@@ -273,6 +273,7 @@ struct Emitter {
     std::vector<uint8_t> is_wide_op;             // out: per op of the last section(), was its value a pair
     std::vector<uint8_t> wide_hint;              // in: the same from a dry run (types the regions' variables, which are declared ahead of their last op)
     bool fuse_cmp = true;                       // Step(x + k) as one compare (MARAY_JIT_FUSE_CMP=0: ablation)
+    bool no_defer = false;                      // PIXEL: no tile goes to the interpreter -- an unbounded Step(Sin) takes the full path (maray_jit_pixels_ss)
     bool texel_once = false;                    // PIXEL: App ops of one image on the same coordinates share one mr_texel (descriptors mr_t<image> in scope)
     std::map<std::string, std::pair<std::string, uint32_t>> texels;      // (image, x, y, width) -> its variable and the block it was declared in
     const RedPlan *rplan = nullptr;             // PIXEL: the guarded OR-reductions of the section being emitted (null: walk the tree as written)
@@ -573,8 +574,8 @@ struct Emitter {
             case MARAY_OP_STEPSIN:
                 if ((aux & MARAY_AUX_SIN_BOUNDED) && sin_k >= 0 && td == "double") be = "mr_stepsin_bounded_mk(" + dbl(va, "m", i, 0) + ", mr_kc + " + std::to_string(sin_k) + ")";
                 else if (aux & MARAY_AUX_SIN_BOUNDED) be = "mr_stepsin_bounded_m(" + dbl(va, "m", i, 0) + ")";
-                else if (pixel && sin_k >= 0 && td == "double") e = "mr_stepsin_fast_k(" + quiet_arg(dbl(va, "m", i, 0)) + ", &mr_defer, mr_kc + " + std::to_string(sin_k) + ")";
-                else e = pixel ? "mr_stepsin_fast(" + quiet_arg(dbl(va, "m", i, 0)) + ", &mr_defer)" : "mr_stepsin(" + dbl(va, "m", i, 0) + ")";
+                else if (pixel && !no_defer && sin_k >= 0 && td == "double") e = "mr_stepsin_fast_k(" + quiet_arg(dbl(va, "m", i, 0)) + ", &mr_defer, mr_kc + " + std::to_string(sin_k) + ")";
+                else e = (pixel && !no_defer) ? "mr_stepsin_fast(" + quiet_arg(dbl(va, "m", i, 0)) + ", &mr_defer)" : "mr_stepsin(" + dbl(va, "m", i, 0) + ")";
                 break;
             case MARAY_OP_ADD:
                 // 1.0 + (-(b)) = NOT b

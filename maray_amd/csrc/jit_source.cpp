@@ -754,4 +754,152 @@ std::string jit_source(const maray_program &P, int min_waves)
 }
 
 
+// Source of the supersampling PIXEL kernel, maray_jit_pixels_ss (include/maray_hip.h, supersampling): the
+// narrow form of jit_source -- one sample per lane, the section's guard tests and branch tables as they are -- over the k w x k h
+// sample grid of a supersampled scene.  A wavefront owns a strip of `tiles` tiles of 256 sample columns of one OUTPUT row
+// (blockIdx.y); per pass of 64 sample columns it walks the k sample rows of that output row, each with its own y values
+// and the guard words of its own group of rows (a group may end inside a pixel's k rows), and adds the cast samples of a
+// lane in integer registers.  k divides 64: a pixel's k columns are k neighbouring lanes, summed across by shuffles; the
+// group's first lane stores the pixel's mean.  k is a literal of the source, so it is part of the code object's key.
+// Nothing is deferred to the interpreter: an unbounded Sin takes its full reduction here.  Separate from jit_source, whose
+// text this does not change.
+std::string jit_source_samples(const maray_program &P, uint32_t k, int min_waves)
+{
+    validate_program(P);
+    if (k != 2 && k != 4 && k != 8) throw Error{MARAY_E_ARG, "supersampling kernels exist for k = 2, 4 and 8"};
+    const int min_waves_arg = min_waves;
+    Emitter E(P);
+    E.min_region = 24;          // as jit_source
+    E.ybool = jit_bool_yvals(P);
+    E.ktab = true;
+    E.no_defer = true;
+    for (uint32_t i = 0; i < P.n_pix_ops && E.sin_k < 0; i++)
+        if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_STEPSIN) {
+            static const double sin_k[8] = {0x1.45f306dc9c883p-1, 0x1.8p52, 0x1.921fb58000000p+0, -0x1.dde973c000000p-27, -0x1.cb3b398000000p-55, -0x1.d747f23e32ed7p-83, 0x1p-70, 0.0};
+            E.sin_k = 0;
+            E.ktab_vals.assign(sin_k, sin_k + 8);
+        }
+    std::string &s = E.out;
+    const uint32_t n_ynum = numeric_yvals(P);
+    const uint32_t n_gwords = jit_guard_words(P);
+    E.ignore_row_guards = n_gwords == 0;
+    const GuardPlan plan = jit_guard_plan(P);
+    const GuardGeom geom = jit_guard_geom(P);
+    const uint32_t sub = 256u / geom.gw;
+    // every guard word of the rectangle at hand is a named SGPR pair, loaded per sample row and pass (scalar loads)
+    if (n_gwords) { E.guard_first = n_ynum; E.guard_words = n_gwords; E.plan = &plan; E.gw_inline_max = n_gwords; }
+    RedPlan reductions;
+    if (!E.ignore_row_guards) {
+        Emitter D(P);
+        D.ignore_row_guards = true;
+        D.min_region = E.min_region;
+        D.ybool = E.ybool;
+        D.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+        E.bool_hint = D.is_bool_op;
+        reductions = plan_reductions(P.pix_ops, P.n_pix_ops, P.n_pix_slots, D.is_bool_op, n_ynum, plan, E.ybool);
+    }
+    if (min_waves_arg == 0) min_waves = reductions.empty() ? 6 : 8;
+    const std::string K = std::to_string(k), nw = std::to_string(n_gwords);
+    const std::string esub = sub == 1 ? "0u" : sub == 2 ? "(e >> 1u)" : "e";       // rectangle of pass e inside its tile
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; supersampling " + K + " x " + K + " samples per pixel, one sample per lane\n"
+         "#define MR_VEC4 1\n"
+         "#include \"device_math.h\"\n"
+         "typedef const __attribute__((address_space(4))) double *mr_kptr;\n"
+         "typedef const __attribute__((address_space(4))) unsigned long long *mr_gptr;\n"
+         "__device__ inline mr_mask mr_lane64(unsigned long long v, unsigned lane)\n"
+         "{\n"
+         "    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, (int)lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), (int)lane);\n"
+         "    return ((mr_mask)hi << 32) | lo;\n"
+         "}\n/*MR_KTAB*/\n";
+    // w, y0, blk_rows, blk_stride: samples; row_base + blockIdx.y: the OUTPUT row of the call; yvals, gbits and rgb8 belong to the whole call
+    s += "extern \"C\" __global__ void __launch_bounds__(256, " + std::to_string(min_waves) +
+         ") maray_jit_pixels_ss(unsigned char *__restrict__ rgb8, const double *__restrict__ yvals, const MarayTex *__restrict__ tex,\n"
+         "                                                                       const unsigned long long *__restrict__ gbits, unsigned n_tx,\n"
+         "                                                                       unsigned w, unsigned y0, unsigned n_yvals, unsigned tiles,\n"
+         "                                                                       unsigned blk_rows, unsigned blk_stride, unsigned row_base, unsigned yrows,\n"
+         "                                                                       unsigned w_out)\n{\n"
+         "    const unsigned mr_wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), mr_lane = threadIdx.x & 63u;\n"
+         "    const unsigned tile0 = (blockIdx.x * 4u + mr_wv) * tiles;\n"
+         "    if (tile0 >= n_tx) return;\n"
+         "    const unsigned r = row_base + blockIdx.y;                               // output row of the call\n"
+         "    (void)tex; (void)gbits; (void)yrows;\n";
+    {
+        std::vector<uint8_t> used;
+        for (uint32_t i = 0; i < P.n_pix_ops; i++)
+            if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_APP) { const uint32_t img = MARAY_INS_AUX(P.pix_ops[i]) / 5u; if (used.size() <= img) used.resize(img + 1, 0); used[img] = 1; }
+        E.texel_once = !used.empty();
+        for (size_t img = 0; img < used.size(); img++)
+            if (used[img]) s += "    const MarayTex mr_t" + std::to_string(img) + " = tex[" + std::to_string(img) + "];\n";
+    }
+    s += "    for (unsigned t = 0; t < tiles; t++) {\n"
+         "    const unsigned x0 = (tile0 + t) * 256u;\n"
+         "    if (x0 >= w) break;\n"
+         "/*MR_KBASE*/"
+         "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n"
+         "    const unsigned x = x0 + 64u * e + mr_lane;                             // sample column\n"
+         "    const double X = (double)x;\n"
+         "    unsigned mr_s01 = 0u, mr_s2 = 0u;                                       // R | G << 16, B: at most 255 k^2 <= 16320 each\n"
+         "    (void)X;\n"
+         "    _Pragma(\"unroll 1\") for (unsigned mr_j = 0; mr_j < " + K + "u; mr_j++) {\n"
+         "    const unsigned rs = r * " + K + "u + mr_j;                                 // sample row of the call\n"
+         "    const double Y = (double)(blk_stride == 0u ? y0 + rs : y0 + (rs / blk_rows) * blk_stride + rs % blk_rows);\n"
+         "    (void)Y;\n"
+         "    unsigned long long mr_ybase = (unsigned long long)(yvals + (size_t)rs * n_yvals);\n"
+         "    asm volatile(\"\" : \"+s\"(mr_ybase));\n"
+         "    mr_kptr yv = (mr_kptr)mr_ybase;\n"
+         "    const __attribute__((address_space(4))) unsigned *yw = (const __attribute__((address_space(4))) unsigned *)yv;\n"
+         "    (void)yv; (void)yw;\n/*MR_KC*/";
+    if (n_gwords) {
+        s += "    unsigned long long mr_gb = (unsigned long long)(gbits + (((size_t)(rs >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * " + std::to_string(sub) +
+             "u + " + esub + ") * " + nw + "u);\n"
+             "    asm volatile(\"\" : \"+s\"(mr_gb));\n"
+             "    const mr_gptr mr_g = (mr_gptr)mr_gb;\n";
+        for (uint32_t j = 0; j < n_gwords; j++) {
+            const std::string q = std::to_string(j);
+            s += "    mr_mask gq" + q + " = mr_g[" + q + "];\n";
+        }
+    }
+    s += "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
+         "    float mr_defer = 0.0f;\n"
+         "    (void)mr_defer;\n";
+    E.td = "double"; E.tm = "mr_mask";
+    E.rplan = &reductions;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    E.rplan = nullptr;
+    s += "    mr_s01 += mr_cast_u8(o0) | (mr_cast_u8(o1) << 16);\n"
+         "    mr_s2 += mr_cast_u8(o2);\n"
+         "    }\n"
+         "    // a pixel's k sample columns are k neighbouring lanes: their sums, across lanes without memory\n"
+         "    _Pragma(\"unroll\") for (unsigned m = 1u; m < " + K + "u; m <<= 1) {\n"
+         "        mr_s01 += (unsigned)__shfl_xor((int)mr_s01, (int)m);\n"
+         "        mr_s2 += (unsigned)__shfl_xor((int)mr_s2, (int)m);\n"
+         "    }\n"
+         "    const unsigned xo = x / " + K + "u;\n"
+         "    if ((mr_lane & " + std::to_string(k - 1) + "u) == 0u && xo < w_out) {\n"
+         "        unsigned char *q = rgb8 + ((size_t)r * w_out + xo) * 3;\n"
+         "        q[0] = (unsigned char)(((mr_s01 & 0xFFFFu) + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
+         "        q[1] = (unsigned char)(((mr_s01 >> 16) + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
+         "        q[2] = (unsigned char)((mr_s2 + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
+         "    }\n"
+         "    }\n"
+         "    }\n}\n";
+    {
+        std::string tab;
+        if (!E.ktab_vals.empty()) {
+            tab += "__constant__ __attribute__((aligned(64))) double mr_kc_tab[" + std::to_string(E.ktab_vals.size()) + "] = {";
+            for (size_t j = 0; j < E.ktab_vals.size(); j++) { tab += (j % 6 ? " " : "\n    "); tab += lit(E.ktab_vals[j]); tab += ","; }
+            tab += "\n};\n";
+        }
+        s.replace(s.find("/*MR_KTAB*/"), 11, tab);
+        for (size_t at; (at = s.find("/*MR_KBASE*/")) != std::string::npos;)
+            s.replace(at, 12, E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n");
+        const std::string kc = E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
+                               "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
+                               "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n";
+        for (size_t at; (at = s.find("/*MR_KC*/")) != std::string::npos;) s.replace(at, 9, kc);
+    }
+    return s;
+}
+
 }   // namespace maray

@@ -354,6 +354,27 @@ void scene_fix_color(Scene &s)
 }
 
 // --------------------------------------------------------------- rescale ----
+namespace {
+// X -> nx and Y -> ny everywhere, Let definitions and Decor tokens included (nodes below n0 are the scene's own)
+void remap_xy(Scene &s, size_t n0, int32_t nx, int32_t ny)
+{
+    auto remap = [&](int32_t &i) {
+        if (i < 0 || (size_t)i >= n0) return;
+        if (s.nodes[i].tag == T_X) i = nx;
+        else if (s.nodes[i].tag == T_Y) i = ny;
+    };
+    for (size_t i = 0; i < n0; i++) { remap(s.nodes[i].a); remap(s.nodes[i].b); }
+    for (Ctx &c : s.ctxs) for (int32_t &d : c.defs) remap(d);
+    for (auto &tl : s.toklists) for (Token &t : tl) if (t.kind == 0) remap(t.expr);
+    for (int c = 0; c < 3; c++) remap(s.color[c]);
+}
+int32_t add_node(Scene &s, uint8_t tag, int32_t a = -1, int32_t b = -1, uint64_t u = 0)
+{
+    Node n; n.tag = tag; n.a = a; n.b = b; n.u = u;
+    return s.add(n);
+}
+}   // namespace
+
 void scene_rescale(Scene &s, uint32_t sx, uint32_t sy)
 {
     if (sx == 0 || sy == 0) throw Error{MARAY_E_ARG, "scale factors must be non-zero"};
@@ -369,15 +390,28 @@ void scene_rescale(Scene &s, uint32_t sx, uint32_t sy)
     };
     size_t n0 = s.nodes.size();
     int32_t nx = scaled(T_X, sx), ny = scaled(T_Y, sy);
-    auto remap = [&](int32_t &i) {
-        if (i < 0 || (size_t)i >= n0) return;
-        if (s.nodes[i].tag == T_X) i = nx;
-        else if (s.nodes[i].tag == T_Y) i = ny;
+    remap_xy(s, n0, nx, ny);
+    s.w = (uint32_t)w; s.h = (uint32_t)h;
+}
+
+// ----------------------------------------------------------- supersample ----
+// X -> X * (1/k) + -((k - 1) * (1/(2k))), Y the same, size * k: the scene evaluated at the integer sample index k px + i
+// sees px + (2i + 1 - k) / (2k), exactly (k a power of two: every constant, product and sum is a dyadic rational far inside
+// f64's precision for indices below 2^20).  k = 1 changes nothing.
+void scene_supersample(Scene &s, uint32_t k)
+{
+    if (k != 1 && k != 2 && k != 4 && k != 8) throw Error{MARAY_E_ARG, "samples must be 1, 2, 4 or 8"};
+    const uint64_t w = (uint64_t)s.w * k, h = (uint64_t)s.h * k;
+    if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "supersampled size overflows u32"};
+    if (k == 1) return;
+    auto centred = [&](uint8_t leaf) {
+        const int32_t scaled = add_node(s, T_MUL, add_node(s, leaf), add_node(s, T_RECIP, add_node(s, T_NAT, -1, -1, k)));
+        const int32_t off = add_node(s, T_MUL, add_node(s, T_NAT, -1, -1, k - 1), add_node(s, T_RECIP, add_node(s, T_NAT, -1, -1, 2ull * k)));
+        return add_node(s, T_ADD, scaled, add_node(s, T_NEG, off));
     };
-    for (size_t i = 0; i < n0; i++) { remap(s.nodes[i].a); remap(s.nodes[i].b); }
-    for (Ctx &c : s.ctxs) for (int32_t &d : c.defs) remap(d);
-    for (auto &tl : s.toklists) for (Token &t : tl) if (t.kind == 0) remap(t.expr);
-    for (int c = 0; c < 3; c++) remap(s.color[c]);
+    const size_t n0 = s.nodes.size();
+    const int32_t nx = centred(T_X), ny = centred(T_Y);
+    remap_xy(s, n0, nx, ny);
     s.w = (uint32_t)w; s.h = (uint32_t)h;
 }
 
