@@ -63,7 +63,6 @@ struct JitBackend final : Backend {
     uint32_t n_row_chunks = 1, n_gwords = 0, n_gjobs = 0, guard_rows = 1, guard_sub = 1;       // guard_sub: guard rectangles per 256-pixel tile
     uint32_t n_cu = 256;
     bool wide_all = false;              // the whole section runs four pixels per lane (jit_wide_general)
-    bool rows2 = false;                 // busy tiles two rows per wavefront (JitCode::rows2)
     unsigned k_tiles = 0;               // MARAY_JIT_TILES: tiles per wavefront (0 = by launch size), read once when the context is created
     bool has_sin = false;               // some Sin argument is not proven bounded: tiles may be deferred to `slow`
     hipStream_t last_stream = nullptr; bool have_last = false;      // the stream of the last launch (see launch())
@@ -125,7 +124,6 @@ struct JitBackend final : Backend {
         lap("load PIXEL module");
         n_row_chunks = code->n_row_chunks; n_gjobs = code->n_gjobs;
         wide_all = jit_wide_general(prog, code->n_gwords);
-        rows2 = code->rows2;
         if (ss > 1) {               // the supersampling kernel defers nothing: no interpreter behind it
             code_ss = jit_code_samples(prog, ss);
             HIP_TRY(hipModuleLoadData(&mod_ss, code_ss->data()));
@@ -265,9 +263,7 @@ struct JitBackend final : Backend {
         }
         // launch order of the PIXEL kernel (maray_jit_order): once per geometry, from the guard bits the ROW kernel just wrote;
         // a cached order is used by every launch of that geometry, with or without a ROW pass (time_rows)
-        // two rows per wavefront: when the launch's guard groups have an even number of rows (a pair then lies inside one group)
-        const unsigned rpw = (rows2 && yrows >= 2 && yrows % 2 == 0) ? 2u : 1u;
-        const uint32_t rows_per_grid = 65534u * rpw;                   // gridDim.y limit (an even number of rows either way: pairs, 32-row groups)
+        const uint32_t rows_per_grid = 65534u;                         // gridDim.y limit (an even number of rows: whole 32-row groups)
         // the order is a permutation of the launch's rows and every grid reads it from its first entry: a launch of more
         // than one grid takes none
         const unsigned *row_order = nullptr;
@@ -305,8 +301,6 @@ struct JitBackend final : Backend {
         const uint64_t device_slots = (uint64_t)n_cu * 4 * 7;
         unsigned tiles = wide_all ? (n_tiles <= device_slots ? 1 : n_tiles <= 4 * device_slots ? 2 : n_tiles <= 16 * device_slots ? 4 : 8)
                                   : (n_tiles <= 4 * device_slots ? 1 : n_tiles <= 16 * device_slots ? 2 : 4);
-        // two rows per wavefront: the strip is half as long, so that a wavefront owns as many pixels as it would with one row
-        if (rpw == 2 && tiles > 1) tiles /= 2;
         if (k_tiles) tiles = std::min(64u, k_tiles);
         if (n_gwords && n_gwords <= GW_INLINE_MAX) tiles = std::min(tiles, 64u / (n_gwords * guard_sub));      // a strip's guard words: one per lane
         tiles = std::max(1u, std::min(tiles, n_tx));
@@ -325,9 +319,9 @@ struct JitBackend final : Backend {
             unsigned ww = w, yy0 = y0, tile_base = r0 * n_tx, row_base = r0;
             const unsigned long long *gb = d_gbits;              // indexed by the row of the whole call
             unsigned ntx = n_tx;
-            unsigned rpw_ = rpw;
-            void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw_};
-            HIP_TRY(hipModuleLaunchKernel(f_pix, gx, (rows + rpw - 1) / rpw, 1, 256, 1, 1, 0, st, args, nullptr));
+            unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
+            void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw};
+            HIP_TRY(hipModuleLaunchKernel(f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
         if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, d_yvals);   // no-op unless a tile was deferred
     }

@@ -21,12 +21,6 @@ namespace maray {
 
 namespace {
 
-bool jit_row_guards_enabled()
-{
-    const char *e_ = getenv("MARAY_JIT_ROW_GUARDS");      // "0": compile the row-level SKIP ops away (ablation)
-    return !(e_ && e_[0] == '0');
-}
-
 // f64 values a VALU instruction encodes as an inline constant (gfx9: 0, +-0.5, +-1, +-2, +-4, 1/(2 pi))
 bool inline_f64(uint64_t bits)
 {
@@ -229,10 +223,9 @@ struct Emitter {
         std::string d;   // name / literal of the double, empty until materialised
         std::string b;   // name / literal of the lane mask (BOOL, NEGBOOL)
         uint32_t d_scope = 0;   // the region (C++ block) the materialised double was declared in; 0 = the kernel's own block
-        bool wide = false;      // two rows per lane (Emitter::pair): the value differs between the rows (a pair, mr_p / mr_pm); else one value serves both
         // value = x + k (cmp_kind 1) or -(x + k) (2) with k a finite constant: Step of it is the compare x >= -k (x <= -k), without
         // the addition (jit_emit: case MARAY_OP_STEP)
-        int cmp_kind = 0; std::string cmp_x; double cmp_k = 0.0; bool cmp_wide = false;
+        int cmp_kind = 0; std::string cmp_x; double cmp_k = 0.0;
         bool cst = false;       // a known constant (a literal of the tape, MR_NONE / MR_ALL as numbers, or arithmetic on such): cval
         double cval = 0.0;
     };
@@ -267,11 +260,6 @@ struct Emitter {
     std::string td = "double", tm = "mr_mask";  // types of a value / a boolean in the generated text ("mr_d" / "mr_m": four pixels per lane)
     std::vector<double> ktab_vals;
     std::unordered_map<uint64_t, uint32_t> ktab_block;
-    // Two rows per lane (device_math.h, mr_p / mr_pm): the NARROW passes of a wavefront that owns the same 64 pixels of two
-    // neighbouring rows.  y values and Y are pairs (yv / yw: row r, yv1 / yw1: row r + 1); an op is a pair when an operand is.
-    bool pair = false;
-    std::vector<uint8_t> is_wide_op;             // out: per op of the last section(), was its value a pair
-    std::vector<uint8_t> wide_hint;              // in: the same from a dry run (types the regions' variables, which are declared ahead of their last op)
     bool fuse_cmp = true;                       // Step(x + k) as one compare (MARAY_JIT_FUSE_CMP=0: ablation)
     bool no_defer = false;                      // PIXEL: no tile goes to the interpreter -- an unbounded Step(Sin) takes the full path (maray_jit_pixels_ss)
     bool texel_once = false;                    // PIXEL: App ops of one image on the same coordinates share one mr_texel (descriptors mr_t<image> in scope)
@@ -300,8 +288,6 @@ struct Emitter {
         vals.assign(n, Val());
         texels.clear();
         is_bool_op.assign(n, 0);
-        is_wide_op.assign(n, 0);
-        const std::string tdw = pair ? "mr_p" : td, tmw = pair ? "mr_pm" : tm;      // types of a pair
         std::vector<int> slot(n_slots, -1);
         int acc = -1;
         char name[48];
@@ -330,24 +316,19 @@ struct Emitter {
             }
             case MARAY_K_YVAL:
                 t.d = yv_name + "[" + std::to_string(idx) + "]";
-                if (pair) { t.d = "mr_p(" + t.d + ", " + yv_name + "1[" + std::to_string(idx) + "])"; t.wide = true; }
-                if (idx < ybool.size() && ybool[idx]) {
-                    t.kind = BOOL; t.b = "mr_ym(yw, " + std::to_string(idx) + "u)";
-                    if (pair) t.b = "mr_pm(" + t.b + ", mr_ym(yw1, " + std::to_string(idx) + "u))";
-                }
+                if (idx < ybool.size() && ybool[idx]) { t.kind = BOOL; t.b = "mr_ym(yw, " + std::to_string(idx) + "u)"; }
                 return &t;
             default:
                 if (idx == MARAY_SPEC_ACC) return &vals[acc];
                 static const char *const spec_name[] = {"X", "Y", "", "XMAX", "XMIN", "YMAX", "YMIN"};
                 t.d = spec_name[idx];
-                t.wide = pair && idx == MARAY_SPEC_Y;
                 return &t;
             }
         };
         // the double form of a value, materialising it once if needed
         // leaf: the block of a reduction's leaf (no variable, no else).  mask: the lanes on which what the region computes can
         // matter -- a wave-level region of booleans computes q of n = p AND q (p OR q): where p is 0 (1), n does not depend on q
-        struct Open { uint32_t end; bool as_bool; bool nz; uint32_t id; bool leaf; std::string mask; bool mask_wide; };
+        struct Open { uint32_t end; bool as_bool; bool nz; uint32_t id; bool leaf; std::string mask; };
         std::vector<Open> open;     // SKIPZ / SKIPNZ regions being emitted, innermost last
         uint32_t next_scope = 1;
         auto dbl = [&](Val *v, const char *hint, uint32_t i, int which) -> std::string {
@@ -358,7 +339,7 @@ struct Emitter {
             if (v->b == "MR_NONE") return v->d = v->kind == BOOL ? "0.0" : "(-0.0)";
             if (v->b == "MR_ALL") return v->d = v->kind == BOOL ? "1.0" : "(-1.0)";
             snprintf(name, sizeof name, "%s%u_%c", hint, i, which ? 'b' : 'a');
-            out += "    const " + (v->wide ? tdw : td) + " ";
+            out += "    const " + td + " ";
             out += name;
             out += v->kind == BOOL ? " = mr_pos(" + v->b + ");\n" : " = mr_neg01(" + v->b + ");\n";
             v->d = name;
@@ -382,7 +363,7 @@ struct Emitter {
             if (role == RedPlan::IGNORED_SKIP) continue;            // legal: an evaluator may ignore any SKIP op
             if (role == RedPlan::LEAF_SKIP) {
                 out_saved.swap(out);                                // (out_saved was empty: leaves do not nest)
-                open.push_back(Open{i + aux, true, false, next_scope++, true, std::string(), false});
+                open.push_back(Open{i + aux, true, false, next_scope++, true, std::string()});
                 ktab_block.clear();
                 continue;
             }
@@ -446,29 +427,24 @@ struct Emitter {
                         }
                     cond = "(" + (any.empty() ? std::string("0u") : any) + ") != 0u";
                 } else if (row_guard) {
-                    // a y value is uniform over the block: test its bits on the scalar unit, no ballot, no VALU (two rows per
-                    // lane: the region is entered when either row needs it)
+                    // a y value is uniform over the block: test its bits on the scalar unit, no ballot, no VALU
                     const std::string k = std::to_string(MARAY_REF_INDEX(gref));
-                    auto test = [&](const std::string &yw_) {
-                        return nz ? "!(" + yw_ + "[2 * " + k + " + 1] == 0x3ff00000u && " + yw_ + "[2 * " + k + "] == 0u)"
-                                  : "((" + yw_ + "[2 * " + k + " + 1] << 1) | " + yw_ + "[2 * " + k + "]) != 0u";
-                    };
-                    cond = pair ? "(" + test("yw") + ") || (" + test("yw1") + ")" : test("yw");
+                    cond = nz ? "!(yw[2 * " + k + " + 1] == 0x3ff00000u && yw[2 * " + k + "] == 0u)"
+                              : "((yw[2 * " + k + " + 1] << 1) | yw[2 * " + k + "]) != 0u";
                 } else if (as_bool) cond = nz ? "mr_any(~" + va->b + ")" : "mr_any(" + va->b + ")";      // a scalar compare
                 else cond = (nz ? "mr_any(mr_ne1(" : "mr_any(mr_ne0(") + dbl(va, "m", i, 0) + "))";
                 // several regions may end at one op (a row-level guard around a wave-level one): one variable
                 bool typed_bool = as_bool;
                 bool declared = false;
                 for (const Open &o : open) if (o.end == end && !o.leaf) { declared = true; typed_bool = o.as_bool; }
-                const bool wide_var = pair && (end >= wide_hint.size() || wide_hint[end]);      // (no hint: the typing run, whose text is not used)
-                if (!declared) out += typed_bool ? "    " + (wide_var ? tmw : tm) + " b" + std::string(name) + ";\n" : "    " + (wide_var ? tdw : td) + " " + std::string(name) + ";\n";
+                if (!declared) out += typed_bool ? "    " + tm + " b" + std::string(name) + ";\n" : "    " + td + " " + std::string(name) + ";\n";
                 // A region behind a rectangle guard is entered rarely (chess: 4 of the 15 a pass tests): unlikely, so that the block
                 // placement keeps the skip path as the fall-through and moves the bodies out of line (taken jumps stall on
                 // instruction fetch).  A wave-level region of the PIXEL section sits inside a shape whose guard let the wavefront
                 // in, and is entered nine times in ten (18 of 20 per pass): likely (board crop 82.3 -> 81.6 us).
                 out += "    if (__builtin_expect(" + cond + (pixel && !row_guard ? ", 1)) {\n" : ", 0)) {\n");
                 open.push_back(Open{end, typed_bool, nz, next_scope++, false,
-                                    (!row_guard && as_bool && va->kind == BOOL) ? (nz ? "~" + va->b : va->b) : std::string(), va->wide});
+                                    (!row_guard && as_bool && va->kind == BOOL) ? (nz ? "~" + va->b : va->b) : std::string()});
                 ktab_block.clear();
                 continue;
             }
@@ -492,7 +468,6 @@ struct Emitter {
             std::string e;      // double expression
             std::string be;     // bool expression
             const bool both_bool = va && vb && va->kind == BOOL && vb->kind == BOOL;
-            r.wide = pair && ((va && va->wide) || (vb && vb->wide));
             auto m_and = [](const std::string &a, const std::string &b) -> std::string {
                 if (a == "MR_NONE" || b == "MR_NONE") return "MR_NONE";
                 if (a == "MR_ALL") return b;
@@ -515,7 +490,7 @@ struct Emitter {
             // (1,000 triangles: 2.2 ms of the frame's 2.4).
             auto quiet_arg = [&](const std::string &x) -> std::string {
                 std::string m;
-                for (const Open &o : open) if (!o.mask.empty()) { m += (m.empty() ? "" : " & ") + o.mask; if (pair && o.mask_wide) r.wide = true; }      // (a pair of masks makes a pair of arguments)
+                for (const Open &o : open) if (!o.mask.empty()) m += (m.empty() ? "" : " & ") + o.mask;
                 return m.empty() ? x : "mr_sel0(" + m + ", " + x + ")";
             };
             // Arithmetic on known constants is done here (the lowering folded what it could see; what is left appears when a
@@ -554,7 +529,7 @@ struct Emitter {
             else if (role == RedPlan::INNER || role == RedPlan::ROOT) ;     // an OR of a reduction: below
             else
             switch (op) {
-            case MARAY_OP_MOV: { const bool w_ = r.wide; r = *va; r.wide = w_ || va->wide; break; }
+            case MARAY_OP_MOV: r = *va; break;
             case MARAY_OP_NEG:
                 if (va->kind == BOOL) { r.kind = NEGBOOL; r.b = va->b; }
                 else {
@@ -614,16 +589,16 @@ struct Emitter {
                 if (!(pixel && texel_once)) { e = "mr_app(tex, " + std::to_string(aux) + "u, " + ax + ", " + ay + ")"; break; }
                 // one texel, three channels: the coordinate work and the address are shared by the App ops of one image on the
                 // same two operands (device_math.h, mr_texel); the texel's variable is reused while its block is open
-                const std::string key = std::to_string(aux / 5u) + "|" + ax + "|" + ay + "|" + td + (r.wide ? "2" : "");
+                const std::string key = std::to_string(aux / 5u) + "|" + ax + "|" + ay + "|" + td;
                 auto it = texels.find(key);
                 bool in_scope = false;
                 if (it != texels.end()) { in_scope = it->second.second == 0; for (const Open &o : open) in_scope |= o.id == it->second.second; }
                 if (!in_scope) {
-                    const std::string tn = "mr_tl" + std::to_string(i);          // (not mr_tx<i>: mr_tx2 and mr_tx4 are types -- seed 8157 of a compile sweep had its lookup at op 4)
+                    const std::string tn = "mr_tl" + std::to_string(i);          // (not mr_tx<i>: mr_tx4 is a type -- seed 8157 of a compile sweep had its lookup at op 4)
                     // (four pixels per lane: both coordinates may be numbers that are not typed mr_d -- a constant and a y value, say: the texel is
                     // then the same for the four pixels, and without the conversions the call would resolve to the scalar form)
                     const bool four = td == "mr_d";
-                    out += "    const " + std::string(four ? "mr_tx4 " : r.wide ? "mr_tx2 " : "mr_tx ") + tn + " = mr_texel(mr_t" + std::to_string(aux / 5u) + ", tex, " +
+                    out += "    const " + std::string(four ? "mr_tx4 " : "mr_tx ") + tn + " = mr_texel(mr_t" + std::to_string(aux / 5u) + ", tex, " +
                            (four ? "mr_d(" + ax + "), mr_d(" + ay + ")" : ax + ", " + ay) + ");\n";
                     it = texels.insert_or_assign(key, std::make_pair(tn, open.empty() ? 0u : open.back().id)).first;
                 }
@@ -643,7 +618,7 @@ struct Emitter {
                     if (m != "MR_NONE") red_free[id].push_back(m);
                 }
                 if (role == RedPlan::INNER) {
-                    r.kind = REDPART; r.wide = pair;
+                    r.kind = REDPART;
                     vals[i] = r;
                     is_bool_op[i] = rbool;
                     acc = (int)i;
@@ -656,9 +631,8 @@ struct Emitter {
                 const RedPlan::Red &red = rp->reds[id];
                 const std::string rid = std::to_string(serial) + "_" + std::to_string(id);
                 const std::string racc = "mr_racc" + rid;
-                r.wide = pair;                  // the accumulator is a pair whatever the leaves are: a shape may show on one row only
                 if (rbool) {
-                    out += "    " + std::string(pair ? "mr_pm " : "mr_mask ") + racc + " = MR_NONE";
+                    out += "    mr_mask " + racc + " = MR_NONE";
                     for (const std::string &m : red_free[id]) out += " | " + m;
                     out += ";\n";
                 } else {
@@ -672,7 +646,7 @@ struct Emitter {
                         snprintf(hex, sizeof hex, "0x%llxull", (unsigned long long)mask);
                         all += std::string(all.empty() ? "" : " && ") + "(" + guard_word(wi) + " & " + hex + ") == " + hex;
                     }
-                    out += "    " + std::string(pair ? "mr_p " : "double ") + racc + " = (" + all + ") ? __builtin_nan(\"\") : 0.0;\n";
+                    out += "    double " + racc + " = (" + all + ") ? __builtin_nan(\"\") : 0.0;\n";
                     for (const std::string &m : red_free[id]) out += "    " + racc + " = mr_max(" + racc + ", " + m + ");\n";
                 }
                 for (uint32_t wi = 0; wi < guard_words; wi++) {
@@ -706,8 +680,7 @@ struct Emitter {
                         if (leaf_of_bit[b] < 0) continue;
                         std::string yf;              // the leaf's y factors: all must hold on this row
                         for (uint32_t yk : red.leaf_yfactors[leaf_of_bit[b]]) {
-                            const std::string k_ = std::to_string(yk);
-                            yf += (yf.empty() ? "" : " & ") + (pair ? "mr_pm(mr_ym(yw, " + k_ + "u), mr_ym(yw1, " + k_ + "u))" : "mr_ym(yw, " + k_ + "u)");
+                            yf += std::string(yf.empty() ? "" : " & ") + "mr_ym(yw, " + std::to_string(yk) + "u)";
                         }
                         out += "    mr_rl" + rid + "_" + std::to_string(leaf_of_bit[b]) + ": {\n" +
                                (yf.empty() ? std::string() : "    if (!mr_any(" + yf + ")) goto " + next + ";      // not on this row (frame 29.5 -> 29.0 us)\n") +
@@ -724,7 +697,6 @@ struct Emitter {
                 // the AND / OR that ends a region: assign the variable declared before the `if`
                 const Open o = open.back();
                 open.pop_back();
-                if (pair && i < wide_hint.size()) r.wide = wide_hint[i] != 0;      // (= the width its variable was declared with; the typing run has no hint and finds it)
                 if (o.as_bool && !be.empty()) {
                     out += "    b" + self + " = " + be + ";\n    } else b" + self + (o.nz ? " = MR_ALL;\n" : " = MR_NONE;\n");
                     r.kind = BOOL; r.b = "b" + self;
@@ -744,16 +716,16 @@ struct Emitter {
                                      : "    } else " + self + (o2.nz ? " = 1.0;\n" : " = 0.0;\n");
                 }
             } else if (be == "MR_NONE" || be == "MR_ALL") {
-                r.kind = BOOL; r.b = be; r.wide = false;      // a literal: later ops fold it
+                r.kind = BOOL; r.b = be;             // a literal: later ops fold it
             } else if (!be.empty() && be[0] != '(' && be[0] != '~' && be.compare(0, 3, "mr_") != 0) {
                 r.kind = BOOL; r.b = be;             // folded to one of its operands: an alias, no new variable
             } else if (!be.empty()) {
-                out += "    const " + (r.wide ? tmw : tm) + " b" + self + " = " + be + ";\n";
+                out += "    const " + tm + " b" + self + " = " + be + ";\n";
                 r.kind = BOOL; r.b = "b" + self;
             } else if (!e.empty() && folded) {
-                r.kind = DBL; r.d = e; r.cst = true; r.cval = fold_val; r.wide = false;      // a literal: no statement
+                r.kind = DBL; r.d = e; r.cst = true; r.cval = fold_val;      // a literal: no statement
             } else if (!e.empty()) {
-                out += "    const " + (r.wide ? tdw : td) + " " + self + " = " + e + ";\n";
+                out += "    const " + td + " " + self + " = " + e + ";\n";
                 r.kind = DBL; r.d = self;
             }
             if (role == RedPlan::LEAF_END) {
@@ -769,9 +741,8 @@ struct Emitter {
                 out_saved.clear();
                 ktab_block.clear();
                 r = Val();
-                r.kind = REDPART; r.wide = pair;
+                r.kind = REDPART;
                 vals[i] = r;
-                is_wide_op[i] = pair;
                 is_bool_op[i] = 1;
                 acc = (int)i;
                 if (dst != MARAY_DST_NONE) slot[dst] = (int)i;
@@ -779,7 +750,6 @@ struct Emitter {
             }
             vals[i] = r;
             is_bool_op[i] = r.kind == BOOL;
-            is_wide_op[i] = r.wide;
             acc = (int)i;
             if (dst != MARAY_DST_NONE) slot[dst] = (int)i;
         }

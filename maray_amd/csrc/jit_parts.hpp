@@ -27,9 +27,20 @@ struct GuardGeom { uint32_t gw, gh; };          // the rectangle a guard is boun
 
 std::vector<std::string> jit_option_words();                          // JIT_OPTIONS with MARAY_JIT_OPT / MARAY_JIT_EXTRA applied: what every compile is given (jit_build.cpp)
 bool may_defer_tiles(const maray_program &P);                       // some Sin whose argument is not provably bounded: tiles may go to the interpreter
-uint32_t jit_guard_words(const maray_program &P);                   // 64-bit words of guard bits per rectangle
-GuardGeom jit_guard_geom(const maray_program &P);
-bool jit_wide_general(const maray_program &P, uint32_t n_gwords);   // the general section four pixels per lane
-bool jit_rows2(const maray_program &P);                             // busy tiles two rows per wavefront (the launch passes rpw = 2 when its guard groups allow)
+// The generators' settings, one field per MARAY_JIT_* variable they honour (ablations and measurement knobs);
+// jit_knobs() reads the environment, the defaults are what an empty one gives.
+struct JitKnobs {
+    bool row_guards = true;             // MARAY_JIT_ROW_GUARDS=0: compile the row-level SKIP ops away
+    int guard_w = 0, guard_h = -1;      // MARAY_JIT_GUARD_W / _H as given (unset: 0 / -1): jit_guard_geom takes the values it knows
+    bool wide_app = true;               // MARAY_JIT_WIDE_APP=0: a program with texture lookups stays one pixel per lane
+    uint32_t min_region = 24;           // MARAY_JIT_MIN_REGION: wave-level SKIP ops of the PIXEL section over less than this are ignored
+    bool fuse_cmp = true;               // MARAY_JIT_FUSE_CMP=0: Step(x + k) as an addition and a compare
+    bool reduce = true;                 // MARAY_JIT_REDUCE=0: OR trees of guarded shapes walked as written
+    bool texel_once = true;             // MARAY_JIT_TEXEL_ONCE=0: a call of mr_app per App op
+};
+JitKnobs jit_knobs();
+uint32_t jit_guard_words(const maray_program &P, const JitKnobs &K = jit_knobs());      // 64-bit words of guard bits per rectangle
+GuardGeom jit_guard_geom(const maray_program &P, const JitKnobs &K = jit_knobs());
+bool jit_wide_general(const maray_program &P, uint32_t n_gwords, const JitKnobs &K = jit_knobs());   // the general section four pixels per lane
 
 }   // namespace maray

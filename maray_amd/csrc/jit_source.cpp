@@ -26,6 +26,23 @@ bool may_defer_tiles(const maray_program &P)
     return false;
 }
 
+// Every MARAY_JIT_* setting the generators read (each is part of the code key through the text it changes).  Read here and
+// nowhere else: a generator takes the struct, so what its text can depend on is what it is handed.
+JitKnobs jit_knobs()
+{
+    JitKnobs K;
+    auto off = [](const char *name) { const char *e_ = getenv(name); return e_ && e_[0] == '0'; };
+    K.row_guards = !off("MARAY_JIT_ROW_GUARDS");
+    if (const char *e_ = getenv("MARAY_JIT_GUARD_W")) K.guard_w = atoi(e_);
+    if (const char *e_ = getenv("MARAY_JIT_GUARD_H")) K.guard_h = std::max(0, atoi(e_));        // (set at all: jit_guard_geom keeps the height it is given)
+    K.wide_app = !off("MARAY_JIT_WIDE_APP");
+    if (const char *e_ = getenv("MARAY_JIT_MIN_REGION")) K.min_region = (uint32_t)atoi(e_);
+    K.fuse_cmp = !off("MARAY_JIT_FUSE_CMP");
+    K.reduce = !off("MARAY_JIT_REDUCE");
+    K.texel_once = !off("MARAY_JIT_TEXEL_ONCE");
+    return K;
+}
+
 // Which y values are booleans: a dry run of the emitter over the ROW section (its typing is the one the PIXEL section
 // will rely on).
 std::vector<uint8_t> jit_bool_yvals(const maray_program &P)
@@ -148,9 +165,9 @@ RowChunks split_row_tape(const maray_program &P, const RowTapeDeps &d, uint32_t 
 // How the specialised kernels use the row guards of a program: as bits, 64 per word, one set per
 // 256-pixel tile of a row (guard_words = 0: not at all -- none, far too many, or switched off).  Up to 12 words a tile's
 // words sit in SGPRs; beyond, a guard test reads its word from LDS.
-uint32_t jit_guard_words(const maray_program &P)
+uint32_t jit_guard_words(const maray_program &P, const JitKnobs &K)
 {
-    if (!jit_row_guards_enabled() || P.n_yvals == numeric_yvals(P)) return 0;
+    if (!K.row_guards || P.n_yvals == numeric_yvals(P)) return 0;
     const uint32_t nw = (jit_guard_plan(P).n_pos + 63) / 64;
     return nw <= 1024 ? std::max(nw, 1u) : 0;       // 1024 words x 8 tiles = 64 KB of LDS
 }
@@ -166,22 +183,48 @@ uint32_t jit_guard_words(const maray_program &P)
 // 64 x 16: 45.5 / 84; 64 x 32: 43.8 / 84; 64 x 64: 45.1 / 86; 64 x 128: 48.1 / 88).  MARAY_JIT_GUARD_W = 64 / 128 / 256,
 // MARAY_JIT_GUARD_H = 8 ... 128: measurement knobs.  A strip's words are held one per lane, so a tile's rectangles together
 // have to fit a wavefront's 64 lanes: a program with many guard words gets wider rectangles.
-GuardGeom jit_guard_geom(const maray_program &P)
+GuardGeom jit_guard_geom(const maray_program &P, const JitKnobs &K)
 {
     GuardGeom g{256u, 1u};
-    const uint32_t nw = jit_guard_words(P);
+    const uint32_t nw = jit_guard_words(P, K);
     if (!nw || any_guard_reads_y(P)) return g;
     g.gh = 32u;
-    const char *env_h = getenv("MARAY_JIT_GUARD_H");
-    if (env_h) { const int v = atoi(env_h); if (v == 8 || v == 16 || v == 32 || v == 64 || v == 128) g.gh = (uint32_t)v; }
+    const bool env_h = K.guard_h >= 0;
+    if (env_h) { const int v = K.guard_h; if (v == 8 || v == 16 || v == 32 || v == 64 || v == 128) g.gh = (uint32_t)v; }
     uint32_t want = 64u;
-    if (const char *e_ = getenv("MARAY_JIT_GUARD_W")) { const int v = atoi(e_); if (v == 64 || v == 128 || v == 256) want = (uint32_t)v; }
+    if (K.guard_w == 64 || K.guard_w == 128 || K.guard_w == 256) want = (uint32_t)K.guard_w;
     while (want < 256u && nw * (256u / want) > 64u) want *= 2u;
     if (want == 256u && !env_h) g.gh = 8u;      // wide rectangles gain nothing from height (chess, 256 x 8 / 256 x 32: 48.6 / 50.2 us per frame)
     g.gw = want;
     return g;
 }
 
+
+// Launch order of the PIXEL kernel: groups of rows by what they cost, dearest first, so that the tail of the launch is
+// made of cheap blocks.  Cost of a group = set bits in the guard words of its rectangles (shapes that may show there).
+// The bits are a function of the program and of the launch's geometry only: the order is computed once per geometry
+// (one block; rank by counting) and reused.  Rows of a group stay neighbours (they share guard words and cache lines).
+static std::string row_order_kernel(uint32_t n_gwords)
+{
+    return "extern \"C\" __global__ void __launch_bounds__(256) maray_jit_order(const unsigned long long *__restrict__ gbits, unsigned *__restrict__ order,\n"
+         "                                                                  unsigned rows, unsigned n_tx, unsigned yrows)\n{\n"
+         "    extern __shared__ unsigned mr_cost[];\n"
+         "    const unsigned n_groups = (rows + yrows - 1u) / yrows, n_full = rows / yrows, per = n_tx * " + std::to_string(n_gwords) + "u;\n"
+         "    for (unsigned g = threadIdx.x; g < n_groups; g += 256u) {\n"
+         "        unsigned c = 0;\n"
+         "        for (unsigned i = 0; i < per; i++) c += (unsigned)__builtin_popcountll(gbits[(size_t)g * per + i]);\n"
+         "        mr_cost[g] = c;\n"
+         "    }\n"
+         "    __syncthreads();\n"
+         "    for (unsigned g = threadIdx.x; g < n_full; g += 256u) {\n"
+         "        const unsigned c = mr_cost[g];\n"
+         "        unsigned rank = 0;\n"
+         "        for (unsigned h = 0; h < n_full; h++) rank += (mr_cost[h] > c || (mr_cost[h] == c && h < g)) ? 1u : 0u;\n"
+         "        for (unsigned i = 0; i < yrows; i++) order[rank * yrows + i] = g * yrows + i;\n"
+         "    }\n"
+         "    for (unsigned r = n_full * yrows + threadIdx.x; r < rows; r += 256u) order[r] = r;      // a partial last group stays last\n"
+         "}\n";
+}
 
 // Source of the ROW kernel, maray_jit_rows: one wavefront per block, blockIdx.y picks the job.
 //  y < n_chunks: chunk y of the ROW section, one work-item per row; writes the y values the pixel
@@ -199,9 +242,10 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
     validate_program(P);
     Emitter E(P);
     const RowTapeDeps deps = row_tape_deps(P);
-    const uint32_t n_ynum = numeric_yvals(P), n_gwords = jit_guard_words(P);
+    const JitKnobs K = jit_knobs();
+    const uint32_t n_ynum = numeric_yvals(P), n_gwords = jit_guard_words(P, K);
     const GuardPlan plan = jit_guard_plan(P);
-    const GuardGeom geom = jit_guard_geom(P);
+    const GuardGeom geom = jit_guard_geom(P, K);
     // wave-level SKIP ops of the ROW section: a wavefront's lanes are 64 rows, or the 64 rectangles of a band of rows, and
     // agree on the sky only; a job is one wavefront's chain, and every short region it has to test and branch around
     // lengthens it (chess, step minus pixel kernel in us, regions kept from 0 / 12 / 24 / 60 / 200 instructions / none:
@@ -301,162 +345,171 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
              "    ((unsigned char *)gbits)[(size_t)item * " + std::to_string(8 * n_gwords) + "u + (mr_job - " + std::to_string(chunks.size()) + "u)] = (unsigned char)gacc;\n";
     }
     s += "}\n";
-    // Launch order of the PIXEL kernel: groups of rows by what they cost, dearest first, so that the tail of the launch is
-    // made of cheap blocks.  Cost of a group = set bits in the guard words of its rectangles (shapes that may show there).
-    // The bits are a function of the program and of the launch's geometry only: the order is computed once per geometry
-    // (one block; rank by counting) and reused.  Rows of a group stay neighbours (they share guard words and cache lines).
-    if (n_gwords)
-        s += "extern \"C\" __global__ void __launch_bounds__(256) maray_jit_order(const unsigned long long *__restrict__ gbits, unsigned *__restrict__ order,\n"
-             "                                                                  unsigned rows, unsigned n_tx, unsigned yrows)\n{\n"
-             "    extern __shared__ unsigned mr_cost[];\n"
-             "    const unsigned n_groups = (rows + yrows - 1u) / yrows, n_full = rows / yrows, per = n_tx * " + std::to_string(n_gwords) + "u;\n"
-             "    for (unsigned g = threadIdx.x; g < n_groups; g += 256u) {\n"
-             "        unsigned c = 0;\n"
-             "        for (unsigned i = 0; i < per; i++) c += (unsigned)__builtin_popcountll(gbits[(size_t)g * per + i]);\n"
-             "        mr_cost[g] = c;\n"
-             "    }\n"
-             "    __syncthreads();\n"
-             "    for (unsigned g = threadIdx.x; g < n_full; g += 256u) {\n"
-             "        const unsigned c = mr_cost[g];\n"
-             "        unsigned rank = 0;\n"
-             "        for (unsigned h = 0; h < n_full; h++) rank += (mr_cost[h] > c || (mr_cost[h] == c && h < g)) ? 1u : 0u;\n"
-             "        for (unsigned i = 0; i < yrows; i++) order[rank * yrows + i] = g * yrows + i;\n"
-             "    }\n"
-             "    for (unsigned r = n_full * yrows + threadIdx.x; r < rows; r += 256u) order[r] = r;      // a partial last group stays last\n"
-             "}\n";
+    if (n_gwords) s += row_order_kernel(n_gwords);
     return s;
 }
 
 // The general section four pixels per lane: only a short program without guards whose ops are single instructions (no libm
 // bodies, no gathers).
-bool jit_wide_general(const maray_program &P, uint32_t n_gwords)        // n_gwords = jit_guard_words(P) (a walk over the ROW tape: the caller has it)
+bool jit_wide_general(const maray_program &P, uint32_t n_gwords, const JitKnobs &K)        // n_gwords = jit_guard_words(P) (a walk over the ROW tape: the caller has it)
 {
     bool heavy = false;
     // texture lookups do not keep a small program from the four-wide form (round 4: four gathers per lane in flight, the scalar
     // unit's share paid once per 256 pixels: config 5 41.5 -> 39.3 us); MARAY_JIT_WIDE_APP=0: one pixel per lane (ablation)
-    const char *e_ = getenv("MARAY_JIT_WIDE_APP");
-    const bool wide_app = !(e_ && e_[0] == '0');
     for (uint32_t i = 0; i < P.n_pix_ops; i++) {
         const uint32_t op = MARAY_INS_OP(P.pix_ops[i]);
-        heavy |= op == MARAY_OP_SIN || op == MARAY_OP_EXP || op == MARAY_OP_LN || op == MARAY_OP_STEPSIN || (op == MARAY_OP_APP && !wide_app);
+        heavy |= op == MARAY_OP_SIN || op == MARAY_OP_EXP || op == MARAY_OP_LN || op == MARAY_OP_STEPSIN || (op == MARAY_OP_APP && !K.wide_app);
     }
-    return n_gwords == 0 && !heavy && P.n_pix_slots <= (wide_app ? 12u : 6u) && P.n_pix_ops <= 256;
+    return n_gwords == 0 && !heavy && P.n_pix_slots <= (K.wide_app ? 12u : 6u) && P.n_pix_ops <= 256;
 }
 
-// Two rows per wavefront in the busy tiles (jit_source): a program whose shapes are guarded per rectangle of an even number
-// of rows, evaluated one pixel per lane.  MARAY_JIT_ROWS2=0 / 1: off / on (ablation; part of the code key like every MARAY_JIT_*).
-bool jit_rows2(const maray_program &P)
-{
-    const char *e_ = getenv("MARAY_JIT_ROWS2");
-    if (!(e_ && e_[0] == '1')) return false;
-    const uint32_t nw = jit_guard_words(P);
-    if (!nw || nw > GW_INLINE_MAX || jit_wide_general(P, nw)) return false;
-    const GuardGeom g = jit_guard_geom(P);
-    return g.gh >= 2 && g.gh % 2 == 0;
-}
+// ---- what the PIXEL generators share ---------------------------------------------------------------------------------------
+// The set-up of a PIXEL source, the same for every kernel form: the emitter configured for the section, the guard words'
+// plan and geometry, the typing of booleans, the reduction plan and the occupancy asked of the compiler.  A generator makes
+// one, writes its kernel's text into E.out around E.section(), and ends with splice_constants().
+namespace {
 
-// Source of the PIXEL kernel, maray_jit_pixels.  A wavefront owns a strip of `tiles` consecutive 256-pixel tiles of one
-// row (blockIdx.y); a block is four wavefronts = four neighbouring strips that share nothing but the instruction cache:
-// no staging, no barrier.  The strip's guard words arrive with one vector load (lane i = word i); per tile one scalar
-// test of a ballot picks the variant:
-//
-//  * WIDE, four pixels per lane (device_math.h, MR_VEC4: every value four f64, every boolean four lane masks).  The
-//    variant of a tile none of whose guard bits is set (every guarded region is the literal 0: for chess the background,
-//    one multiply), and the whole section of a small program without guards (config 2: six ops).  The scalar unit's
-//    share of a tile and the store's address arithmetic are paid once per 256 pixels, and a lane's four RGB8 pixels are
-//    12 contiguous bytes: one global_store_dwordx3, no cross-lane packing.  This is the path that is bound by the store
-//    (3 B per pixel) and little else.
-//  * NARROW, one pixel per lane, four passes of 64 pixels (a loop: the section's code exists once).  The variant of a
-//    tile where shapes may show.  Regions are entered per 64 pixels, where a wave-level SKIP op still finds all lanes
-//    agreeing; values are single f64.  The passes leave their packed pixels in LDS (same-wave traffic: no barrier) and
-//    the tile is stored like a wide one.
-//
-// When f64 planes are wanted too, element e of a wide lane l is pixel x0 + 64 e + l and every 64-pixel run is stored on
-// its own (24 B per lane, the coalesced pattern of the f64 planes).  A Sin whose argument is huge (|x| >= 105414350), inf
-// or NaN does not call the slow reduction here (a call site per Sin op would force every live value through scratch): the
-// tile is flagged instead and re-evaluated by the tape interpreter kernel afterwards, so the final raster is identical.
-// Layouts that were measured and lost (a wavefront per 64 pixels with guard words staged in LDS, a busy tile on the
-// block's four wavefronts side by side, persistent wavefronts, two pixels per lane, guard words by scalar loads, a
-// sky loop of its own ...) are history: DESIGN.md section 7.1, profiles/r2_ablations.jsonl.
-std::string jit_source(const maray_program &P, int min_waves)
-{
-    validate_program(P);
-    // 6 waves per SIMD, i.e. up to 102 SGPRs (at 8 the compiler gets 76 and spills ~400 of them to VGPR lanes, in the skeleton
-    // of bit tests and branches every pass walks; chess needs 38 VGPRs either way and runs 7 waves per SIMD)
-    const int min_waves_arg = min_waves;
-    Emitter E(P);
-    // Wave-level SKIP ops over fewer than 12 instructions' worth of ops are ignored: a busy tile is bound by the scalar unit
-    // (branches, bit tests, mask algebra: 0.59 SALU instructions per cycle and CU against 35 % VALU issue), and a short
-    // region's test and branch cost that unit more than its ops cost the vector one (chess board, us per 16.7 Mpx, with
-    // guards per 256 x 8 pixels: none ignored 111, 24: 104; with guards per 64 x 32: 8 / 12 / 16 ... 32 / 64 / 200:
-    // 83.3 / 82.4 / 84.7 / 85.4 / 128).
-    E.min_region = 24;          // (round 4: from 12; pixel kernel / step / board 27.34 / 34.02 / 60.9 against 27.6 / 34.2-34.4 / 61.2 us, the same sign in round 3's table)
-    if (const char *e_ = getenv("MARAY_JIT_MIN_REGION")) E.min_region = (uint32_t)atoi(e_);
-    E.ybool = jit_bool_yvals(P);
-    if (const char *e_ = getenv("MARAY_JIT_FUSE_CMP")) E.fuse_cmp = e_[0] != '0';
-    E.ktab = true;
-    for (uint32_t i = 0; i < P.n_pix_ops && E.sin_k < 0; i++)
-        if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_STEPSIN) {
-            // the first cache line of the table: what every leaf with a texture reads
-            static const double sin_k[8] = {0x1.45f306dc9c883p-1, 0x1.8p52, 0x1.921fb58000000p+0, -0x1.dde973c000000p-27, -0x1.cb3b398000000p-55, -0x1.d747f23e32ed7p-83, 0x1p-70, 0.0};
-            E.sin_k = 0;
-            E.ktab_vals.assign(sin_k, sin_k + 8);
-        }
-    std::string &s = E.out;
-    const uint32_t n_ynum = numeric_yvals(P);
-    const uint32_t n_gwords = jit_guard_words(P);
-    E.ignore_row_guards = n_gwords == 0;
-    const GuardPlan plan = jit_guard_plan(P);
-    const GuardGeom geom = jit_guard_geom(P);
-    const uint32_t sub = 256u / geom.gw;                   // guard rectangles per 256-pixel tile (> 1: their words are taken per pass)
-    const std::string tw = std::to_string(sub * n_gwords);  // guard words per tile
-    if (n_gwords) { E.guard_first = n_ynum; E.guard_words = n_gwords; E.plan = &plan; E.gw_inline_max = GW_INLINE_MAX; }
+struct PixelSetup {
+    Emitter E;
+    const uint32_t n_ynum, n_gwords;
+    const GuardPlan plan;
+    const GuardGeom geom;
+    const uint32_t sub;                 // guard rectangles per 256-pixel tile (> 1: their words are taken per pass)
     RedPlan reductions;
-    if (!E.ignore_row_guards) {         // dry run: which ops yield lane masks
-        Emitter D(P);
-        D.ignore_row_guards = true;
-        D.min_region = E.min_region;
-        D.ybool = E.ybool;
-        D.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        E.bool_hint = D.is_bool_op;
-        // OR trees of guarded shapes: evaluated from their set guard bits (RedPlan).  MARAY_JIT_REDUCE=0: walked as written (ablation)
-        const char *e_ = getenv("MARAY_JIT_REDUCE");
-        if (!(e_ && e_[0] == '0')) reductions = plan_reductions(P.pix_ops, P.n_pix_ops, P.n_pix_slots, D.is_bool_op, n_ynum, plan, E.ybool);
+    int min_waves;
+    std::vector<uint8_t> tex_used;      // per image: some App op of the section samples it
+
+    PixelSetup(const maray_program &P, const JitKnobs &K, int min_waves_arg)
+        : E(P), n_ynum(numeric_yvals(P)), n_gwords(jit_guard_words(P, K)), plan(jit_guard_plan(P)), geom(jit_guard_geom(P, K)), sub(256u / geom.gw), min_waves(min_waves_arg)
+    {
+        // Wave-level SKIP ops over fewer than 12 instructions' worth of ops are ignored: a busy tile is bound by the scalar unit
+        // (branches, bit tests, mask algebra: 0.59 SALU instructions per cycle and CU against 35 % VALU issue), and a short
+        // region's test and branch cost that unit more than its ops cost the vector one (chess board, us per 16.7 Mpx, with
+        // guards per 256 x 8 pixels: none ignored 111, 24: 104; with guards per 64 x 32: 8 / 12 / 16 ... 32 / 64 / 200:
+        // 83.3 / 82.4 / 84.7 / 85.4 / 128).
+        // (round 4: 24, from 12; pixel kernel / step / board 27.34 / 34.02 / 60.9 against 27.6 / 34.2-34.4 / 61.2 us, the same sign in round 3's table)
+        E.min_region = K.min_region;
+        E.ybool = jit_bool_yvals(P);
+        E.fuse_cmp = K.fuse_cmp;
+        E.ktab = true;
+        for (uint32_t i = 0; i < P.n_pix_ops && E.sin_k < 0; i++)
+            if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_STEPSIN) {
+                // the first cache line of the table: what every leaf with a texture reads
+                static const double sin_k[8] = {0x1.45f306dc9c883p-1, 0x1.8p52, 0x1.921fb58000000p+0, -0x1.dde973c000000p-27, -0x1.cb3b398000000p-55, -0x1.d747f23e32ed7p-83, 0x1p-70, 0.0};
+                E.sin_k = 0;
+                E.ktab_vals.assign(sin_k, sin_k + 8);
+            }
+        E.ignore_row_guards = n_gwords == 0;
+        if (n_gwords) { E.guard_first = n_ynum; E.guard_words = n_gwords; E.plan = &plan; E.gw_inline_max = GW_INLINE_MAX; }
+        if (!E.ignore_row_guards) {         // dry run: which ops yield lane masks
+            Emitter D(P);
+            D.ignore_row_guards = true;
+            D.min_region = E.min_region;
+            D.ybool = E.ybool;
+            D.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+            E.bool_hint = D.is_bool_op;
+            // OR trees of guarded shapes: evaluated from their set guard bits (RedPlan).  MARAY_JIT_REDUCE=0: walked as written (ablation)
+            if (K.reduce) reductions = plan_reductions(P.pix_ops, P.n_pix_ops, P.n_pix_slots, D.is_bool_op, n_ynum, plan, E.ybool);
+        }
+        // Occupancy asked of the compiler.  Walking a tree of bit tests needs the SGPRs of 6 waves per SIMD (up to 102; at 8 the
+        // compiler gets 76-80 and spilled ~400 of them to VGPR lanes, in the skeleton of bit tests and branches every pass walked;
+        // chess needs 38 VGPRs either way); with the tree evaluated as a reduction chess fits 78 and runs 8 (frame 29.9 -> 29.5 us,
+        // sky 12.3 -> 11.5, board 67.1 -> 65.1)
+        if (min_waves_arg == 0) min_waves = reductions.empty() ? 6 : 8;
+        for (uint32_t i = 0; i < P.n_pix_ops; i++)
+            if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_APP) { const uint32_t img = MARAY_INS_AUX(P.pix_ops[i]) / 5u; if (tex_used.size() <= img) tex_used.resize(img + 1, 0); tex_used[img] = 1; }
+        E.texel_once = !tex_used.empty() && K.texel_once;       // MARAY_JIT_TEXEL_ONCE=0: a call of mr_app per App op (= round 3; ablation)
     }
-    // Occupancy asked of the compiler.  Walking a tree of bit tests needs the SGPRs of 6 waves per SIMD (up to 102; at 8 the
-    // compiler gets 80 and spilled ~400 of them to VGPR lanes, in the skeleton every pass walked); with the tree evaluated as
-    // a reduction chess fits 78 and runs 8 (frame 29.9 -> 29.5 us, sky 12.3 -> 11.5, board 67.1 -> 65.1)
-    if (min_waves_arg == 0) min_waves = reductions.empty() ? 6 : 8;
-    // two rows per wavefront: twice the lane masks alive (chess at 8 waves: 240 SGPRs spilled to VGPR lanes); MARAY_JIT_ROWS2_WAVES: ablation
-    if (min_waves_arg == 0 && jit_rows2(P)) { min_waves = 6; if (const char *e_ = getenv("MARAY_JIT_ROWS2_WAVES")) if (atoi(e_) > 0) min_waves = atoi(e_); }
-    const bool defer = may_defer_tiles(P);
-    const std::string nw = std::to_string(n_gwords);
-    // a strip's guard words: one vector load per wavefront (lane i holds word i), then v_readlane per tile or pass -- one
-    // memory latency per strip instead of one per tile
-    const bool gw_vgpr = n_gwords && n_gwords <= GW_INLINE_MAX;
-    const bool wide_general = jit_wide_general(P, n_gwords);
-    // Two rows per wavefront (jit_rows2): the busy tiles' passes take the same 64 pixels of two neighbouring rows of one guard
-    // rectangle -- the same shapes are entered for both, so a shape's dispatch, its constants and its x-only arithmetic are
-    // paid once per 128 pixels (device_math.h, mr_p).  Needs guards bounded over rectangles of an even number of rows.
-    const bool pair = jit_rows2(P);
-    const std::string esub = "(e >> " + std::to_string(sub == 4 ? 0 : 1) + "u)";       // rectangle of pass e inside its tile
-    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
-         std::to_string(P.n_pix_ops) + " ops; general variant " + (wide_general ? "four pixels per lane" : "one pixel per lane, four passes per tile") + "\n"
-         "#define MR_VEC4 1\n"
-         "__shared__ unsigned mr_slow[4];           // per wavefront: some Sin of the tile at hand needs the slow path\n"
-         "__shared__ unsigned mr_tp[4 * " + std::string(pair ? "512" : "256") + "];       // per wavefront: the packed pixels of a tile's four passes (of both rows)\n"
-         "__device__ inline double mr_defer_sin(double) { ((volatile unsigned *)mr_slow)[threadIdx.x >> 6] = 1u; return 0.0; }\n"
-         "#define MR_SIN_HUGE(x) mr_defer_sin(x)   // plain Sin ops: flag the tile from the (rare) branch\n"
-         "#include \"device_math.h\"\n"
-         "typedef const __attribute__((address_space(4))) double *mr_kptr;\n"
-         "struct __attribute__((aligned(4))) mr_u3 { unsigned a, b, c; };\n"
-         "struct __attribute__((aligned(16))) mr_u4 { unsigned a, b, c, d; };\n"
-         "__device__ inline mr_mask mr_lane64(unsigned long long v, unsigned lane)      // lane `lane` (wave-uniform) of a per-lane 64-bit value -> SGPR pair\n"
-         "{\n"
-         "    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, (int)lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), (int)lane);\n"
-         "    return ((mr_mask)hi << 32) | lo;\n"
-         "}\n/*MR_KTAB*/\n";
-    s += "extern \"C\" __global__ void __launch_bounds__(256, " + std::to_string(min_waves) +
+    PixelSetup(const PixelSetup &) = delete;        // (E.plan points into this object)
+
+    // the descriptors of the textures the section samples: scalar loads, once per wavefront
+    std::string texture_loads() const
+    {
+        std::string s;
+        for (size_t img = 0; img < tex_used.size() && E.texel_once; img++)
+            if (tex_used[img]) s += "    const MarayTex mr_t" + std::to_string(img) + " = tex[" + std::to_string(img) + "];\n";
+        return s;
+    }
+
+    // Ends a source: E.out's three markers become what the section turned out to need.  /*MR_KTAB*/: `device_text` (functions
+    // of the kernel form that use the types above the marker) and the constant table; /*MR_KBASE*/: the table's address,
+    // taken once per tile; /*MR_KC*/: that address made opaque once per pass (see PASS_TABLES).
+    std::string splice_constants(const std::string &device_text)
+    {
+        std::string &s = E.out;
+        std::string tab = device_text;
+        if (!E.ktab_vals.empty()) {
+            tab += "__constant__ __attribute__((aligned(64))) double mr_kc_tab[" + std::to_string(E.ktab_vals.size()) + "] = {";
+            for (size_t j = 0; j < E.ktab_vals.size(); j++) { tab += (j % 6 ? " " : "\n    "); tab += lit(E.ktab_vals[j]); tab += ","; }
+            tab += "\n};\n";
+        }
+        s.replace(s.find("/*MR_KTAB*/"), 11, tab);
+        for (size_t at; (at = s.find("/*MR_KBASE*/")) != std::string::npos;)
+            s.replace(at, 12, E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n");
+        const std::string kc = E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
+                               "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
+                               "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n";
+        for (size_t at; (at = s.find("/*MR_KC*/")) != std::string::npos;) s.replace(at, 9, kc);
+        return s;
+    }
+};
+
+}   // namespace
+
+// What opens a pass of any width: the y values and the constant table behind addresses made opaque (LICM would hoist every
+// constant and y value out of the loops and spill them).  `mr_ybase` is declared by the kernel form in front of this.
+static const char PASS_TABLES[] =
+    "    asm volatile(\"\" : \"+s\"(mr_ybase));\n"
+    "    mr_kptr yv = (mr_kptr)mr_ybase;\n"
+    "    const __attribute__((address_space(4))) unsigned *yw = (const __attribute__((address_space(4))) unsigned *)yv;\n"
+    "    (void)yv; (void)yw;\n/*MR_KC*/";
+
+// ---- maray_jit_pixels: the pieces of its text ---------------------------------------------------------------------------------
+// The kernel once took two rows per wavefront in its busy tiles (measured, lost, removed).  The `rows` and
+// `rpw` parameters, the two comment lines about rpw = 2 in PIXELS_HEAD and the "(of both rows)" in PIXELS_PROLOGUE's mr_tp
+// comment are what is left of it in the emitted text: the host passes rpw = 1, and they go with the next change that is
+// meant to change these kernels (and measures them), not with one that must keep their text.
+static const char PIXELS_PROLOGUE[] =
+    "#define MR_VEC4 1\n"
+    "__shared__ unsigned mr_slow[4];           // per wavefront: some Sin of the tile at hand needs the slow path\n"
+    "__shared__ unsigned mr_tp[4 * 256];       // per wavefront: the packed pixels of a tile's four passes (of both rows)\n"
+    "__device__ inline double mr_defer_sin(double) { ((volatile unsigned *)mr_slow)[threadIdx.x >> 6] = 1u; return 0.0; }\n"
+    "#define MR_SIN_HUGE(x) mr_defer_sin(x)   // plain Sin ops: flag the tile from the (rare) branch\n"
+    "#include \"device_math.h\"\n"
+    "typedef const __attribute__((address_space(4))) double *mr_kptr;\n"
+    "struct __attribute__((aligned(4))) mr_u3 { unsigned a, b, c; };\n"
+    "struct __attribute__((aligned(16))) mr_u4 { unsigned a, b, c, d; };\n"
+    "__device__ inline mr_mask mr_lane64(unsigned long long v, unsigned lane)      // lane `lane` (wave-uniform) of a per-lane 64-bit value -> SGPR pair\n"
+    "{\n"
+    "    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, (int)lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), (int)lane);\n"
+    "    return ((mr_mask)hi << 32) | lo;\n"
+    "}\n/*MR_KTAB*/\n";
+
+// one 64-pixel run: f64 planes (24 B per lane) and / or RGB8 (48 lanes assemble a dword each from two neighbours'
+// packed colours; ragged ends and unaligned rows store bytes)
+static const char MR_STORE_RUN[] =
+    "__device__ inline void mr_store_run(unsigned char *__restrict__ rgb8, double *__restrict__ rgb64, size_t row_px, unsigned xw, unsigned w,\n"
+    "                                    unsigned lane, unsigned src, unsigned shift, unsigned pk, double c0, double c1, double c2)\n{\n"
+    "    const unsigned x = xw + lane;\n"
+    "    if (rgb64 && x < w) { const size_t p = (row_px + x) * 3; rgb64[p] = c0; rgb64[p + 1] = c1; rgb64[p + 2] = c2; }\n"
+    "    if (rgb8) {\n"
+    "        unsigned char *wave_out = rgb8 + (row_px + xw) * 3;\n"
+    "        if (xw + 64u <= w && ((size_t)wave_out & 3u) == 0u) {                // wave-uniform\n"
+    "            const unsigned pa = (unsigned)__builtin_amdgcn_ds_bpermute((int)(src * 4u), (int)pk);\n"
+    "            const unsigned pb = (unsigned)__builtin_amdgcn_ds_bpermute((int)(src * 4u + 4u), (int)pk);\n"
+    "            const unsigned dw = (unsigned)((((unsigned long long)pb << 24) | pa) >> shift);\n"
+    "            if (lane < 48u) ((unsigned *)wave_out)[lane] = dw;\n"
+    "        } else if (x < w) {\n"
+    "            unsigned char *q = rgb8 + (row_px + x) * 3;\n"
+    "            q[0] = (unsigned char)pk; q[1] = (unsigned char)(pk >> 8); q[2] = (unsigned char)(pk >> 16);\n"
+    "        }\n"
+    "    }\n"
+    "}\n";
+
+// the kernel's parameters and what a wavefront works out once: its strip, its row, the row's y values and Y
+static std::string pixels_head(int min_waves)
+{
+    return "extern \"C\" __global__ void __launch_bounds__(256, " + std::to_string(min_waves) +
          ") maray_jit_pixels(unsigned char *__restrict__ rgb8, double *__restrict__ rgb64,\n"
          "                                                                    const double *__restrict__ yvals, const MarayTex *__restrict__ tex,\n"
          "                                                                    unsigned *__restrict__ tile_list, unsigned tile_base,\n"
@@ -473,112 +526,127 @@ std::string jit_source(const maray_program &P, int min_waves)
          "    // launch's guard groups have an even number of rows): this wavefront owns rows r and r + 1 of one group\n"
          "    const unsigned mr_rr = blockIdx.y * rpw;\n"
          "    const unsigned r = row_order ? row_order[mr_rr] : mr_rr;\n"
-         "    (void)rows;\n" +
-         (pair ? std::string(
-         "    const bool mr_has1 = rpw == 2u && mr_rr + 1u < rows;                  // (else the second row of the pair repeats the first and is not stored)\n"
-         "    const unsigned r1 = mr_has1 ? r + 1u : r;\n"
-         "    const unsigned long long mr_ybase0 = (unsigned long long)(yvals + (size_t)r * n_yvals), mr_ybase1 = (unsigned long long)(yvals + (size_t)r1 * n_yvals);\n"
-         "    const double Y0 = (double)(blk_stride == 0u ? y0 + row_base + r : y0 + ((row_base + r) / blk_rows) * blk_stride + (row_base + r) % blk_rows);\n"
-         "    const double Y1 = (double)(blk_stride == 0u ? y0 + row_base + r1 : y0 + ((row_base + r1) / blk_rows) * blk_stride + (row_base + r1) % blk_rows);\n"
-         "    (void)Y0; (void)Y1; (void)tex; (void)gbits; (void)yrows; (void)tile_list; (void)tile_base;\n")
-               : std::string(
+         "    (void)rows;\n"
          "    const unsigned long long mr_ybase0 = (unsigned long long)(yvals + (size_t)r * n_yvals);\n"
          "    // -> image row (RowBlocks); one range of rows (blk_stride == 0) needs no division, and yrows is a power of two\n"
          "    const double Y = (double)(blk_stride == 0u ? y0 + row_base + r : y0 + ((row_base + r) / blk_rows) * blk_stride + (row_base + r) % blk_rows);\n"
-         "    (void)Y; (void)tex; (void)gbits; (void)yrows; (void)tile_list; (void)tile_base;\n"));
-    {   // the descriptors of the textures the section samples: scalar loads, once per wavefront
-        std::vector<uint8_t> used;
-        for (uint32_t i = 0; i < P.n_pix_ops; i++)
-            if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_APP) { const uint32_t img = MARAY_INS_AUX(P.pix_ops[i]) / 5u; if (used.size() <= img) used.resize(img + 1, 0); used[img] = 1; }
-        const char *e_ = getenv("MARAY_JIT_TEXEL_ONCE");           // "0": a call of mr_app per App op (= round 3; ablation)
-        E.texel_once = !used.empty() && !(e_ && e_[0] == '0');
-        if (E.texel_once)
-            for (size_t img = 0; img < used.size(); img++)
-                if (used[img]) s += "    const MarayTex mr_t" + std::to_string(img) + " = tex[" + std::to_string(img) + "];\n";
-    }
-    if (n_gwords)
-        s += "    const unsigned long long mr_gbase0 = (unsigned long long)(gbits + ((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0) * " + tw + "u);\n";
-    if (gw_vgpr)
-        s += "    const unsigned mr_gn = (n_tx - tile0 < tiles ? n_tx - tile0 : tiles) * " + tw + "u;       // <= 64: the host bounds `tiles`\n"
+         "    (void)Y; (void)tex; (void)gbits; (void)yrows; (void)tile_list; (void)tile_base;\n";
+}
+
+// How the guard words of the tile or pass at hand reach the section's bit tests -- four ways, by how many words a rectangle
+// has (n_gwords; 0: the program has no guards) and how many rectangles a tile (sub):
+//   in_sgprs (<= GW_INLINE_MAX words): a strip's words arrive with one vector load per wavefront (lane i holds word i, mr_gv)
+//     and each word of the rectangle at hand is named, gq<j>, taken with v_readlane per tile (sub == 1) or per pass (sub > 1)
+//     -- one memory latency per strip instead of one per tile;
+//   else one word per lane, loaded per tile: mr_gt0 holds the words of the tile's rectangles (sub > 1: <= 64 together,
+//     jit_guard_geom), or mr_gt<j> the words 64 j .. 64 j + 63 of its one rectangle; a test takes its word with v_readlane.
+namespace {
+struct GuardWords {
+    uint32_t n, sub;
+    bool in_sgprs;
+    std::string nw, tw, esub;       // as text: words per rectangle, words per tile, the rectangle of pass e inside its tile
+    GuardWords(uint32_t n_gwords, uint32_t sub_)
+        : n(n_gwords), sub(sub_), in_sgprs(n_gwords && n_gwords <= GW_INLINE_MAX), nw(std::to_string(n_gwords)), tw(std::to_string(sub_ * n_gwords)),
+          esub("(e >> " + std::to_string(sub_ == 4 ? 0 : 1) + "u)") {}
+    bool per_lane() const { return n && !in_sgprs; }
+    uint32_t lane_vars() const { return (n + 63) / 64; }       // mr_gt<j> of a tile with one rectangle
+};
+}   // namespace
+
+// once per strip: where its guard words are, and (in_sgprs) the words themselves
+static std::string strip_guard_fetch(const GuardWords &g)
+{
+    std::string s;
+    if (g.n)
+        s += "    const unsigned long long mr_gbase0 = (unsigned long long)(gbits + ((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0) * " + g.tw + "u);\n";
+    if (g.in_sgprs)
+        s += "    const unsigned mr_gn = (n_tx - tile0 < tiles ? n_tx - tile0 : tiles) * " + g.tw + "u;       // <= 64: the host bounds `tiles`\n"
              "    const unsigned long long mr_gv = mr_lane < mr_gn ? ((const unsigned long long *)mr_gbase0)[mr_lane] : 0ull;\n" +
-             (sub > 1 ? "    const unsigned long long mr_gnz = mr_ballot(mr_gv != 0ull);            // which of the strip's words have a bit set\n" : "");
-    s += "    const bool mr_wide = rgb64 == nullptr;                                   // wide variants: element e of lane l is pixel x0 + 4 l + e, else x0 + 64 e + l\n"
-         "    const unsigned mr_xl = mr_wide ? 4u * mr_lane : mr_lane, mr_xs = mr_wide ? 1u : 64u;\n"
-         "    const unsigned mr_src = (mr_lane * 4u) / 3u, mr_shift = ((mr_lane * 4u) % 3u) * 8u;   // RGB8 packing of one 64-pixel run\n"
-         + std::string(pair ? "    const size_t row_px0 = (size_t)r * w, row_px1 = (size_t)r1 * w;\n" : "    const size_t row_px = (size_t)r * w;\n") +
-         "    for (unsigned t = 0; t < tiles; t++) {\n"
-         "    const unsigned x0 = (tile0 + t) * 256u;\n"
-         "    if (x0 >= w) break;\n"
-         "    // y values, constants, guard words: scalar loads where they are used, from addresses made opaque in every trip (fresh\n"
-         "    // copies: an asm output carried around the loop counts as divergent once a lane-dependent branch sits in the loop)\n"
-         "/*MR_KBASE*/";
-    if (n_gwords && !gw_vgpr) {
+             (g.sub > 1 ? "    const unsigned long long mr_gnz = mr_ballot(mr_gv != 0ull);            // which of the strip's words have a bit set\n" : "");
+    return s;
+}
+
+// once per tile: its words, one per lane (per_lane) or named (in_sgprs, one rectangle per tile)
+static std::string tile_guard_fetch(const GuardWords &g)
+{
+    std::string s;
+    if (g.per_lane()) {
         s += "    unsigned long long mr_gbase = mr_gbase0;\n"
              "    asm volatile(\"\" : \"+s\"(mr_gbase));\n";
-        if (sub > 1)   // many words, narrow rectangles: lane i of mr_gt0 holds word i of the tile's rectangles (<= 64 together, jit_guard_geom)
-            s += "    unsigned long long mr_gt0 = mr_lane < " + tw + "u ? ((const unsigned long long *)mr_gbase)[t * " + tw + "u + mr_lane] : 0ull;\n";
-        else           // lane i of mr_gt<j> holds word 64 j + i of this tile (one vector load each); a test takes its word with v_readlane
-            for (uint32_t j = 0; j < (n_gwords + 63) / 64; j++)
-                s += "    unsigned long long mr_gt" + std::to_string(j) + " = " + std::to_string(64 * j) + "u + mr_lane < " + nw + "u ? ((const unsigned long long *)mr_gbase)[t * " + nw + "u + " +
+        if (g.sub > 1)
+            s += "    unsigned long long mr_gt0 = mr_lane < " + g.tw + "u ? ((const unsigned long long *)mr_gbase)[t * " + g.tw + "u + mr_lane] : 0ull;\n";
+        else
+            for (uint32_t j = 0; j < g.lane_vars(); j++)
+                s += "    unsigned long long mr_gt" + std::to_string(j) + " = " + std::to_string(64 * j) + "u + mr_lane < " + g.nw + "u ? ((const unsigned long long *)mr_gbase)[t * " + g.nw + "u + " +
                      std::to_string(64 * j) + "u + mr_lane] : 0ull;\n";
-    } else if (gw_vgpr && sub == 1)
-        for (uint32_t j = 0; j < n_gwords; j++)
-            s += "    mr_mask gq" + std::to_string(j) + " = mr_lane64(mr_gv, t * " + nw + "u + " + std::to_string(j) + "u);\n";
-    if (defer) s += "    ((volatile unsigned *)mr_slow)[mr_wv] = 0u;\n    bool mr_slow_tile = false;\n";
-    // what opens a pass of either width: the tables made opaque (LICM would hoist every constant and y value out of the
-    // loops and spill them), the pixel coordinates, the outputs
-    const std::string opaque = std::string(
-        pair ? "    unsigned long long mr_ybase = mr_q ? mr_ybase1 : mr_ybase0;      // (wide tiles of a two-row kernel: row after row)\n"
-             : "    unsigned long long mr_ybase = mr_ybase0;\n") +
-        "    asm volatile(\"\" : \"+s\"(mr_ybase));\n"
-        "    mr_kptr yv = (mr_kptr)mr_ybase;\n"
-        "    const __attribute__((address_space(4))) unsigned *yw = (const __attribute__((address_space(4))) unsigned *)yv;\n"
-        "    (void)yv; (void)yw;\n/*MR_KC*/";
-    // the tables of both rows of a pair
-    const std::string opaque2 =
-        "    unsigned long long mr_ybase = mr_ybase0, mr_ybaseb = mr_ybase1;\n"
-        "    asm volatile(\"\" : \"+s\"(mr_ybase), \"+s\"(mr_ybaseb));\n"
-        "    mr_kptr yv = (mr_kptr)mr_ybase, yv1 = (mr_kptr)mr_ybaseb;\n"
-        "    const __attribute__((address_space(4))) unsigned *yw = (const __attribute__((address_space(4))) unsigned *)yv, *yw1 = (const __attribute__((address_space(4))) unsigned *)yv1;\n"
-        "    (void)yv; (void)yw; (void)yv1; (void)yw1;\n/*MR_KC*/";
-    // the guard words of the rectangle at hand, opaque anew in every pass: left visible, all their bit tests are loop
-    // invariants too (168 booleans for chess, hoisted and spilled to VGPR lanes)
-    std::string gq_pass;
-    if (n_gwords && !gw_vgpr && sub > 1) {
-        gq_pass = "    asm volatile(\"\" : \"+v\"(mr_gt0));\n"
-                  "    const unsigned mr_gsub = " + esub + " * " + nw + "u;           // first word of this pass's rectangle\n"
-                  "    const unsigned long long mr_gnzp = mr_ballot(mr_gt0 != 0ull) >> mr_gsub;      // which of its words have a bit set\n"
-                  "    (void)mr_gnzp;\n";
-        E.gw_lane_base = "mr_gsub";
-    } else if (gw_vgpr && sub > 1)
-        for (uint32_t j = 0; j < n_gwords; j++) {
+    } else if (g.in_sgprs && g.sub == 1)
+        for (uint32_t j = 0; j < g.n; j++)
+            s += "    mr_mask gq" + std::to_string(j) + " = mr_lane64(mr_gv, t * " + g.nw + "u + " + std::to_string(j) + "u);\n";
+    return s;
+}
+
+// once per pass: the guard words of the rectangle at hand, opaque anew in every pass: left visible, all their bit tests are
+// loop invariants too (168 booleans for chess, hoisted and spilled to VGPR lanes)
+static std::string pass_guard_words(const GuardWords &g)
+{
+    std::string s;
+    if (g.per_lane() && g.sub > 1)
+        s = "    asm volatile(\"\" : \"+v\"(mr_gt0));\n"
+            "    const unsigned mr_gsub = " + g.esub + " * " + g.nw + "u;           // first word of this pass's rectangle\n"
+            "    const unsigned long long mr_gnzp = mr_ballot(mr_gt0 != 0ull) >> mr_gsub;      // which of its words have a bit set\n"
+            "    (void)mr_gnzp;\n";
+    else if (g.in_sgprs && g.sub > 1)
+        for (uint32_t j = 0; j < g.n; j++) {
             const std::string k = std::to_string(j);
-            gq_pass += "    mr_mask gq" + k + " = mr_lane64(mr_gv, (t * " + std::to_string(sub) + "u + " + esub + ") * " + nw + "u + " + k + "u);\n"
-                       "    asm volatile(\"\" : \"+s\"(gq" + k + "));\n";
+            s += "    mr_mask gq" + k + " = mr_lane64(mr_gv, (t * " + std::to_string(g.sub) + "u + " + g.esub + ") * " + g.nw + "u + " + k + "u);\n"
+                 "    asm volatile(\"\" : \"+s\"(gq" + k + "));\n";
         }
-    else if (gw_vgpr)
-        for (uint32_t j = 0; j < n_gwords; j++) gq_pass += "    asm volatile(\"\" : \"+s\"(gq" + std::to_string(j) + "));\n";
-    else if (n_gwords)
-        for (uint32_t j = 0; j < (n_gwords + 63) / 64; j++) {
+    else if (g.in_sgprs)
+        for (uint32_t j = 0; j < g.n; j++) s += "    asm volatile(\"\" : \"+s\"(gq" + std::to_string(j) + "));\n";
+    else
+        for (uint32_t j = 0; j < g.lane_vars(); j++) {
             const std::string k = std::to_string(j);
-            gq_pass += "    asm volatile(\"\" : \"+v\"(mr_gt" + k + "));\n"
-                       "    const unsigned long long mr_gnz" + k + " = mr_ballot(mr_gt" + k + " != 0ull);      // which of the tile's words have a bit set\n"
-                       "    (void)mr_gnz" + k + ";\n";
+            s += "    asm volatile(\"\" : \"+v\"(mr_gt" + k + "));\n"
+                 "    const unsigned long long mr_gnz" + k + " = mr_ballot(mr_gt" + k + " != 0ull);      // which of the tile's words have a bit set\n"
+                 "    (void)mr_gnz" + k + ";\n";
         }
-    const std::string wide_open =
-        std::string(pair ? "    for (unsigned mr_q = 0; mr_q <= (unsigned)mr_has1; mr_q++) {\n"
-                           "    const double Y = mr_q ? Y1 : Y0;\n"
-                           "    const size_t row_px = mr_q ? row_px1 : row_px0;\n"
-                           "    (void)Y;\n"
-                         : "    {\n") + opaque + (sub > 1 ? std::string() : gq_pass) +
+    return s;
+}
+
+// `if (no guard bit of this tile is set) {`: what sends a tile to the wide variant
+static std::string sky_test(const GuardWords &g)
+{
+    if (g.per_lane() && g.sub > 1) return "    if (mr_ballot(mr_gt0 != 0ull) == 0ull) {\n";
+    if (g.sub > 1) return "    if (((mr_gnz >> (t * " + g.tw + "u)) & " + std::to_string((1ull << (g.sub * g.n)) - 1ull) + "ull) == 0ull) {\n";
+    std::string any = g.in_sgprs ? "gq0" : "mr_gt0";
+    for (uint32_t j = 1; j < (g.in_sgprs ? g.n : g.lane_vars()); j++) any += (g.in_sgprs ? " | gq" : " | mr_gt") + std::to_string(j);
+    return g.in_sgprs ? "    if ((" + any + ") == 0ull) {\n" : "    if (mr_ballot((" + any + ") != 0ull) == 0ull) {\n";
+}
+
+// the y-value table of a pass of maray_jit_pixels (its one row's) and PASS_TABLES
+static const std::string PIXELS_PASS_TABLES = std::string("    unsigned long long mr_ybase = mr_ybase0;\n") + PASS_TABLES;
+
+// after a pass's section: has some Sin of it sent the tile to the interpreter?
+static std::string defer_pass(bool defer)
+{
+    return defer ? "    mr_slow_tile |= mr_ballot(mr_defer != 0.0f) != 0ull || ((volatile unsigned *)mr_slow)[mr_wv] != 0u;      // wave-uniform\n" : "";
+}
+
+// WIDE: a whole tile in one pass, four pixels per lane.  Opens the block the section goes into ...
+static std::string wide_open(const GuardWords &g)
+{
+    return "    {\n" + PIXELS_PASS_TABLES + (g.sub > 1 ? std::string() : pass_guard_words(g)) +
         "    const unsigned xa = x0 + mr_xl;                                        // this lane's first pixel\n"
         "    const mr_d X((double)xa, (double)(xa + mr_xs), (double)(xa + 2u * mr_xs), (double)(xa + 3u * mr_xs));\n"
         "    mr_d o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
         "    float mr_defer = 0.0f;                     // fused Step(Sin) ops count their undecided cases in here\n"
         "    (void)X; (void)mr_defer;\n";
-    const std::string defer_pass = defer ?
-        "    mr_slow_tile |= mr_ballot(mr_defer != 0.0f) != 0ull || ((volatile unsigned *)mr_slow)[mr_wv] != 0u;      // wave-uniform\n" : "";
-    const std::string wide_close = defer_pass +
+}
+
+// ... and packs, stores and closes it: a lane's four RGB8 pixels are 12 contiguous bytes; with f64 planes, four 64-pixel runs
+static std::string wide_close(bool defer)
+{
+    return defer_pass(defer) +
         "    const unsigned p0 = mr_cast_u8(o0.a) | (mr_cast_u8(o1.a) << 8) | (mr_cast_u8(o2.a) << 16);\n"
         "    const unsigned p1 = mr_cast_u8(o0.b) | (mr_cast_u8(o1.b) << 8) | (mr_cast_u8(o2.b) << 16);\n"
         "    const unsigned p2 = mr_cast_u8(o0.c) | (mr_cast_u8(o1.c) << 8) | (mr_cast_u8(o2.c) << 16);\n"
@@ -603,217 +671,133 @@ std::string jit_source(const maray_program &P, int min_waves)
         "            mr_store_run(rgb8, rgb64, row_px, x0 + 64u * e, w, mr_lane, mr_src, mr_shift, pk[e], c0[e], c1[e], c2[e]);\n"
         "    }\n"
         "    }\n";
-    // one 64-pixel run: f64 planes (24 B per lane) and / or RGB8 (48 lanes assemble a dword each from two neighbours'
-    // packed colours; ragged ends and unaligned rows store bytes)
-    const std::string store_run =
-        "__device__ inline void mr_store_run(unsigned char *__restrict__ rgb8, double *__restrict__ rgb64, size_t row_px, unsigned xw, unsigned w,\n"
-        "                                    unsigned lane, unsigned src, unsigned shift, unsigned pk, double c0, double c1, double c2)\n{\n"
-        "    const unsigned x = xw + lane;\n"
-        "    if (rgb64 && x < w) { const size_t p = (row_px + x) * 3; rgb64[p] = c0; rgb64[p + 1] = c1; rgb64[p + 2] = c2; }\n"
-        "    if (rgb8) {\n"
-        "        unsigned char *wave_out = rgb8 + (row_px + xw) * 3;\n"
-        "        if (xw + 64u <= w && ((size_t)wave_out & 3u) == 0u) {                // wave-uniform\n"
-        "            const unsigned pa = (unsigned)__builtin_amdgcn_ds_bpermute((int)(src * 4u), (int)pk);\n"
-        "            const unsigned pb = (unsigned)__builtin_amdgcn_ds_bpermute((int)(src * 4u + 4u), (int)pk);\n"
-        "            const unsigned dw = (unsigned)((((unsigned long long)pb << 24) | pa) >> shift);\n"
-        "            if (lane < 48u) ((unsigned *)wave_out)[lane] = dw;\n"
-        "        } else if (x < w) {\n"
-        "            unsigned char *q = rgb8 + (row_px + x) * 3;\n"
-        "            q[0] = (unsigned char)pk; q[1] = (unsigned char)(pk >> 8); q[2] = (unsigned char)(pk >> 16);\n"
-        "        }\n"
-        "    }\n"
-        "}\n";
-    std::string tile_end;         // closes a tile: the work list entry of a tile some Sin of which needs the slow path
-    if (defer)
-        tile_end = "    if (mr_slow_tile && mr_lane == 0u) tile_list[1u + atomicAdd(&tile_list[0], 1u)] = tile_base + r * n_tx + tile0 + t;\n" +
-                   std::string(pair ? "    if (mr_slow_tile && mr_has1 && mr_lane == 0u) tile_list[1u + atomicAdd(&tile_list[0], 1u)] = tile_base + r1 * n_tx + tile0 + t;\n" : "");
+}
 
-    if (n_gwords) {
-        // the variant of a tile with no guard bit set, four pixels per lane
-        if (!gw_vgpr && sub > 1)
-            s += "    if (mr_ballot(mr_gt0 != 0ull) == 0ull) {\n";
-        else if (sub > 1)
-            s += "    if (((mr_gnz >> (t * " + tw + "u)) & " + std::to_string((1ull << (sub * n_gwords)) - 1ull) + "ull) == 0ull) {\n";
-        else if (gw_vgpr) {
-            std::string any = "gq0";
-            for (uint32_t j = 1; j < n_gwords; j++) any += " | gq" + std::to_string(j);
-            s += "    if ((" + any + ") == 0ull) {\n";
-        } else {
-            std::string any = "mr_gt0";
-            for (uint32_t j = 1; j < (n_gwords + 63) / 64; j++) any += " | mr_gt" + std::to_string(j);
-            s += "    if (mr_ballot((" + any + ") != 0ull) == 0ull) {\n";
-        }
-        E.td = "mr_d"; E.tm = "mr_m";
-        E.assume_guards_zero = true;
-        s += wide_open;
+// NARROW: one wavefront, four passes of 64 pixels (a loop, not unrolled).  Opens the loop the section goes into ...
+static std::string narrow_open(const GuardWords &g)
+{
+    return "    const bool mr_fast = rgb8 && x0 + 256u <= w && ((size_t)(rgb8 + (row_px + x0) * 3) & 3u) == 0u;      // wave-uniform\n"
+           "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + PIXELS_PASS_TABLES + pass_guard_words(g) +
+           "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
+           "    const double X = (double)x;\n"
+           "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
+           "    float mr_defer = 0.0f;\n"
+           "    (void)X; (void)mr_defer;\n";
+}
+
+// ... and closes it: the passes leave their packed pixels in LDS (same-wave traffic: no barrier) and a whole aligned tile is
+// stored as a dwordx3 per lane
+static std::string narrow_close(bool defer)
+{
+    return defer_pass(defer) +
+           "    const unsigned pk = mr_cast_u8(o0) | (mr_cast_u8(o1) << 8) | (mr_cast_u8(o2) << 16);\n"
+           "    if (mr_fast) {\n"
+           "        mr_tp[mr_wv * 256u + 64u * e + mr_lane] = pk;\n"
+           "        mr_store_run(nullptr, rgb64, row_px, xw, w, mr_lane, mr_src, mr_shift, pk, o0, o1, o2);\n"
+           "    } else mr_store_run(rgb8, rgb64, row_px, xw, w, mr_lane, mr_src, mr_shift, pk, o0, o1, o2);\n"
+           "    }\n"
+           "    if (mr_fast) {\n"
+           "        __builtin_amdgcn_wave_barrier();                                     // same wavefront wrote them: LDS keeps its order\n"
+           "        const mr_u4 p = *(const mr_u4 *)&mr_tp[mr_wv * 256u + 4u * mr_lane];\n"
+           "        mr_u3 d;\n"
+           "        d.a = p.a | (p.b << 24); d.b = (p.b >> 8) | (p.c << 16); d.c = (p.c >> 16) | (p.d << 8);\n"
+           "        *(mr_u3 *)(rgb8 + (row_px + x0 + 4u * mr_lane) * 3) = d;\n"
+           "        __builtin_amdgcn_wave_barrier();\n"
+           "    }\n";
+}
+
+// closes a tile: the work list entry of a tile some Sin of which needs the slow path
+static std::string tile_end(bool defer)
+{
+    return defer ? "    if (mr_slow_tile && mr_lane == 0u) tile_list[1u + atomicAdd(&tile_list[0], 1u)] = tile_base + r * n_tx + tile0 + t;\n" : "";
+}
+
+// Source of the PIXEL kernel, maray_jit_pixels.  A wavefront owns a strip of `tiles` consecutive 256-pixel tiles of one
+// row (blockIdx.y); a block is four wavefronts = four neighbouring strips that share nothing but the instruction cache:
+// no staging, no barrier.  The strip's guard words arrive with one vector load (lane i = word i); per tile one scalar
+// test of a ballot picks the variant:
+//
+//  * WIDE, four pixels per lane (device_math.h, MR_VEC4: every value four f64, every boolean four lane masks).  The
+//    variant of a tile none of whose guard bits is set (every guarded region is the literal 0: for chess the background,
+//    one multiply), and the whole section of a small program without guards (config 2: six ops).  The scalar unit's
+//    share of a tile and the store's address arithmetic are paid once per 256 pixels, and a lane's four RGB8 pixels are
+//    12 contiguous bytes: one global_store_dwordx3, no cross-lane packing.  This is the path that is bound by the store
+//    (3 B per pixel) and little else.
+//  * NARROW, one pixel per lane, four passes of 64 pixels (a loop: the section's code exists once).  The variant of a
+//    tile where shapes may show.  Regions are entered per 64 pixels, where a wave-level SKIP op still finds all lanes
+//    agreeing; values are single f64.  The passes leave their packed pixels in LDS (same-wave traffic: no barrier) and
+//    the tile is stored like a wide one.
+//
+// When f64 planes are wanted too, element e of a wide lane l is pixel x0 + 64 e + l and every 64-pixel run is stored on
+// its own (24 B per lane, the coalesced pattern of the f64 planes).  A Sin whose argument is huge (|x| >= 105414350), inf
+// or NaN does not call the slow reduction here (a call site per Sin op would force every live value through scratch): the
+// tile is flagged instead and re-evaluated by the tape interpreter kernel afterwards, so the final raster is identical.
+// Layouts that were measured and lost (a wavefront per 64 pixels with guard words staged in LDS, a busy tile on the
+// block's four wavefronts side by side, persistent wavefronts, two pixels per lane, two rows per wavefront, guard words by
+// scalar loads, a sky loop of its own ...) are history: DESIGN.md section 7.1, profiles/r2_ablations.jsonl.
+std::string jit_source(const maray_program &P, int min_waves)
+{
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    const bool defer = may_defer_tiles(P), wide_general = jit_wide_general(P, S.n_gwords, K);
+    if (g.per_lane() && g.sub > 1) E.gw_lane_base = "mr_gsub";
+    auto section = [&](const char *td, const char *tm, bool sky, const RedPlan *rplan) {
+        E.td = td; E.tm = tm; E.assume_guards_zero = sky; E.rplan = rplan;
         E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        s += wide_close;
-        E.assume_guards_zero = false;
-        s += tile_end + "    continue;\n    }\n";
+    };
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; general variant " + (wide_general ? "four pixels per lane" : "one pixel per lane, four passes per tile") + "\n" +
+         PIXELS_PROLOGUE + pixels_head(S.min_waves) + S.texture_loads() + strip_guard_fetch(g) +
+         "    const bool mr_wide = rgb64 == nullptr;                                   // wide variants: element e of lane l is pixel x0 + 4 l + e, else x0 + 64 e + l\n"
+         "    const unsigned mr_xl = mr_wide ? 4u * mr_lane : mr_lane, mr_xs = mr_wide ? 1u : 64u;\n"
+         "    const unsigned mr_src = (mr_lane * 4u) / 3u, mr_shift = ((mr_lane * 4u) % 3u) * 8u;   // RGB8 packing of one 64-pixel run\n"
+         "    const size_t row_px = (size_t)r * w;\n"
+         "    for (unsigned t = 0; t < tiles; t++) {\n"
+         "    const unsigned x0 = (tile0 + t) * 256u;\n"
+         "    if (x0 >= w) break;\n"
+         "    // y values, constants, guard words: scalar loads where they are used, from addresses made opaque in every trip (fresh\n"
+         "    // copies: an asm output carried around the loop counts as divergent once a lane-dependent branch sits in the loop)\n"
+         "/*MR_KBASE*/" + tile_guard_fetch(g);
+    if (defer) s += "    ((volatile unsigned *)mr_slow)[mr_wv] = 0u;\n    bool mr_slow_tile = false;\n";
+    if (g.n) {          // the variant of a tile with no guard bit set, four pixels per lane
+        s += sky_test(g) + wide_open(g);
+        section("mr_d", "mr_m", true, nullptr);
+        s += wide_close(defer) + tile_end(defer) + "    continue;\n    }\n";
     }
     if (wide_general) {
-        E.td = "mr_d"; E.tm = "mr_m";
-        s += wide_open;
-        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        s += wide_close + tile_end;
-    } else if (pair) {
-        // one wavefront, four passes of 64 pixels x 2 rows: a value that depends on the row is a pair (mr_p), the rest is
-        // computed once; the packed pixels of both rows go to LDS and each row's tile is stored as a dwordx3 per lane
-        E.td = "double"; E.tm = "mr_mask";
-        E.pair = true;
-        E.rplan = &reductions;
-        {   // typing run: which ops yield pairs (the regions' variables are declared ahead of their last op)
-            Emitter T(E);
-            T.wide_hint.clear();
-            T.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-            E.wide_hint = T.is_wide_op;
-        }
-        s += "    const bool mr_al0 = x0 + 256u <= w && ((size_t)(rgb8 + (row_px0 + x0) * 3) & 3u) == 0u, mr_al1 = x0 + 256u <= w && ((size_t)(rgb8 + (row_px1 + x0) * 3) & 3u) == 0u;\n"
-             "    const bool mr_fast = rgb8 && mr_al0 && mr_al1;      // wave-uniform\n"
-             "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + opaque2 + gq_pass +
-             "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
-             "    const double X = (double)x;\n"
-             "    const mr_p Y(Y0, Y1);\n"
-             "    mr_p o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
-             "    float mr_defer = 0.0f;\n"
-             "    (void)X; (void)Y; (void)mr_defer;\n";
-        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        E.rplan = nullptr;
-        E.pair = false;
-        s += defer_pass +
-             "    const unsigned pk0 = mr_cast_u8(o0.a) | (mr_cast_u8(o1.a) << 8) | (mr_cast_u8(o2.a) << 16);\n"
-             "    const unsigned pk1 = mr_cast_u8(o0.b) | (mr_cast_u8(o1.b) << 8) | (mr_cast_u8(o2.b) << 16);\n"
-             "    if (mr_fast) {\n"
-             "        mr_tp[mr_wv * 512u + 64u * e + mr_lane] = pk0;\n"
-             "        mr_tp[mr_wv * 512u + 256u + 64u * e + mr_lane] = pk1;\n"
-             "        mr_store_run(nullptr, rgb64, row_px0, xw, w, mr_lane, mr_src, mr_shift, pk0, o0.a, o1.a, o2.a);\n"
-             "        if (mr_has1) mr_store_run(nullptr, rgb64, row_px1, xw, w, mr_lane, mr_src, mr_shift, pk1, o0.b, o1.b, o2.b);\n"
-             "    } else {\n"
-             "        mr_store_run(rgb8, rgb64, row_px0, xw, w, mr_lane, mr_src, mr_shift, pk0, o0.a, o1.a, o2.a);\n"
-             "        if (mr_has1) mr_store_run(rgb8, rgb64, row_px1, xw, w, mr_lane, mr_src, mr_shift, pk1, o0.b, o1.b, o2.b);\n"
-             "    }\n"
-             "    }\n"
-             "    if (mr_fast) {\n"
-             "        __builtin_amdgcn_wave_barrier();                                     // same wavefront wrote them: LDS keeps its order\n"
-             "        for (unsigned mr_q = 0; mr_q <= (unsigned)mr_has1; mr_q++) {\n"
-             "            const mr_u4 p = *(const mr_u4 *)&mr_tp[mr_wv * 512u + 256u * mr_q + 4u * mr_lane];\n"
-             "            mr_u3 d;\n"
-             "            d.a = p.a | (p.b << 24); d.b = (p.b >> 8) | (p.c << 16); d.c = (p.c >> 16) | (p.d << 8);\n"
-             "            *(mr_u3 *)(rgb8 + ((mr_q ? row_px1 : row_px0) + x0 + 4u * mr_lane) * 3) = d;\n"
-             "        }\n"
-             "        __builtin_amdgcn_wave_barrier();\n"
-             "    }\n" + tile_end;
+        s += wide_open(g);
+        section("mr_d", "mr_m", false, nullptr);
+        s += wide_close(defer) + tile_end(defer);
     } else {
-        // one wavefront, four passes of 64 pixels (a loop, not unrolled); the passes leave their packed pixels in LDS
-        // (same-wave traffic: no barrier) and a whole aligned tile is stored as a dwordx3 per lane
-        E.td = "double"; E.tm = "mr_mask";
-        s += "    const bool mr_fast = rgb8 && x0 + 256u <= w && ((size_t)(rgb8 + (row_px + x0) * 3) & 3u) == 0u;      // wave-uniform\n"
-             "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + opaque + gq_pass +
-             "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
-             "    const double X = (double)x;\n"
-             "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
-             "    float mr_defer = 0.0f;\n"
-             "    (void)X; (void)mr_defer;\n";
-        E.rplan = &reductions;
-        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        E.rplan = nullptr;
-        s += defer_pass +
-             "    const unsigned pk = mr_cast_u8(o0) | (mr_cast_u8(o1) << 8) | (mr_cast_u8(o2) << 16);\n"
-             "    if (mr_fast) {\n"
-             "        mr_tp[mr_wv * 256u + 64u * e + mr_lane] = pk;\n"
-             "        mr_store_run(nullptr, rgb64, row_px, xw, w, mr_lane, mr_src, mr_shift, pk, o0, o1, o2);\n"
-             "    } else mr_store_run(rgb8, rgb64, row_px, xw, w, mr_lane, mr_src, mr_shift, pk, o0, o1, o2);\n"
-             "    }\n"
-             "    if (mr_fast) {\n"
-             "        __builtin_amdgcn_wave_barrier();                                     // same wavefront wrote them: LDS keeps its order\n"
-             "        const mr_u4 p = *(const mr_u4 *)&mr_tp[mr_wv * 256u + 4u * mr_lane];\n"
-             "        mr_u3 d;\n"
-             "        d.a = p.a | (p.b << 24); d.b = (p.b >> 8) | (p.c << 16); d.c = (p.c >> 16) | (p.d << 8);\n"
-             "        *(mr_u3 *)(rgb8 + (row_px + x0 + 4u * mr_lane) * 3) = d;\n"
-             "        __builtin_amdgcn_wave_barrier();\n"
-             "    }\n" + tile_end;
+        s += narrow_open(g);
+        section("double", "mr_mask", false, &S.reductions);
+        s += narrow_close(defer) + tile_end(defer);
     }
     s += "    }\n}\n";
-    {
-        std::string tab = store_run;
-        if (!E.ktab_vals.empty()) {
-            tab += "__constant__ __attribute__((aligned(64))) double mr_kc_tab[" + std::to_string(E.ktab_vals.size()) + "] = {";
-            for (size_t j = 0; j < E.ktab_vals.size(); j++) { tab += (j % 6 ? " " : "\n    "); tab += lit(E.ktab_vals[j]); tab += ","; }
-            tab += "\n};\n";
-        }
-        s.replace(s.find("/*MR_KTAB*/"), 11, tab);
-        // The table's address, made opaque once per tile and once per pass (see `opaque`)
-        for (size_t at; (at = s.find("/*MR_KBASE*/")) != std::string::npos;)
-            s.replace(at, 12, E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n");
-        const std::string kc = E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
-                               "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
-                               "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n";
-        for (size_t at; (at = s.find("/*MR_KC*/")) != std::string::npos;) s.replace(at, 9, kc);
-    }
-    return s;
+    return S.splice_constants(MR_STORE_RUN);
 }
 
 
-// Source of the supersampling PIXEL kernel, maray_jit_pixels_ss (include/maray_hip.h, supersampling; DESIGN.md 4.5): the
-// narrow form of jit_source -- one sample per lane, the section's guard tests and branch tables as they are -- over the k w x k h
-// sample grid of a supersampled scene.  A wavefront owns a strip of `tiles` tiles of 256 sample columns of one OUTPUT row
-// (blockIdx.y); per pass of 64 sample columns it walks the k sample rows of that output row, each with its own y values
-// and the guard words of its own group of rows (a group may end inside a pixel's k rows), and adds the cast samples of a
-// lane in integer registers.  k divides 64: a pixel's k columns are k neighbouring lanes, summed across by shuffles; the
-// group's first lane stores the pixel's mean.  k is a literal of the source, so it is part of the code object's key.
-// Nothing is deferred to the interpreter: an unbounded Sin takes its full reduction here.  Separate from jit_source, whose
-// text this does not change.
-std::string jit_source_samples(const maray_program &P, uint32_t k, int min_waves)
+// ---- maray_jit_pixels_ss ---------------------------------------------------------------------------------------------------------
+static const char SAMPLES_PROLOGUE[] =
+    "#define MR_VEC4 1\n"
+    "#include \"device_math.h\"\n"
+    "typedef const __attribute__((address_space(4))) double *mr_kptr;\n"
+    "typedef const __attribute__((address_space(4))) unsigned long long *mr_gptr;\n"
+    "__device__ inline mr_mask mr_lane64(unsigned long long v, unsigned lane)\n"
+    "{\n"
+    "    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, (int)lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), (int)lane);\n"
+    "    return ((mr_mask)hi << 32) | lo;\n"
+    "}\n/*MR_KTAB*/\n";
+
+// w, y0, blk_rows, blk_stride: samples; row_base + blockIdx.y: the OUTPUT row of the call; yvals, gbits and rgb8 belong to the whole call
+static std::string samples_head(int min_waves)
 {
-    validate_program(P);
-    if (k != 2 && k != 4 && k != 8) throw Error{MARAY_E_ARG, "supersampling kernels exist for k = 2, 4 and 8"};
-    const int min_waves_arg = min_waves;
-    Emitter E(P);
-    E.min_region = 24;          // as jit_source
-    E.ybool = jit_bool_yvals(P);
-    E.ktab = true;
-    E.no_defer = true;
-    for (uint32_t i = 0; i < P.n_pix_ops && E.sin_k < 0; i++)
-        if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_STEPSIN) {
-            static const double sin_k[8] = {0x1.45f306dc9c883p-1, 0x1.8p52, 0x1.921fb58000000p+0, -0x1.dde973c000000p-27, -0x1.cb3b398000000p-55, -0x1.d747f23e32ed7p-83, 0x1p-70, 0.0};
-            E.sin_k = 0;
-            E.ktab_vals.assign(sin_k, sin_k + 8);
-        }
-    std::string &s = E.out;
-    const uint32_t n_ynum = numeric_yvals(P);
-    const uint32_t n_gwords = jit_guard_words(P);
-    E.ignore_row_guards = n_gwords == 0;
-    const GuardPlan plan = jit_guard_plan(P);
-    const GuardGeom geom = jit_guard_geom(P);
-    const uint32_t sub = 256u / geom.gw;
-    // every guard word of the rectangle at hand is a named SGPR pair, loaded per sample row and pass (scalar loads)
-    if (n_gwords) { E.guard_first = n_ynum; E.guard_words = n_gwords; E.plan = &plan; E.gw_inline_max = n_gwords; }
-    RedPlan reductions;
-    if (!E.ignore_row_guards) {
-        Emitter D(P);
-        D.ignore_row_guards = true;
-        D.min_region = E.min_region;
-        D.ybool = E.ybool;
-        D.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-        E.bool_hint = D.is_bool_op;
-        reductions = plan_reductions(P.pix_ops, P.n_pix_ops, P.n_pix_slots, D.is_bool_op, n_ynum, plan, E.ybool);
-    }
-    if (min_waves_arg == 0) min_waves = reductions.empty() ? 6 : 8;
-    const std::string K = std::to_string(k), nw = std::to_string(n_gwords);
-    const std::string esub = sub == 1 ? "0u" : sub == 2 ? "(e >> 1u)" : "e";       // rectangle of pass e inside its tile
-    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
-         std::to_string(P.n_pix_ops) + " ops; supersampling " + K + " x " + K + " samples per pixel, one sample per lane\n"
-         "#define MR_VEC4 1\n"
-         "#include \"device_math.h\"\n"
-         "typedef const __attribute__((address_space(4))) double *mr_kptr;\n"
-         "typedef const __attribute__((address_space(4))) unsigned long long *mr_gptr;\n"
-         "__device__ inline mr_mask mr_lane64(unsigned long long v, unsigned lane)\n"
-         "{\n"
-         "    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, (int)lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), (int)lane);\n"
-         "    return ((mr_mask)hi << 32) | lo;\n"
-         "}\n/*MR_KTAB*/\n";
-    // w, y0, blk_rows, blk_stride: samples; row_base + blockIdx.y: the OUTPUT row of the call; yvals, gbits and rgb8 belong to the whole call
-    s += "extern \"C\" __global__ void __launch_bounds__(256, " + std::to_string(min_waves) +
+    return "extern \"C\" __global__ void __launch_bounds__(256, " + std::to_string(min_waves) +
          ") maray_jit_pixels_ss(unsigned char *__restrict__ rgb8, const double *__restrict__ yvals, const MarayTex *__restrict__ tex,\n"
          "                                                                       const unsigned long long *__restrict__ gbits, unsigned n_tx,\n"
          "                                                                       unsigned w, unsigned y0, unsigned n_yvals, unsigned tiles,\n"
@@ -824,15 +808,38 @@ std::string jit_source_samples(const maray_program &P, uint32_t k, int min_waves
          "    if (tile0 >= n_tx) return;\n"
          "    const unsigned r = row_base + blockIdx.y;                               // output row of the call\n"
          "    (void)tex; (void)gbits; (void)yrows;\n";
-    {
-        std::vector<uint8_t> used;
-        for (uint32_t i = 0; i < P.n_pix_ops; i++)
-            if (MARAY_INS_OP(P.pix_ops[i]) == MARAY_OP_APP) { const uint32_t img = MARAY_INS_AUX(P.pix_ops[i]) / 5u; if (used.size() <= img) used.resize(img + 1, 0); used[img] = 1; }
-        E.texel_once = !used.empty();
-        for (size_t img = 0; img < used.size(); img++)
-            if (used[img]) s += "    const MarayTex mr_t" + std::to_string(img) + " = tex[" + std::to_string(img) + "];\n";
-    }
-    s += "    for (unsigned t = 0; t < tiles; t++) {\n"
+}
+
+// Source of the supersampling PIXEL kernel, maray_jit_pixels_ss (include/maray_hip.h, supersampling; DESIGN.md 4.5): the
+// narrow form of jit_source -- one sample per lane, the section's guard tests and branch tables as they are -- over the k w x k h
+// sample grid of a supersampled scene.  A wavefront owns a strip of `tiles` tiles of 256 sample columns of one OUTPUT row
+// (blockIdx.y); per pass of 64 sample columns it walks the k sample rows of that output row, each with its own y values
+// and the guard words of its own group of rows (a group may end inside a pixel's k rows), and adds the cast samples of a
+// lane in integer registers.  k divides 64: a pixel's k columns are k neighbouring lanes, summed across by shuffles; the
+// group's first lane stores the pixel's mean.  k is a literal of the source, so it is part of the code object's key.
+// Nothing is deferred to the interpreter: an unbounded Sin takes its full reduction here.  What differs from jit_source is
+// what stands here: one kernel form, every guard word of the rectangle at hand a named SGPR pair loaded per sample row and
+// pass (scalar loads), the sums and the store.
+std::string jit_source_samples(const maray_program &P, uint32_t k, int min_waves)
+{
+    validate_program(P);
+    if (k != 2 && k != 4 && k != 8) throw Error{MARAY_E_ARG, "supersampling kernels exist for k = 2, 4 and 8"};
+    // This kernel was written without the ablation knobs of the section's text, and its pinned sources
+    // (tests/golden/jit_source_hashes.json) say it still ignores them: the defaults, whatever the environment says.  The
+    // knobs of the guards (MARAY_JIT_ROW_GUARDS, MARAY_JIT_GUARD_W / _H) are the ROW kernel's too and are honoured.
+    JitKnobs K = jit_knobs();
+    K.min_region = JitKnobs().min_region; K.fuse_cmp = true; K.reduce = true; K.texel_once = true;
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    E.no_defer = true;
+    if (S.n_gwords) E.gw_inline_max = S.n_gwords;
+    const std::string Ks = std::to_string(k), nw = std::to_string(S.n_gwords), half = std::to_string(k * k / 2), shift = std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3));
+    const std::string esub = S.sub == 1 ? "0u" : S.sub == 2 ? "(e >> 1u)" : "e";       // rectangle of pass e inside its tile
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; supersampling " + Ks + " x " + Ks + " samples per pixel, one sample per lane\n" +
+         SAMPLES_PROLOGUE + samples_head(S.min_waves) + S.texture_loads() +
+         "    for (unsigned t = 0; t < tiles; t++) {\n"
          "    const unsigned x0 = (tile0 + t) * 256u;\n"
          "    if (x0 >= w) break;\n"
          "/*MR_KBASE*/"
@@ -841,65 +848,41 @@ std::string jit_source_samples(const maray_program &P, uint32_t k, int min_waves
          "    const double X = (double)x;\n"
          "    unsigned mr_s01 = 0u, mr_s2 = 0u;                                       // R | G << 16, B: at most 255 k^2 <= 16320 each\n"
          "    (void)X;\n"
-         "    _Pragma(\"unroll 1\") for (unsigned mr_j = 0; mr_j < " + K + "u; mr_j++) {\n"
-         "    const unsigned rs = r * " + K + "u + mr_j;                                 // sample row of the call\n"
+         "    _Pragma(\"unroll 1\") for (unsigned mr_j = 0; mr_j < " + Ks + "u; mr_j++) {\n"
+         "    const unsigned rs = r * " + Ks + "u + mr_j;                                 // sample row of the call\n"
          "    const double Y = (double)(blk_stride == 0u ? y0 + rs : y0 + (rs / blk_rows) * blk_stride + rs % blk_rows);\n"
          "    (void)Y;\n"
-         "    unsigned long long mr_ybase = (unsigned long long)(yvals + (size_t)rs * n_yvals);\n"
-         "    asm volatile(\"\" : \"+s\"(mr_ybase));\n"
-         "    mr_kptr yv = (mr_kptr)mr_ybase;\n"
-         "    const __attribute__((address_space(4))) unsigned *yw = (const __attribute__((address_space(4))) unsigned *)yv;\n"
-         "    (void)yv; (void)yw;\n/*MR_KC*/";
-    if (n_gwords) {
-        s += "    unsigned long long mr_gb = (unsigned long long)(gbits + (((size_t)(rs >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * " + std::to_string(sub) +
+         "    unsigned long long mr_ybase = (unsigned long long)(yvals + (size_t)rs * n_yvals);\n" + PASS_TABLES;
+    if (S.n_gwords) {
+        s += "    unsigned long long mr_gb = (unsigned long long)(gbits + (((size_t)(rs >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * " + std::to_string(S.sub) +
              "u + " + esub + ") * " + nw + "u);\n"
              "    asm volatile(\"\" : \"+s\"(mr_gb));\n"
              "    const mr_gptr mr_g = (mr_gptr)mr_gb;\n";
-        for (uint32_t j = 0; j < n_gwords; j++) {
-            const std::string q = std::to_string(j);
-            s += "    mr_mask gq" + q + " = mr_g[" + q + "];\n";
-        }
+        for (uint32_t j = 0; j < S.n_gwords; j++) s += "    mr_mask gq" + std::to_string(j) + " = mr_g[" + std::to_string(j) + "];\n";
     }
     s += "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
          "    float mr_defer = 0.0f;\n"
          "    (void)mr_defer;\n";
-    E.td = "double"; E.tm = "mr_mask";
-    E.rplan = &reductions;
+    E.td = "double"; E.tm = "mr_mask"; E.rplan = &S.reductions;
     E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
-    E.rplan = nullptr;
     s += "    mr_s01 += mr_cast_u8(o0) | (mr_cast_u8(o1) << 16);\n"
          "    mr_s2 += mr_cast_u8(o2);\n"
          "    }\n"
          "    // a pixel's k sample columns are k neighbouring lanes: their sums, across lanes without memory\n"
-         "    _Pragma(\"unroll\") for (unsigned m = 1u; m < " + K + "u; m <<= 1) {\n"
+         "    _Pragma(\"unroll\") for (unsigned m = 1u; m < " + Ks + "u; m <<= 1) {\n"
          "        mr_s01 += (unsigned)__shfl_xor((int)mr_s01, (int)m);\n"
          "        mr_s2 += (unsigned)__shfl_xor((int)mr_s2, (int)m);\n"
          "    }\n"
-         "    const unsigned xo = x / " + K + "u;\n"
+         "    const unsigned xo = x / " + Ks + "u;\n"
          "    if ((mr_lane & " + std::to_string(k - 1) + "u) == 0u && xo < w_out) {\n"
          "        unsigned char *q = rgb8 + ((size_t)r * w_out + xo) * 3;\n"
-         "        q[0] = (unsigned char)(((mr_s01 & 0xFFFFu) + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
-         "        q[1] = (unsigned char)(((mr_s01 >> 16) + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
-         "        q[2] = (unsigned char)((mr_s2 + " + std::to_string(k * k / 2) + "u) >> " + std::to_string(2 * (k == 2 ? 1 : k == 4 ? 2 : 3)) + "u);\n"
+         "        q[0] = (unsigned char)(((mr_s01 & 0xFFFFu) + " + half + "u) >> " + shift + "u);\n"
+         "        q[1] = (unsigned char)(((mr_s01 >> 16) + " + half + "u) >> " + shift + "u);\n"
+         "        q[2] = (unsigned char)((mr_s2 + " + half + "u) >> " + shift + "u);\n"
          "    }\n"
          "    }\n"
          "    }\n}\n";
-    {
-        std::string tab;
-        if (!E.ktab_vals.empty()) {
-            tab += "__constant__ __attribute__((aligned(64))) double mr_kc_tab[" + std::to_string(E.ktab_vals.size()) + "] = {";
-            for (size_t j = 0; j < E.ktab_vals.size(); j++) { tab += (j % 6 ? " " : "\n    "); tab += lit(E.ktab_vals[j]); tab += ","; }
-            tab += "\n};\n";
-        }
-        s.replace(s.find("/*MR_KTAB*/"), 11, tab);
-        for (size_t at; (at = s.find("/*MR_KBASE*/")) != std::string::npos;)
-            s.replace(at, 12, E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n");
-        const std::string kc = E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
-                               "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
-                               "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n";
-        for (size_t at; (at = s.find("/*MR_KC*/")) != std::string::npos;) s.replace(at, 9, kc);
-    }
-    return s;
+    return S.splice_constants("");
 }
 
 }   // namespace maray

@@ -147,10 +147,8 @@ def _build(tape):
     return build(tape)
 
 
-@pytest.mark.parametrize('rows2', ['0', '1'])
-def test_edge_scenes_build_offline(rows2, monkeypatch):
-    """Both kernels of every cell compile for gfx950 with hiprtc, one and two rows per wavefront."""
-    monkeypatch.setenv('MARAY_JIT_ROWS2', rows2)
+def test_edge_scenes_build_offline():
+    """Both kernels of every cell compile for gfx950 with hiprtc."""
     tapes = [M.Scene(c.data()).lower(hoist_rows=c.hoist) for c in CASES]
     with ThreadPoolExecutor(4) as pool:
         blobs = list(pool.map(lambda t: _build(t)[1], tapes))

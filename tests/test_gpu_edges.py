@@ -75,12 +75,11 @@ def test_edge_matrix_on_every_back_end():
 
 
 @pytest.mark.parametrize('knobs,only,backends', [
-    ({'MARAY_JIT_ROWS2': '1'}, ('guarded',), ('JIT',)),                                  # two rows per wavefront (guarded programs)
     ({'MARAY_JIT_WIDE_APP': '0'}, ('texel', 'texel-wide', 'guarded'), ('JIT',)),         # texel lookups one pixel per lane
     ({'MARAY_JIT_TEXEL_ONCE': '0'}, ('texel', 'texel-wide', 'guarded'), ('JIT',)),       # a call of mr_app per channel
     ({'MARAY_TAPE_GENERIC': '1'}, (), ('TAPE', 'INTERP')),                               # the interpreter's generic loop
     ({'MARAY_TAPE_ROW_GUARDS': '1'}, ('guarded', 'x-narrow', 'y-row'), ('TAPE', 'INTERP')),   # guards per row as y values
-], ids=['rows2', 'wide_app0', 'texel_once0', 'tape_generic', 'tape_row_guards'])
+], ids=['wide_app0', 'texel_once0', 'tape_generic', 'tape_row_guards'])
 def test_edge_matrix_under_knobs(knobs, only, backends):
     """The cells a knob changes the code of, on the back-ends it applies to."""
     _matrix(knobs, only, backends)

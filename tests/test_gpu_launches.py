@@ -221,9 +221,8 @@ for b in (JIT, M.BACKEND_TAPE, INTERP):
     launches(ctx, [FULL, RAGGED, FULL, RAGGED], (b, 'A B A B'))
     launches(ctx, [TOP, TOP, TOP, SHIFTED, SHIFTED, SHIFTED], (b, 'y0 = 0, then y0 = 32'))
     ctx.close()
-os.environ['MARAY_JIT_ROWS2'] = '1'          # (part of the kernels' code key: read when the context is built)
 ctx = M.Context(tape, backend=JIT)
-launches(ctx, [ODD] * 3 + [ODD2] * 3 + [ODD], 'two rows per wavefront, odd row counts')
+launches(ctx, [ODD] * 3 + [ODD2] * 3 + [ODD], 'odd row counts')
 ctx.close()
 print('repeated ok', name)
 """
@@ -234,8 +233,8 @@ def test_repeated_launches_of_one_geometry_equal_the_first(name):
     """Each of three geometries -- the whole 1024^2 frame, a ragged range (rows 5..1020) and a rank's share of row blocks
     that start off the guard groups -- launched three times on one context, on all three back-ends; then two geometries in
     turn (A A B B A B A B: orders computed, then evicted), the same (w, rows) at y0 = 0 and at y0 = 32 (the first
-    order must not serve the second), and under MARAY_JIT_ROWS2=1 odd row counts (two-row wavefronts meet a partial
-    last group under the order).  Every launch, RGB8 and f64, equals the interpreter's first render of its geometry;
+    order must not serve the second), and odd row counts on the specialised kernels (a partial last group under the
+    order).  Every launch, RGB8 and f64, equals the interpreter's first render of its geometry;
     those against the oracle on bands.  Scenes: chess, guarded triangles, curved shapes, guarded triangles with a
     Sin beyond the reduction range (deferred tiles), and the radial gradient (no guards: never an order)."""
     _run(_REPEATED, 'repeated ok', 300, name=name)
@@ -260,28 +259,24 @@ for w in w_list:
         ora.check(want[n], g, [(0, 4), (32, 64), (n - 40, n)], f64_bands=[(n - 4, n)])
     ref.close()
     assert float(want[65536][0][32:64].float().std()) > 1.0          # (a picture where the order puts its first rows)
-    for knobs in ({}, {'MARAY_JIT_ROWS2': '1'}):
-        os.environ.pop('MARAY_JIT_ROWS2', None)
-        os.environ.update(knobs)
-        ctx = M.Context(tape, backend=JIT)
-        # a launch taller than any below first: the context's y values, guard words and order then cover any stray read
-        assert same(render(ctx, w, H, TALL, f64=False), want_tall), (w, knobs, 'tall')
-        for n in (65534, 65535, 65536):
-            g = ('rows', 0, n)
-            for i in range(3):
-                got = render(ctx, w, H, g)
-                assert same(got, want[n]), (w, knobs, n, i)
-                if i == 0:
-                    ora.check(got, g, [(0, 4), (32, 64), (n - 40, n)], f64_bands=[(n - 4, n)])
-            assert same(render(ctx, w, H, g, f64=False), want[n]), (w, knobs, n, 'RGB8 only')
-        ctx.close()
+    ctx = M.Context(tape, backend=JIT)
+    # a launch taller than any below first: the context's y values, guard words and order then cover any stray read
+    assert same(render(ctx, w, H, TALL, f64=False), want_tall), (w, 'tall')
+    for n in (65534, 65535, 65536):
+        g = ('rows', 0, n)
+        for i in range(3):
+            got = render(ctx, w, H, g)
+            assert same(got, want[n]), (w, n, i)
+            if i == 0:
+                ora.check(got, g, [(0, 4), (32, 64), (n - 40, n)], f64_bands=[(n - 4, n)])
+        assert same(render(ctx, w, H, g, f64=False), want[n]), (w, n, 'RGB8 only')
+    ctx.close()
 print('grid ok')
 """
 
 
 def test_row_counts_at_the_grid_boundary_launched_again_and_again():
-    """65,534, 65,535 and 65,536 rows (one grid holds 65,534 rows of one-row wavefronts), 64 and 320 pixels wide, default
-    knobs and two rows per wavefront: each three times into a guarded buffer (f64 planes too), then once more RGB8 only,
+    """65,534, 65,535 and 65,536 rows (one grid holds 65,534 rows), 64 and 320 pixels wide: each three times into a guarded buffer (f64 planes too), then once more RGB8 only,
     after one 70,000-row launch on the same context.  The scene's costliest 32-row group is group 1 by construction:
     were a second grid to read the launch order from its start, it would write group 1's rows past the end of the
     raster, into the band.  Every byte against the interpreter; the oracle on rows 0-3, 32-63 and the last 40, f64

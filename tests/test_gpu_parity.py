@@ -600,11 +600,11 @@ def test_textured_scene(chess_bytes, monkeypatch):
 def test_ops_on_the_value_of_guarded_shapes(monkeypatch):
     """scenes.ops_on_a_guarded_mask: every kind of op, texture lookups included, fed with the value of guarded shapes -- literal
     zeros in the specialised kernel's variant for tiles without a guard bit (tests/test_jit_offline.py has the build): every
-    evaluator against the oracle on every pixel, the specialised kernel also two rows per wavefront and one texel per App."""
+    evaluator against the oracle on every pixel, the specialised kernel also with a call of mr_app per App op."""
     tex = scenes.textures(scale=8)
     data = encode((512, 256), scenes.ops_on_a_guarded_mask(512, 256))
     gpu_vs_oracle(data, 512, 256, [(0, 256)], textures=tex)
-    for env in ({'MARAY_JIT_ROWS2': '1'}, {'MARAY_JIT_TEXEL_ONCE': '0'}):
+    for env in ({'MARAY_JIT_TEXEL_ONCE': '0'},):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         gpu_vs_oracle(data, 512, 256, [(0, 256)], textures=tex, backends=[M.BACKEND_JIT])
@@ -941,8 +941,7 @@ def test_specialised_kernel_variants_selected_by_tuning_knobs(chess_bytes, monke
     for env in ({'MARAY_JIT_TILES': '1'}, {'MARAY_JIT_TILES': '5'}, {'MARAY_JIT_GUARD_W': '256', 'MARAY_JIT_GUARD_H': '8'},
                 {'MARAY_JIT_GUARD_W': '128', 'MARAY_JIT_GUARD_H': '16', 'MARAY_JIT_TILES': '3'}, {'MARAY_JIT_GUARD_W': '64', 'MARAY_JIT_GUARD_H': '128'},
                 {'MARAY_JIT_MIN_REGION': '0'}, {'MARAY_JIT_MIN_REGION': '12'}, {'MARAY_JIT_MIN_REGION': '100000'}, {'MARAY_JIT_ROW_GUARDS': '0'},
-                {'MARAY_JIT_HELPER': '0', 'MARAY_JIT_OPT': '-O1'}, {'MARAY_JIT_ROWS2': '1'}, {'MARAY_JIT_ROWS2': '1', 'MARAY_JIT_TILES': '3'},
-                {'MARAY_JIT_ROWS2': '0'}, {'MARAY_JIT_TEXEL_ONCE': '0'}):
+                {'MARAY_JIT_HELPER': '0', 'MARAY_JIT_OPT': '-O1'}, {'MARAY_JIT_TEXEL_ONCE': '0'}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         ctx = M.Context(tape, backend=M.BACKEND_JIT)

@@ -107,11 +107,11 @@ def test_random_scenes_build():
     assert built >= 35
 
 
-def test_ops_on_literal_operands_build_in_every_form(monkeypatch):
+def test_ops_on_literal_operands_build_in_every_form():
     """In the variant for tiles without a guard bit the value of every guarded shape is the literal 0.0: ops meet operands
     that are numbers, not vector values -- texture coordinates too (seed 6462 of round 4's second GPU sweep: `mr_texel(t, tex,
     0.0, yv[2])` resolved to the one-pixel form inside the four-pixel variant and the kernel did not compile).  The crafted
-    scene does that to every kind of op; both builds with one and with two rows per wavefront."""
+    scene does that to every kind of op."""
     import re
     from test_fuzz import lowered
     tape = M.Scene(encode((512, 256), scenes.ops_on_a_guarded_mask(512, 256))).lower()
@@ -124,9 +124,6 @@ def test_ops_on_literal_operands_build_in_every_form(monkeypatch):
     build(tape2)
     _, tape3 = lowered(8157, 2)      # its texture lookup is op 4: the texel's variable was named mr_tx4, which is a type
     build(tape3)
-    monkeypatch.setenv('MARAY_JIT_ROWS2', '1')
-    for t in (tape, tape2, tape3):
-        build(t)
 
 
 def test_code_key_is_remembered_under_the_programs_name(chess_bytes, tmp_path, monkeypatch):
@@ -249,20 +246,20 @@ def test_a_damaged_cache_file_is_a_miss(tmp_path):
     n0 = run()
     (path,) = glob.glob(str(tmp_path / '*.mrco'))
     good = open(path, 'rb').read()
-    hdr = list(struct.unpack('<10I', good[:40]))
-    assert hdr[0] == 0x3463726d and hdr[4] == n0 and hdr[7] in (64, 128, 256) and hdr[9] in (0, 1) and len(good) == 40 + hdr[4] + hdr[5] + 8
+    hdr = list(struct.unpack('<9I', good[:36]))
+    assert hdr[0] == 0x3563726d and hdr[4] == n0 and hdr[7] in (64, 128, 256) and len(good) == 36 + hdr[4] + hdr[5] + 8
 
     def fnv(data, h=0xcbf29ce484222325):
         for b in data:
             h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
         return h
-    assert struct.unpack('<Q', good[-8:])[0] == fnv(good[40 + hdr[4]:-8], fnv(good[40:40 + hdr[4]], fnv(good[:40])))     # the sum covers the header
-    for field, value in ((7, 0), (7, 96), (8, 24), (8, 0), (6, 5000), (3, 3), (1, 0), (9, 2)):
+    assert struct.unpack('<Q', good[-8:])[0] == fnv(good[36 + hdr[4]:-8], fnv(good[36:36 + hdr[4]], fnv(good[:36])))     # the sum covers the header
+    for field, value in ((7, 0), (7, 96), (8, 24), (8, 0), (6, 5000), (3, 3), (1, 0)):
         bad = list(hdr)
         bad[field] = value
-        head = struct.pack('<10I', *bad)
-        body = good[40:-8]
-        forged = head + body + struct.pack('<Q', fnv(good[40 + hdr[4]:-8], fnv(good[40:40 + hdr[4]], fnv(head))))   # checksum made to fit
+        head = struct.pack('<9I', *bad)
+        body = good[36:-8]
+        forged = head + body + struct.pack('<Q', fnv(good[36 + hdr[4]:-8], fnv(good[36:36 + hdr[4]], fnv(head))))   # checksum made to fit
         for blob in (forged, head + body + good[-8:]):
             open(path, 'wb').write(blob)
             os.utime(path, (1, 1))
