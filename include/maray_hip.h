@@ -91,6 +91,28 @@ int maray_scene_compress(maray_scene *s, uint32_t *n_vars3);
 /* `format!("{}", color[c]).chars().count()` (impl Display for Expr, src/lib.rs:196-366): what compress weighs. */
 int maray_scene_display_len(maray_scene *s, int c, uint64_t *len);
 
+/* ---- scene parameters: a free variable gets its value at render time --------------------------------------------
+ * A `Var` that no enclosing `Let` defines evaluates to NaN (src/cache.rs:32-40).  A scene may DECLARE such ids
+ * (`var(name)`, src/lib.rs:845-850) as parameters: the lowering then keeps them as run-time operands (include/
+ * maray_tape.h, SPEC PARAM), and a context takes new values between two launches -- the tape, the specialised kernels'
+ * code objects, the contexts and everything gen_to_image keeps are reused from frame to frame.
+ * Meaning: with parameter p = Var(id) set to v, the image is the one the reference renders for the scene in which every
+ * occurrence of Var(id) that resolves to no definition at its use site (inside Let definitions too) is replaced by an
+ * expression whose value is exactly v, bit for bit.  An occurrence a Let defines keeps its definition; a parameter that
+ * was never set is NaN, i.e. the scene as it renders without the declaration.
+ * The declared range [lo, hi] is what the lowering's static analysis works with (intervals, bounded Sin arguments,
+ * guards); -inf, +inf means "anything, NaN included".  It is a promise that is checked: a value outside the range (or
+ * NaN with any other range; -0.0 when the range starts at +0.0) is MARAY_E_ARG and the old value stays -- on the scene
+ * and, with the ranges that travel in the program, on every context.
+ * Declarations are not part of the encoding (`save` / `open` are unchanged); they are part of the name gen_to_image
+ * keeps a scene's program under, values are not.  Indices are handed out in declaration order; declaring an id again
+ * with the same range returns its index; the 65th parameter is MARAY_E_LIMIT; lo > hi or a NaN bound MARAY_E_ARG. */
+uint64_t maray_var_id(const char *name);      /* the id `var(name)` makes */
+int maray_scene_declare_param(maray_scene *s, uint64_t var_id, double lo, double hi, uint32_t *index /* may be NULL */);
+int maray_scene_param_count(const maray_scene *s, uint32_t *n);
+int maray_scene_param_info(const maray_scene *s, uint32_t index, uint64_t *var_id, double *lo, double *hi, double *value);   /* any may be NULL */
+int maray_scene_set_param(maray_scene *s, uint32_t index, double value);      /* what gen / gen_to_image render with */
+
 /* ---- lowering: Expr -> tape ---------------------------------------------------
  * Replaces what the reference does per pixel in `Expr::eval2` + `Cache`
  * (src/lib.rs:623-670, src/cache.rs) with a one-time pass: fix_color, inline
@@ -134,6 +156,10 @@ int maray_lower(const maray_scene *s, const maray_lower_opts *opts, maray_tape *
 void maray_tape_free(maray_tape *t);
 int maray_tape_program(const maray_tape *t, maray_program *out);   /* pointers valid until maray_tape_free */
 int maray_tape_get_info(const maray_tape *t, maray_tape_info *out);
+/* Parameters of the program: the scene's declared count when some op reads one, else 0 (then the program is the
+ * version-2 one the scene always had); and the range that travels with it. */
+int maray_tape_param_count(const maray_tape *t, uint32_t *n);
+int maray_tape_param_range(const maray_tape *t, uint32_t index, double *lo, double *hi);
 
 /* ---- tape-level device ABI (what a Rust `RenderMethod::Hip` arm binds) --------
  * Replaces par_gen_to_image / wasm_par_gen_to_image (src/render.rs:35-192) and
@@ -185,6 +211,13 @@ int maray_hip_device_count(int *n);
 int maray_hip_ctx_create(int device, const maray_program *prog, const maray_texture *tex, uint32_t n_tex,
                          const maray_ctx_opts *opts, maray_ctx **out);
 void maray_hip_ctx_free(maray_ctx *c);
+/* The values of the program's parameters for the launches enqueued AFTER this call (n = the program's count, else
+ * MARAY_E_ARG; each value inside its range, else MARAY_E_ARG and every old value stays).  Returns without touching the
+ * device: the next launch copies the values on its own stream in front of its ROW pass, from pinned staging, so the
+ * device-pointer entry points still return without synchronising and several frames may be in flight.  Launches of one
+ * context with different values go on one stream, or are ordered by the caller.  Every value is NaN until set. */
+int maray_hip_ctx_set_params(maray_ctx *c, const double *values, uint32_t n);
+int maray_hip_ctx_param_count(const maray_ctx *c, uint32_t *n);
 
 /* Evaluate rows [y0, y1) of a w x h image: p = [x as f64, y as f64],
  * x in [0,w) (src/render.rs:88-95).  rgb8: (y1-y0)*w*3 bytes, interleaved RGB,

@@ -42,6 +42,12 @@
  *                 YMIN / YMAX and not Y holds for every pixel of [XMIN, XMAX] x [YMIN, YMAX]; an
  *                 evaluator may compute it once for several rows.  A guard that reads Y is exact
  *                 for that row and valid for that row only.  Evaluating per row: YMIN = YMAX = Y.
+ *                 7 + p = PARAM p (both sections; version 3 only, p < n_params): the run-time value of scene
+ *                 parameter p -- a free `Var` (src/lib.rs:845-850; undefined = NaN, src/cache.rs:32-40) that the
+ *                 scene declared as a parameter.  One value per launch, the same for every pixel and row; set on a
+ *                 context between two launches (maray_hip_ctx_set_params), NaN until then.  The lowering never
+ *                 folds it; what it proved about the program (bounded Sin arguments, guards) holds for every
+ *                 value inside the declared range param_ranges[2 p] .. [2 p + 1], and only for those.
  *
  * Every op also leaves its result in ACC.  An op with dst == MARAY_DST_NONE
  * is consumed only through ACC by the next op.
@@ -52,6 +58,10 @@
 #include <stdint.h>
 
 #define MARAY_TAPE_VERSION 2u   /* 2: SPEC XMIN, YMAX, YMIN */
+/* A program at least one of whose ops reads a PARAM operand carries version 3: the two fields at the end of
+ * maray_program exist.  Every other program is version 2, byte for byte what it was; the evaluators accept both. */
+#define MARAY_TAPE_VERSION_PARAMS 3u
+#define MARAY_MAX_PARAMS 64u
 
 enum {
     MARAY_OP_NOP = 0,
@@ -95,7 +105,8 @@ enum {
 #define MARAY_MAX_INDEX 0x3FFFu
 
 enum { MARAY_K_SLOT = 0, MARAY_K_CONST = 1, MARAY_K_YVAL = 2, MARAY_K_SPEC = 3 };
-enum { MARAY_SPEC_X = 0, MARAY_SPEC_Y = 1, MARAY_SPEC_ACC = 2, MARAY_SPEC_XMAX = 3, MARAY_SPEC_XMIN = 4, MARAY_SPEC_YMAX = 5, MARAY_SPEC_YMIN = 6 };
+enum { MARAY_SPEC_X = 0, MARAY_SPEC_Y = 1, MARAY_SPEC_ACC = 2, MARAY_SPEC_XMAX = 3, MARAY_SPEC_XMIN = 4, MARAY_SPEC_YMAX = 5, MARAY_SPEC_YMIN = 6,
+       MARAY_SPEC_PARAM0 = 7 /* + p, p < MARAY_MAX_PARAMS */ };
 
 #define MARAY_REF(kind, index) ((uint32_t)(((kind) << 14) | ((index) & 0x3FFFu)))
 #define MARAY_REF_KIND(r) (((r) >> 14) & 3u)
@@ -113,7 +124,7 @@ enum { MARAY_SPEC_X = 0, MARAY_SPEC_Y = 1, MARAY_SPEC_ACC = 2, MARAY_SPEC_XMAX =
 
 /* A lowered program, as plain pointers + sizes (what the tape-level ABI takes). */
 typedef struct maray_program {
-    uint32_t version;        /* MARAY_TAPE_VERSION */
+    uint32_t version;        /* MARAY_TAPE_VERSION, or MARAY_TAPE_VERSION_PARAMS */
     uint32_t n_consts;
     const double *consts;
     uint32_t n_row_ops;      /* ROW section */
@@ -124,6 +135,9 @@ typedef struct maray_program {
     const uint64_t *pix_ops;
     uint32_t n_pix_slots;
     uint32_t n_app;          /* 1 + highest App id used (0 if none) */
+    /* version 3 only (a version-2 struct ends above and is never read past n_app): */
+    uint32_t n_params;       /* parameters declared on the scene, read by an op or not: 1 .. MARAY_MAX_PARAMS */
+    const double *param_ranges;   /* n_params pairs lo, hi (lo <= hi, no NaN; -inf, +inf = any value, NaN included) */
 } maray_program;
 
 #endif

@@ -24,7 +24,9 @@ class Program(C.Structure):
     _fields_ = [('version', C.c_uint32), ('n_consts', C.c_uint32), ('consts', C.POINTER(C.c_double)),
                 ('n_row_ops', C.c_uint32), ('row_ops', C.POINTER(C.c_uint64)), ('n_row_slots', C.c_uint32),
                 ('n_yvals', C.c_uint32), ('n_pix_ops', C.c_uint32), ('pix_ops', C.POINTER(C.c_uint64)),
-                ('n_pix_slots', C.c_uint32), ('n_app', C.c_uint32)]
+                ('n_pix_slots', C.c_uint32), ('n_app', C.c_uint32),
+                # version 3 only (include/maray_tape.h): a version-2 struct ends at n_app
+                ('n_params', C.c_uint32), ('param_ranges', C.POINTER(C.c_double))]
 
 
 class TapeInfo(C.Structure):
@@ -95,6 +97,15 @@ def lib():
         'maray_scene_simplify_ex': (C.c_int, [vp, C.c_uint32]),
         'maray_scene_compress': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_scene_display_len': (C.c_int, [vp, C.c_int, u64p]),
+        'maray_var_id': (C.c_uint64, [C.c_char_p]),
+        'maray_scene_declare_param': (C.c_int, [vp, C.c_uint64, C.c_double, C.c_double, C.POINTER(u32)]),
+        'maray_scene_param_count': (C.c_int, [vp, C.POINTER(u32)]),
+        'maray_scene_param_info': (C.c_int, [vp, u32, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        'maray_scene_set_param': (C.c_int, [vp, u32, C.c_double]),
+        'maray_tape_param_count': (C.c_int, [vp, C.POINTER(u32)]),
+        'maray_tape_param_range': (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        'maray_hip_ctx_set_params': (C.c_int, [vp, C.POINTER(C.c_double), u32]),
+        'maray_hip_ctx_param_count': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_lower': (C.c_int, [vp, C.POINTER(LowerOpts), C.POINTER(vp)]),
         'maray_tape_free': (None, [vp]),
         'maray_tape_program': (C.c_int, [vp, C.POINTER(Program)]),
@@ -147,6 +158,15 @@ def device_count():
     n = C.c_int(0)
     _check(lib().maray_hip_device_count(C.byref(n)))
     return n.value
+
+
+def var_id(name):
+    """The id `var(name)` makes (src/lib.rs:845-850)."""
+    return lib().maray_var_id(name.encode())
+
+
+def _param_id(name_or_id):
+    return var_id(name_or_id) if isinstance(name_or_id, str) else int(name_or_id)
 
 
 def _textures(textures):
@@ -244,6 +264,38 @@ class Scene:
         Context(..., samples=k) reduces."""
         _check(lib().maray_scene_supersample(self._h, k))
 
+    # ---- parameters (include/maray_hip.h, "scene parameters") ----
+    def declare_param(self, name_or_id, lo=float('-inf'), hi=float('inf')):
+        """Declares the free variable `var(name)` (or a raw id) as a run-time parameter with values in [lo, hi]; returns
+        its index.  Declaring it again with the same range returns the same index."""
+        k = C.c_uint32()
+        _check(lib().maray_scene_declare_param(self._h, _param_id(name_or_id), lo, hi, C.byref(k)))
+        return k.value
+
+    @property
+    def param_count(self):
+        n = C.c_uint32()
+        _check(lib().maray_scene_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def param_info(self, index):
+        """(var id, lo, hi, current value) of parameter `index`."""
+        i, lo, hi, v = C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
+        _check(lib().maray_scene_param_info(self._h, index, C.byref(i), C.byref(lo), C.byref(hi), C.byref(v)))
+        return i.value, lo.value, hi.value, v.value
+
+    def param_index(self, name_or_id):
+        want = _param_id(name_or_id)
+        for k in range(self.param_count):
+            if self.param_info(k)[0] == want:
+                return k
+        raise KeyError(name_or_id)
+
+    def set_param(self, index_or_name, value):
+        """The value gen / gen_to_image render parameter `index` (or the parameter declared for a name) with."""
+        k = self.param_index(index_or_name) if isinstance(index_or_name, str) else index_or_name
+        _check(lib().maray_scene_set_param(self._h, k, value))
+
     def lower(self, hoist_rows=True, plain_cse=False, fuse=True, skips=True, row_guards=True, private_regions=True, rebalance=True,
               y_spans=True):
         return Tape(self, hoist_rows, plain_cse, fuse, skips, row_guards, private_regions, rebalance, y_spans)
@@ -277,6 +329,18 @@ class Tape:
         if getattr(self, '_h', None):
             lib().maray_tape_free(self._h)
             self._h = None
+
+    @property
+    def param_count(self):
+        """Parameters of the program: the scene's declared count if some op reads one, else 0."""
+        n = C.c_uint32()
+        _check(lib().maray_tape_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def param_range(self, index):
+        lo, hi = C.c_double(), C.c_double()
+        _check(lib().maray_tape_param_range(self._h, index, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
 
     @property
     def jit_code_key(self):
@@ -349,6 +413,18 @@ class Context:
             lib().maray_hip_ctx_free(self._h)
             self._h = None
 
+    @property
+    def param_count(self):
+        n = C.c_uint32()
+        _check(lib().maray_hip_ctx_param_count(self._h, C.byref(n)))
+        return n.value
+
+    def set_params(self, values):
+        """The parameters' values for the launches enqueued after this call (one per parameter of the program, each
+        inside its declared range).  Returns without touching the device."""
+        a = (C.c_double * len(values))(*values)
+        _check(lib().maray_hip_ctx_set_params(self._h, a, len(values)))
+
     def render_rows(self, w, h, y0, y1, want_u8=True, want_f64=True):
         rows = y1 - y0
         rgb8 = np.zeros((rows, w, 3), np.uint8) if want_u8 else None
@@ -395,9 +471,13 @@ class Context:
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,
-                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0):
+                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None):
     """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
-    samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling)."""
+    samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling).
+    params={name_or_id: value}: sets these declared parameters of the scene first (Scene.declare_param); the scene's
+    program and contexts are found again whatever the values."""
+    for k, v in (params or {}).items():
+        scene.set_param(scene.param_index(k), v)
     w, h = size if size else scene.size
     img = np.zeros((h, w, 3), np.uint8) if out is None else out
     assert img.shape == (h, w, 3) and img.dtype == np.uint8 and img.flags['C_CONTIGUOUS']

@@ -4,6 +4,8 @@
 #include <pthread.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -137,6 +139,13 @@ void scene_cache_key(const maray_scene *cs, uint64_t out[2])
         s->key_valid = true;
     }
     out[0] = s->key[0]; out[1] = s->key[1];
+    // Declared parameters are not in the encoding but they are part of the program (its ranges, which Var ids are operands):
+    // folded in here, on every read, so that whatever renamed or dropped the scene's own name above -- rescale, supersample,
+    // simplify, ... -- keeps them.  Values are not part of the name: every frame of an animation finds the same program.
+    for (const ParamDecl &pd : s->s.params) {
+        struct { uint64_t tag, id; double lo, hi; } d = {0x5041524Dull, pd.id, pd.lo, pd.hi};      // "PARM"
+        hash128(&d, sizeof d, out);
+    }
 }
 
 // gen_to_image with samples = k: a private copy of the scene, supersampled (named after the scene and k)
@@ -153,9 +162,35 @@ maray_scene *scene_supersampled_copy(const maray_scene *cs, uint32_t k)
     return c.release();
 }
 
+maray_program load_program(const maray_program *p)
+{
+    if (!p) throw Error{MARAY_E_ARG, "null argument"};
+    maray_program r;
+    memset(&r, 0, sizeof r);
+    memcpy(&r, p, offsetof(maray_program, n_params));        // what a version-2 struct has
+    if (p->version == MARAY_TAPE_VERSION_PARAMS) { r.n_params = p->n_params; r.param_ranges = p->param_ranges; }
+    return r;
+}
+
+bool param_value_ok(const double *ranges, uint32_t p, double v)
+{
+    const double lo = ranges[2 * p], hi = ranges[2 * p + 1];
+    if (lo == -INFINITY && hi == INFINITY) return true;          // anything, NaN included
+    if (!(v >= lo && v <= hi)) return false;                     // (false for NaN)
+    if (v == 0.0 && lo == 0.0 && std::signbit(v) && !std::signbit(lo)) return false;      // -0.0 is below +0.0 here
+    if (v == 0.0 && hi == 0.0 && !std::signbit(v) && std::signbit(hi)) return false;
+    return true;
+}
+
 void validate_program(const maray_program &p)
 {
-    if (p.version != MARAY_TAPE_VERSION) throw Error{MARAY_E_ARG, "tape version mismatch"};
+    if (p.version != MARAY_TAPE_VERSION && p.version != MARAY_TAPE_VERSION_PARAMS) throw Error{MARAY_E_ARG, "tape version mismatch"};
+    const uint32_t n_params = p.version == MARAY_TAPE_VERSION_PARAMS ? p.n_params : 0u;
+    if (p.version == MARAY_TAPE_VERSION_PARAMS) {
+        if (n_params == 0 || n_params > MARAY_MAX_PARAMS || !p.param_ranges) throw Error{MARAY_E_ARG, "a version-3 program has 1 to 64 parameters and their ranges"};
+        for (uint32_t k = 0; k < n_params; k++)
+            if (!(p.param_ranges[2 * k] <= p.param_ranges[2 * k + 1])) throw Error{MARAY_E_ARG, "parameter range with lo > hi or a NaN bound"};
+    }
     if ((p.n_consts && !p.consts) || (p.n_row_ops && !p.row_ops) || (p.n_pix_ops && !p.pix_ops))
         throw Error{MARAY_E_ARG, "null section pointer"};
     if (p.n_row_slots > MARAY_MAX_SLOTS || p.n_pix_slots > MARAY_MAX_SLOTS) throw Error{MARAY_E_LIMIT, "too many slots"};
@@ -188,7 +223,8 @@ void validate_program(const maray_program &p)
                 case MARAY_K_SLOT: ok = idx < n_slots && written[idx]; break;
                 case MARAY_K_CONST: ok = idx < p.n_consts; break;
                 case MARAY_K_YVAL: ok = pixel && idx < p.n_yvals; break;
-                default: ok = idx <= MARAY_SPEC_YMIN && (idx != MARAY_SPEC_ACC || have_acc) && (idx != MARAY_SPEC_X || pixel) &&
+                default: ok = idx >= MARAY_SPEC_PARAM0 ? idx - MARAY_SPEC_PARAM0 < n_params :      // a parameter: either section
+                              (idx != MARAY_SPEC_ACC || have_acc) && (idx != MARAY_SPEC_X || pixel) &&
                               (idx < MARAY_SPEC_XMAX || !pixel);      // the span specials are for the ROW section
                 }
                 if (!ok) throw Error{MARAY_E_ARG, "operand out of range or read before write at op " + std::to_string(i)};
@@ -368,6 +404,67 @@ int maray_scene_supersample(maray_scene *s, uint32_t k)
     });
 }
 
+// ---- scene parameters ---------------------------------------------------------
+uint64_t maray_var_id(const char *name)
+{
+    // `var(name)` (src/lib.rs:845-850): fnv::FnvHasher (FNV-1a, 64 bits) over what Rust's `str::hash` feeds it, the name's
+    // bytes and a 0xff terminator; the same id as var() of include/maray_builders.hpp
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (const unsigned char *p = (const unsigned char *)(name ? name : ""); *p; p++) { h ^= *p; h *= 0x100000001b3ull; }
+    h ^= 0xffu; h *= 0x100000001b3ull;
+    return h;
+}
+
+int maray_scene_declare_param(maray_scene *s, uint64_t var_id, double lo, double hi, uint32_t *index)
+{
+    return guard([&] {
+        REQUIRE(s, "null argument");
+        REQUIRE(lo <= hi, "parameter range with lo > hi or a NaN bound");
+        std::vector<ParamDecl> &ps = s->s.params;
+        for (size_t k = 0; k < ps.size(); k++)
+            if (ps[k].id == var_id) {
+                REQUIRE(memcmp(&ps[k].lo, &lo, 8) == 0 && memcmp(&ps[k].hi, &hi, 8) == 0, "parameter declared twice with different ranges");
+                if (index) *index = (uint32_t)k;
+                return;
+            }
+        if (ps.size() >= MARAY_MAX_PARAMS) throw Error{MARAY_E_LIMIT, "more than 64 parameters"};
+        ParamDecl pd;
+        pd.id = var_id; pd.lo = lo; pd.hi = hi; pd.value = NAN;
+        // (the scene's stored name does not change: declarations are folded into it where it is read, scene_cache_key)
+        std::lock_guard<std::mutex> lk(s->key_mutex);
+        ps.push_back(pd);
+        if (index) *index = (uint32_t)ps.size() - 1;
+    });
+}
+
+int maray_scene_param_count(const maray_scene *s, uint32_t *n)
+{
+    return guard([&] { REQUIRE(s && n, "null argument"); *n = (uint32_t)s->s.params.size(); });
+}
+
+int maray_scene_param_info(const maray_scene *s, uint32_t index, uint64_t *var_id, double *lo, double *hi, double *value)
+{
+    return guard([&] {
+        REQUIRE(s && index < s->s.params.size(), "no such parameter");
+        const ParamDecl &pd = s->s.params[index];
+        if (var_id) *var_id = pd.id;
+        if (lo) *lo = pd.lo;
+        if (hi) *hi = pd.hi;
+        if (value) *value = pd.value;
+    });
+}
+
+int maray_scene_set_param(maray_scene *s, uint32_t index, double value)
+{
+    return guard([&] {
+        REQUIRE(s && index < s->s.params.size(), "no such parameter");
+        ParamDecl &pd = s->s.params[index];
+        const double r[2] = {pd.lo, pd.hi};
+        REQUIRE(param_value_ok(r, 0, value), "parameter value outside its declared range");
+        pd.value = value;
+    });
+}
+
 int maray_scene_simplify(maray_scene *s)
 {
     return guard([&] { REQUIRE(s, "null argument"); s->key_valid = false; run_big_stack([&] { scene_simplify(s->s); }); });
@@ -426,6 +523,19 @@ int maray_tape_get_info(const maray_tape *t, maray_tape_info *out)
     return guard([&] { REQUIRE(t && out, "null argument"); *out = t->t.info; });
 }
 
+int maray_tape_param_count(const maray_tape *t, uint32_t *n)
+{
+    return guard([&] { REQUIRE(t && n, "null argument"); *n = (uint32_t)(t->t.param_ranges.size() / 2); });
+}
+
+int maray_tape_param_range(const maray_tape *t, uint32_t index, double *lo, double *hi)
+{
+    return guard([&] {
+        REQUIRE(t && lo && hi && index < t->t.param_ranges.size() / 2, "no such parameter");
+        *lo = t->t.param_ranges[2 * index]; *hi = t->t.param_ranges[2 * index + 1];
+    });
+}
+
 // ---- device ---------------------------------------------------------------------
 int maray_hip_device_count(int *n)
 {
@@ -439,6 +549,8 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         REQUIRE(prog && out, "null argument");
         REQUIRE(n_tex == 0 || tex, "null texture table");
         *out = nullptr;
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         validate_program(*prog);
         if (prog->n_app > 5u * n_tex)   // reference: rt.functions[id] panics (src/lib.rs:665)
             throw Error{MARAY_E_APP_RANGE, "scene calls App id " + std::to_string(prog->n_app - 1) + " but only " +
@@ -487,7 +599,31 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         c->backend = b;
         c->n_tex = n_tex;
         c->samples = samples;
+        if (prog->n_params) c->param_ranges.assign(prog->param_ranges, prog->param_ranges + 2 * (size_t)prog->n_params);
+        for (uint32_t p = 0; p < prog->n_params; p++) c->params_ready = c->params_ready && param_value_ok(c->param_ranges.data(), p, NAN);
         *out = c;
+    });
+}
+
+int maray_hip_ctx_param_count(const maray_ctx *c, uint32_t *n)
+{
+    return guard([&] { REQUIRE(c && n, "null argument"); *n = (uint32_t)(c->param_ranges.size() / 2); });
+}
+
+int maray_hip_ctx_set_params(maray_ctx *c, const double *values, uint32_t n)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend, "null context");
+        REQUIRE(n == c->param_ranges.size() / 2, "parameter count differs from the program's");
+        if (!n) return;
+        REQUIRE(values, "null argument");
+        // every value is checked before any is taken: a call that fails leaves the old values.  The ranges are the program's:
+        // what the lowering proved -- a bounded Sin's table index among it -- holds for values inside them only.
+        for (uint32_t p = 0; p < n; p++)
+            if (!param_value_ok(c->param_ranges.data(), p, values[p]))
+                throw Error{MARAY_E_ARG, "value of parameter " + std::to_string(p) + " is outside its declared range"};
+        c->backend->set_params(values, n);
+        c->params_ready = true;
     });
 }
 
@@ -510,6 +646,7 @@ static void check_rows(uint32_t w, uint32_t h, uint32_t y0, uint32_t y1)
 // MARAY_DOMAIN_MAX.  It writes RGB8 only.
 static void check_samples(const maray_ctx *c, uint32_t w, uint32_t h, bool want64)
 {
+    if (!c->params_ready) throw Error{MARAY_E_ARG, "the program's parameters have ranges that exclude NaN and no values yet: call maray_hip_ctx_set_params first"};
     if (c->samples <= 1) return;
     if (want64) throw Error{MARAY_E_ARG, "a supersampling context renders RGB8 only (no f64 planes)"};
     if ((uint64_t)w * c->samples > MARAY_DOMAIN_MAX || (uint64_t)h * c->samples > MARAY_DOMAIN_MAX)
@@ -625,6 +762,8 @@ int maray_jit_source(const maray_program *prog, char **src_out)
 {
     return guard([&] {
         REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         const std::string s = jit_source(*prog);
         *src_out = (char *)malloc(s.size() + 1);
         if (!*src_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
@@ -636,6 +775,8 @@ int maray_jit_source_samples(const maray_program *prog, uint32_t k, char **src_o
 {
     return guard([&] {
         REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         const std::string s = jit_source_samples(*prog, k);
         *src_out = (char *)malloc(s.size() + 1);
         if (!*src_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
@@ -647,6 +788,8 @@ int maray_jit_source_rows(const maray_program *prog, char **src_out, uint32_t *n
 {
     return guard([&] {
         REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         const std::string s = jit_source_rows(*prog, n_chunks);
         *src_out = (char *)malloc(s.size() + 1);
         if (!*src_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
@@ -658,6 +801,8 @@ int maray_row_cone(const maray_program *prog, uint32_t first_out, uint32_t n_out
 {
     return guard([&] {
         REQUIRE(prog && ops_out && n_ops_out && n_slots_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         validate_program(*prog);
         const RowTapeDeps deps = row_tape_deps(*prog);
         std::vector<uint32_t> outs;
@@ -678,6 +823,8 @@ int maray_jit_build(const maray_program *prog, void **code_out, size_t *len_out)
 {
     return guard([&] {
         REQUIRE(prog && code_out && len_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         // both kernels, through the code object cache (this is also how a cache is warmed ahead of a render)
         const std::vector<char> &code = jit_code_for(*prog)->pix;
         *code_out = malloc(code.size() ? code.size() : 1);
@@ -691,6 +838,8 @@ int maray_jit_build_samples(const maray_program *prog, uint32_t k, void **code_o
 {
     return guard([&] {
         REQUIRE(prog && code_out && len_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         const std::shared_ptr<const std::vector<char>> code = jit_code_samples(*prog, k);
         *code_out = malloc(code->size() ? code->size() : 1);
         if (!*code_out) throw Error{MARAY_E_INTERNAL, "out of memory"};
@@ -703,6 +852,8 @@ int maray_jit_code_key(const maray_program *prog, char *out33)
 {
     return guard([&] {
         REQUIRE(prog && out33, "null argument");
+        const maray_program loaded = load_program(prog);
+        prog = &loaded;
         const std::string k = jit_code_key(*prog);
         memcpy(out33, k.c_str(), std::min<size_t>(k.size(), 32) + 1);
         out33[32] = 0;
@@ -711,7 +862,7 @@ int maray_jit_code_key(const maray_program *prog, char *out33)
 
 int maray_jit_code_cached(const maray_program *prog, int *cached)
 {
-    return guard([&] { REQUIRE(prog && cached, "null argument"); *cached = jit_code_is_cached(*prog) ? 1 : 0; });
+    return guard([&] { REQUIRE(prog && cached, "null argument"); *cached = jit_code_is_cached(load_program(prog)) ? 1 : 0; });
 }
 
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }

@@ -35,6 +35,10 @@ struct Backend {
     // average ms per launch of the pixel kernel, HIP events on the launch stream
     virtual float time_rows(uint32_t w, uint32_t h, const RowBlocks &rb, void *d8, void *d64, int reps) = 0;
     virtual const char *kernel_name() const = 0;
+    // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
+    // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
+    // own stream, in front of its ROW pass.
+    virtual void set_params(const double *, uint32_t) { throw Error{MARAY_E_INTERNAL, "this program has no parameters"}; }
     // Tape interpreter only: re-evaluate the 256-pixel tiles of the device work list
     // {count, tile, tile, ...} (tile = row_in_launch * ceil(w/256) + x/256), reading the row
     // values from `yvals` instead of running the ROW section.  Enqueued on `stream`.
@@ -75,6 +79,32 @@ std::shared_ptr<const JitCode> jit_code_for(const maray_program &prog);      // 
 std::string jit_code_key(const maray_program &prog);                        // 128-bit hash (hex) of generated sources + toolchain: the cache's file name
 bool jit_code_is_cached(const maray_program &prog);                         // in this process or on disk: no hiprtc build needed
 void validate_program(const maray_program &p);
+maray_program load_program(const maray_program *p);
+
+// The interpreter's view of a program with parameters: PARAM p is the constant n_consts + p of a pool that ends in the
+// parameters' values (NaN until set), so that its kernels -- generic loop, pre-decoded loop, LDS staging -- read a
+// parameter as the wave-uniform table entry a constant is, unchanged.  A version-2 program in every other respect.
+struct ParamsAsConsts {
+    std::vector<double> consts;
+    std::vector<uint64_t> row_ops, pix_ops;
+    maray_program prog;                 // points into this object
+    explicit ParamsAsConsts(const maray_program &P);
+    ParamsAsConsts(const ParamsAsConsts &) = delete;
+};
+
+// Parameter values on their way to the device: pinned host slots, so that a launch's copy is asynchronous and several
+// frames can be in flight.  A slot is reused once the copy that read it has completed (an event per slot).
+struct ParamRing {
+    static constexpr int SLOTS = 8;
+    double *host = nullptr;
+    void *events[SLOTS] = {};
+    uint32_t n = 0;
+    int next = 0;
+    void init(uint32_t n_params);       // throws Error
+    double *take();                     // the next free slot (waits for its last copy, if that is still in flight)
+    void sent(void *stream);            // the slot take() returned is being read by a copy enqueued on `stream`
+    void release();
+};
 
 // ---- ROW-tape analysis shared by the evaluators (row_split.cpp) ------------------------------------
 // Number of leading y values that PIXEL ops read as arithmetic operands; the rest of the table only gates SKIP ops.
@@ -102,4 +132,8 @@ struct maray_ctx {
     maray::Backend *backend = nullptr;
     uint32_t n_tex = 0;
     uint32_t samples = 1;       // maray_ctx_opts.samples (0 taken as 1)
+    std::vector<double> param_ranges;   // lo, hi per parameter of the program: what maray_hip_ctx_set_params enforces
+    // Every parameter starts as NaN, which only the range (-inf, +inf) admits: a program with any other range renders once
+    // its values have been set (what the lowering proved from a finite range does not hold for NaN).
+    bool params_ready = true;
 };

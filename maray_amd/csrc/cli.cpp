@@ -1,7 +1,10 @@
 // cli.cpp — `maray` command line (product code).  Mirrors examples/maray.rs:
 //   maray -c N -i in.maray -o out.png [-t tex.png ...]        (:9-47)
-// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing).  -c/--cpus is parsed and
+// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), -p NAME=VALUE[:LO:HI] (a scene parameter:
+// the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
+// the one program and the contexts the first frame set up).  -c/--cpus is parsed and
 // ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,13 +24,57 @@ static void usage()
             "  -t, --textures <textures>... Texture files (PNG, BMP, PNM, TGA, QOI, farbfeld, GIF, TIFF)\n"
             "      --gpus <n>               Number of MI355X devices (default: all)\n"
             "      --backend <b>            auto | jit | tape | tape-smem (default: auto)\n"
-            "  -s, --samples <k>            Anti-aliasing: k x k samples per pixel, box-filtered; k = 1, 2, 4 or 8 (default: 1)\n");
+            "  -s, --samples <k>            Anti-aliasing: k x k samples per pixel, box-filtered; k = 1, 2, 4 or 8 (default: 1)\n"
+            "  -p, --param <name=v[:lo:hi]> Value of the scene's free variable `name` (repeatable); lo:hi = the range it is\n"
+            "                               declared with (default: any value)\n"
+            "      --animate <name=a:b:n>   n images, `name` going from a to b in equal steps; --output needs a `%%d`\n"
+            "                               conversion (`frame%%03d.png`), numbered from 0\n");
 }
+
+namespace {
+struct Param { std::string name; double value, lo, hi; };
+
+// "a:b:c" -> numbers, every field a whole strtod
+bool numbers(const std::string &t, std::vector<double> &out)
+{
+    size_t at = 0;
+    for (;;) {
+        const size_t end = t.find(':', at);
+        const std::string f = t.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        char *rest = nullptr;
+        const double v = strtod(f.c_str(), &rest);
+        if (f.empty() || !rest || *rest) return false;
+        out.push_back(v);
+        if (end == std::string::npos) return true;
+        at = end + 1;
+    }
+}
+
+bool split_name(const std::string &arg, std::string &name, std::vector<double> &nums)
+{
+    const size_t eq = arg.find('=');
+    if (eq == std::string::npos || eq == 0) return false;
+    name = arg.substr(0, eq);
+    return numbers(arg.substr(eq + 1), nums);
+}
+
+// exactly one conversion, %d with an optional zero-padded width
+bool numbered(const std::string &path)
+{
+    const size_t at = path.find('%');
+    if (at == std::string::npos || path.find('%', at + 1) != std::string::npos) return false;
+    size_t k = at + 1;
+    while (k < path.size() && path[k] >= '0' && path[k] <= '9') k++;
+    return k < path.size() && path[k] == 'd' && k - at <= 4;
+}
+}   // namespace
 
 int main(int argc, char **argv)
 {
     std::string input, output;
     std::vector<std::string> textures;
+    std::vector<Param> params;
+    Param anim; uint32_t frames = 0;
     maray_gen_opts go;
     memset(&go, 0, sizeof go);
     go.backend = MARAY_BACKEND_AUTO;
@@ -48,6 +95,19 @@ int main(int argc, char **argv)
             }
             go.samples = (uint32_t)(k[0] - '0');
         }
+        else if (a == "-p" || a == "--param") {
+            Param p; std::vector<double> n;
+            if (!split_name(val(), p.name, n) || (n.size() != 1 && n.size() != 3)) { fprintf(stderr, "Error: -p takes NAME=VALUE or NAME=VALUE:LO:HI\n"); usage(); return 2; }
+            p.value = n[0]; p.lo = n.size() == 3 ? n[1] : -INFINITY; p.hi = n.size() == 3 ? n[2] : INFINITY;
+            params.push_back(p);
+        }
+        else if (a == "--animate") {
+            std::vector<double> n;
+            if (!split_name(val(), anim.name, n) || n.size() != 3 || !(n[2] >= 1.0 && n[2] <= 1e6) || n[2] != std::floor(n[2]) || !(n[0] == n[0] && n[1] == n[1])) {
+                fprintf(stderr, "Error: --animate takes NAME=FROM:TO:FRAMES with FRAMES >= 1\n"); usage(); return 2;
+            }
+            anim.value = n[0]; anim.hi = n[1]; frames = (uint32_t)n[2];
+        }
         else if (a == "--backend") {
             std::string b = val();
             if (b == "tape") go.backend = MARAY_BACKEND_TAPE;
@@ -59,6 +119,7 @@ int main(int argc, char **argv)
         else { usage(); return 2; }
     }
     if (input.empty() || output.empty()) { usage(); return 2; }
+    if (frames && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
 
     maray_scene *scene = nullptr;
     if (maray_scene_open(input.c_str(), &scene)) { fprintf(stderr, "Error: %s\n", maray_last_error()); return 1; }
@@ -70,8 +131,31 @@ int main(int argc, char **argv)
         rasters.push_back(rgb);
         tex.push_back(maray_texture{rgb, w, h});
     }
+    // parameters: declared with their ranges and set; a value its range excludes is the command line's mistake
+    for (const Param &p : params) {
+        uint32_t k = 0;
+        if (maray_scene_declare_param(scene, maray_var_id(p.name.c_str()), p.lo, p.hi, &k) || maray_scene_set_param(scene, k, p.value)) {
+            fprintf(stderr, "Error: -p %s: %s\n", p.name.c_str(), maray_last_error());
+            return 2;
+        }
+    }
+    uint32_t anim_index = 0;
+    const double from = anim.value, to = anim.hi;
+    if (frames && maray_scene_declare_param(scene, maray_var_id(anim.name.c_str()), std::fmin(from, to), std::fmax(from, to), &anim_index)) {
+        fprintf(stderr, "Error: --animate %s: %s\n", anim.name.c_str(), maray_last_error());
+        return 2;
+    }
     maray_report rep{MARAY_REPORT_DURATION_MS, 500};   // Report::Duration(500 ms), examples/maray.rs:77-79
-    int rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());
+    int rc = 0;
+    if (!frames) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());
+    for (uint32_t f = 0; f < frames && !rc; f++) {
+        // FROM + i (TO - FROM) / (FRAMES - 1) in f64; the last frame is TO itself (the range's end, whatever the rounding)
+        const double v = frames == 1 ? from : f == frames - 1 ? to : from + (double)f * (to - from) / (double)(frames - 1);
+        char path[4096];
+        snprintf(path, sizeof path, output.c_str(), (int)f);
+        rc = maray_scene_set_param(scene, anim_index, v);
+        if (!rc) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, path);
+    }
     if (rc) fprintf(stderr, "Error: %s\n", maray_last_error());
     for (auto p : rasters) maray_free(p);
     maray_scene_free(scene);

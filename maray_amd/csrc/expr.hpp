@@ -43,7 +43,15 @@ struct Token {
     std::string str;
 };
 
+// A free `Var` id declared as a run-time parameter (include/maray_hip.h, "scene parameters"): not part of the encoding.
+struct ParamDecl {
+    uint64_t id = 0;
+    double lo = 0.0, hi = 0.0;      // declared range; -inf, +inf: any value, NaN included
+    double value = 0.0;             // what gen / gen_to_image render with (NaN until set)
+};
+
 struct Scene {
+    std::vector<ParamDecl> params;  // index = parameter number
     std::vector<Node> nodes;
     std::vector<Ctx> ctxs;
     std::vector<std::vector<Token>> toklists;

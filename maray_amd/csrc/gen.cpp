@@ -305,6 +305,16 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     } else pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
     maray_tape_program(entry->tape, &prog);
+    // The scene's current parameter values: the program was found by its name (declarations in, values out), so a frame
+    // with other values is the same entry, the same contexts and the same code objects; each context is given the values
+    // in front of its tiles.  (A program none of whose ops reads a parameter has none: nothing is set.)
+    std::vector<double> param_values;
+    if (prog.version == MARAY_TAPE_VERSION_PARAMS)
+        for (uint32_t p = 0; p < prog.n_params; p++) {
+            double v = 0.0;
+            if (const int rc = maray_scene_param_info(s, p, nullptr, nullptr, nullptr, &v)) return rc;
+            param_values.push_back(v);
+        }
 
     maray_ctx_opts co;
     memset(&co, 0, sizeof co);
@@ -329,6 +339,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         const IdleCtx kept = gen_cache_take(*entry, dev, co.backend == MARAY_BACKEND_AUTO, co.hint_mpixels);
         maray_ctx *ctx = kept.ctx;
         int r = ctx ? MARAY_OK : maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx);
+        if (!r && !param_values.empty()) r = maray_hip_ctx_set_params(ctx, param_values.data(), (uint32_t)param_values.size());
         if (!r && !share[d].empty())
             r = maray_hip_render_tiles(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), rgb8, on_tile, &tu);
         const std::string msg = r ? maray_last_error() : "";      // this thread's message, re-raised on the calling thread

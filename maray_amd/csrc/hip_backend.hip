@@ -20,8 +20,10 @@
 // consecutive 8-byte words per wave, conflict-free.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -703,6 +705,12 @@ struct TapeBackend final : Backend {
     uint32_t row_lds_slots = 0, row_lds_bytes = 0;
     uint32_t ss = 1;                    // samples per output pixel and axis (maray_tape_pixels_ss when > 1)
     std::string kname;
+    // Parameters (backend.hpp, ParamsAsConsts): the tail of d_consts, n_consts_own .. + n_params.  set_params keeps the values
+    // on the host; the first launch after it copies them on its stream, ahead of everything the launch enqueues.
+    uint32_t n_params = 0, n_consts_own = 0;
+    std::vector<double> param_values;
+    bool params_dirty = false;
+    ParamRing ring;
 
     ~TapeBackend() override {
         (void)hipSetDevice(device);
@@ -713,10 +721,19 @@ struct TapeBackend final : Backend {
         (void)hipFree(d_xtape_bits); (void)hipFree(d_xtape_rows); (void)hipFree(d_xrows); (void)hipFree(d_xguards);
         (void)hipFree(d_row_job_off); (void)hipFree(d_row_job_len); (void)hipFree(d_job_id); (void)hipFree(d_queue);
         if (handover) (void)hipEventDestroy(handover);
+        ring.release();
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
     }
 
-    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples) {
+    void init(int dev, const maray_program &prog_in, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples) {
+        // a program with parameters: from here on the version-2 program whose pool ends in their values
+        std::unique_ptr<ParamsAsConsts> as_consts;
+        if (prog_in.n_params) {
+            as_consts.reset(new ParamsAsConsts(prog_in));
+            n_params = prog_in.n_params; n_consts_own = prog_in.n_consts;
+            param_values.assign(n_params, NAN);
+        }
+        const maray_program &prog = as_consts ? as_consts->prog : prog_in;
         device = dev;
         ss = samples;
         HIP_TRY(hipSetDevice(dev));
@@ -728,6 +745,7 @@ struct TapeBackend final : Backend {
         pipe = host_pipe_acquire(dev);
         own_stream = pipe->compute_stream();
         HIP_TRY(hipEventCreateWithFlags(&handover, hipEventDisableTiming));
+        if (n_params) ring.init(n_params);
         auto up = [&](const void *src, size_t bytes, void **dst) {
             HIP_TRY(hipMalloc(dst, bytes ? bytes : 8));
             if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -889,6 +907,17 @@ struct TapeBackend final : Backend {
             HIP_TRY(hipStreamWaitEvent(st, handover, 0));
         }
         last_stream = st; have_last = true;
+        if (params_dirty) {
+            // New values: copied on this launch's stream, so launches enqueued before the set_params call keep theirs.  Without
+            // a ROW pass of its own (time_rows; not the drain, whose y values are the caller's and of the same values) the y
+            // values and guard bits in the tables are the old values': this launch gets the pass.
+            double *slot = ring.take();
+            memcpy(slot, param_values.data(), (size_t)n_params * sizeof(double));
+            HIP_TRY(hipMemcpyAsync(d_consts + n_consts_own, slot, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice, st));
+            ring.sent(st);
+            params_dirty = false;
+            if (!ext_yvals) rows_pass = true;
+        }
         HIP_TRY(hipMemsetAsync(d_queue, 0, 8, st));              // both kernels' work queues start at 0
         (void)hipGetLastError();        // the launches below are checked with hipGetLastError(): drop what an earlier, unrelated call left
         if (!ext_yvals) ensure(d_yvals, yvals_cap, (size_t)rows * std::max<uint32_t>(P.n_yvals, 1));
@@ -1018,6 +1047,13 @@ struct TapeBackend final : Backend {
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         return ms / (float)(reps > 0 ? reps : 1);
+    }
+
+    void set_params(const double *values, uint32_t n) override {
+        if (n != n_params) throw Error{MARAY_E_INTERNAL, "parameter count"};
+        if (memcmp(param_values.data(), values, (size_t)n * sizeof(double)) == 0) return;       // the same bits: nothing to send
+        param_values.assign(values, values + n);
+        params_dirty = true;
     }
 
     const char *kernel_name() const override { return kname.c_str(); }

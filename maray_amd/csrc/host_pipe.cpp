@@ -43,6 +43,39 @@ void host_free_pinned(void *p)
     if (p) (void)hipHostFree(p);
 }
 
+// ---- parameter staging (backend.hpp) -------------------------------------------------------------------------------------
+void ParamRing::init(uint32_t n_params)
+{
+    n = n_params;
+    host = (double *)host_alloc_pinned((size_t)SLOTS * n * sizeof(double));
+    for (int i = 0; i < SLOTS; i++) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        events[i] = e;
+    }
+}
+
+double *ParamRing::take()
+{
+    // (an event that was never recorded is complete; one that was says whether the copy out of this slot is done)
+    HIP_TRY(hipEventSynchronize((hipEvent_t)events[next]));
+    return host + (size_t)next * n;
+}
+
+void ParamRing::sent(void *stream)
+{
+    HIP_TRY(hipEventRecord((hipEvent_t)events[next], (hipStream_t)stream));
+    next = (next + 1) % SLOTS;
+}
+
+void ParamRing::release()
+{
+    // (a copy may still be reading a slot: the events are the ring's own, whatever became of the caller's stream)
+    for (void *&e : events) if (e) { (void)hipEventSynchronize((hipEvent_t)e); (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+    host_free_pinned(host);
+    host = nullptr;
+}
+
 void host_register(void *p, size_t bytes) { HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterPortable)); }
 void host_unregister(void *p) { HIP_TRY(hipHostUnregister(p)); }
 

@@ -67,6 +67,12 @@ struct JitBackend final : Backend {
     bool has_sin = false;               // some Sin argument is not proven bounded: tiles may be deferred to `slow`
     hipStream_t last_stream = nullptr; bool have_last = false;      // the stream of the last launch (see launch())
     hipEvent_t handover = nullptr;
+    // Parameters: the table `mr_par_tab` of every module of the program (PIXEL, ROW, supersampling); values wait on the host
+    // (set_params) for the next launch, which copies them on its stream in front of its ROW pass (send_params)
+    std::vector<hipDeviceptr_t> d_par;
+    std::vector<double> param_values;
+    bool params_dirty = false;
+    ParamRing ring;
 
     ~JitBackend() override {
         (void)hipSetDevice(device);
@@ -80,6 +86,7 @@ struct JitBackend final : Backend {
         (void)hipFree(d_order); (void)hipFree(d_rgb8);
         (void)hipFree(d_yvals); (void)hipFree(d_gbits);
         if (handover) (void)hipEventDestroy(handover);
+        ring.release();
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
     }
 
@@ -142,6 +149,20 @@ struct JitBackend final : Backend {
             lap("load ROW module");
 
         }
+        if (prog.n_params) {
+            param_values.assign(prog.n_params, NAN);
+            for (hipModule_t m : {mod, mod_rows, mod_ss}) {
+                if (!m) continue;
+                hipDeviceptr_t p = nullptr;
+                size_t bytes = 0;
+                HIP_TRY(hipModuleGetGlobal(&p, &bytes, m, "mr_par_tab"));
+                if (bytes != (size_t)prog.n_params * sizeof(double)) throw Error{MARAY_E_INTERNAL, "parameter table of a module has another size than the program"};
+                HIP_TRY(hipMemcpyHtoD(p, param_values.data(), bytes));          // NaN until set
+                d_par.push_back(p);
+            }
+            ring.init(prog.n_params);
+            P.param_ranges = nullptr;
+        }
         pipe = host_pipe_acquire(dev);
         lap("host pipe");
         own_stream = pipe->compute_stream();
@@ -169,6 +190,36 @@ struct JitBackend final : Backend {
         cap = n;
     }
 
+    void set_params(const double *values, uint32_t n) override {
+        if (n != param_values.size()) throw Error{MARAY_E_INTERNAL, "parameter count"};
+        if (slow) slow->set_params(values, n);          // the interpreter that drains deferred tiles renders the same frame
+        if (memcmp(param_values.data(), values, (size_t)n * sizeof(double)) == 0) return;       // the same bits: nothing to send
+        param_values.assign(values, values + n);
+        params_dirty = true;
+    }
+
+    // New values reach the tables on the launch's own stream: launches enqueued before the set_params call keep theirs.
+    // Three things assumed that a geometry's ROW outputs never change; with new values:
+    //  - launches without a ROW pass (time_rows): the y values and guard bits in the tables are the old values' -- wrong
+    //    pixels, not slow ones.  The launch that carries new values runs its ROW pass (the return value says so).
+    //  - the cached launch order: a permutation of rows from the guard bits of the values it was computed with.  Still a
+    //    permutation, so pixels stay right, but no longer "dearest first".  Dropped, and so is the memory of the geometry:
+    //    the order kernel costs more than ten launches' gain, so it runs again only once a geometry comes a second time
+    //    with the SAME values (a paused animation, a benchmark loop), never per frame of a moving one.
+    //  - deferred tiles: the interpreter behind this context has the values already (set_params) and sends them on the
+    //    same stream, in front of its kernel.
+    bool send_params(hipStream_t st) {
+        if (!params_dirty) return false;
+        double *slot = ring.take();
+        const size_t bytes = param_values.size() * sizeof(double);
+        memcpy(slot, param_values.data(), bytes);
+        for (hipDeviceptr_t p : d_par) HIP_TRY(hipMemcpyHtoDAsync(p, slot, bytes, st));
+        ring.sent(st);
+        params_dirty = false;
+        for (int i = 0; i < 3; i++) order_key[i] = seen_key[i] = 0;
+        return true;
+    }
+
     // Supersampling (maray_jit_pixels_ss): w_out and rb_out are output pixels and rows; the ROW stage covers the k x k times
     // larger sample grid, the PIXEL kernel's grid counts output rows (65,534 per grid).  No launch order, nothing deferred.
     void launch_ss(uint32_t w_out, const RowBlocks &rb_out, unsigned char *d8, hipStream_t st, bool rows_pass) {
@@ -182,6 +233,7 @@ struct JitBackend final : Backend {
             HIP_TRY(hipStreamWaitEvent(st, handover, 0));
         }
         last_stream = st; have_last = true;
+        if (send_params(st)) rows_pass = true;
         unsigned yrows = (guard_rows > 1 && (blk_rows >= rows_total || blk_rows % guard_rows == 0)) ? guard_rows : 1u;
         const uint32_t n_groups = (rows_total + yrows - 1) / yrows;
         if (rows_pass) {
@@ -236,6 +288,7 @@ struct JitBackend final : Backend {
             HIP_TRY(hipStreamWaitEvent(st, handover, 0));
         }
         last_stream = st; have_last = true;
+        if (send_params(st)) rows_pass = true;
         // rows per guard evaluation: a group must not straddle two row blocks (its image rows have to be consecutive)
         unsigned yrows = (guard_rows > 1 && (blk_rows >= rows_total || blk_rows % guard_rows == 0)) ? guard_rows : 1u;
         const uint32_t n_groups = (rows_total + yrows - 1) / yrows;

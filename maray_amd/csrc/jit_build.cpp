@@ -228,6 +228,7 @@ std::string program_name(const maray_program &prog)
     for (uint64_t &x : h) {
         x = fnv1a(salt.data(), salt.size(), x);
         x = fnv1a(counts, sizeof counts, x);
+        if (prog.version == MARAY_TAPE_VERSION_PARAMS) x = fnv1a(&prog.n_params, sizeof prog.n_params, x);      // (the size of the sources' parameter table)
         x = fnv1a(prog.consts, (size_t)prog.n_consts * sizeof(double), x);
         x = fnv1a(prog.row_ops, (size_t)prog.n_row_ops * sizeof(uint64_t), x);
         x = fnv1a(prog.pix_ops, (size_t)prog.n_pix_ops * sizeof(uint64_t), x);

@@ -320,6 +320,13 @@ struct Emitter {
                 return &t;
             default:
                 if (idx == MARAY_SPEC_ACC) return &vals[acc];
+                if (idx >= MARAY_SPEC_PARAM0) {
+                    // a parameter: wave-uniform and NOT a constant -- no literal, no entry of the constant table, no
+                    // MR_ALL / MR_NONE typing, never the k of a fused compare (cst stays false): a scalar load from the
+                    // module's parameter table, whose address every pass makes opaque like the constant table's (mr_par)
+                    t.d = "mr_par[" + std::to_string(idx - MARAY_SPEC_PARAM0) + "]";
+                    return &t;
+                }
                 static const char *const spec_name[] = {"X", "Y", "", "XMAX", "XMIN", "YMAX", "YMIN"};
                 t.d = spec_name[idx];
                 return &t;

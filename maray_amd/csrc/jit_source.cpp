@@ -119,6 +119,20 @@ GuardPlan jit_guard_plan(const maray_program &P)
     return gp;
 }
 
+// The parameter table of a program with parameters (include/maray_tape.h, SPEC PARAM): a global of every module of the
+// program, written by the host alone (JitBackend::send_params finds it by name) and read by scalar loads.  Only sources
+// of programs that have parameters contain it; nothing in a source depends on a parameter's VALUE.
+static std::string jit_param_table(const maray_program &P)
+{
+    return "__device__ __attribute__((aligned(64))) double mr_par_tab[" + std::to_string(P.n_params) + "];      // the parameters' values: set by the host between launches\n";
+}
+// ... behind an address made opaque where the constant table's is: a visible one makes every parameter a loop invariant,
+// hoisted out of the tile and pass loops and spilled ("Constants")
+static const char PARAM_POINTER[] =
+    "    asm volatile(\"\" : \"+s\"(mr_pbase));\n"
+    "    const mr_kptr mr_par = (mr_kptr)mr_pbase;\n"
+    "    (void)mr_par;\n";
+
 // The ROW section split into chunks that different wavefronts evaluate side by side.  One
 // work-item per row is all the parallelism a straight-line ROW kernel has (4096 rows = 64 waves,
 // each walking thousands of dependent f64 ops: ~45 us for chess, an eighth of the frame).  The y
@@ -264,6 +278,7 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
          "// each bounded over rectangles of " + std::to_string(geom.gw) + " pixels x " + std::to_string(geom.gh) + " rows (the height is a launch parameter, and part of the code key through this line:\n"
          "// a cached code object carries its geometry)\n";
     s += "#include \"device_math.h\"\n\n";
+    if (P.n_params) s += jit_param_table(P) + "typedef const __attribute__((address_space(4))) double *mr_kptr;\n";
     // (constants stay literals here: from a table in constant memory like the PIXEL kernel's, the code is a tenth shorter
     // and the kernel 0.8 us slower -- the loads' waits sit in the one chain a job is -- and spills to scratch)
     const unsigned row_block = ROW_BLOCK;
@@ -272,7 +287,7 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
          "                                                                 unsigned y0, unsigned rows, unsigned n_yvals, unsigned w, unsigned n_tx,\n"
          "                                                                 unsigned blk_rows, unsigned blk_stride, unsigned yrows)\n{\n"
          "    const unsigned item = blockIdx.x * blockDim.x + threadIdx.x;         // (the host keeps the items of a launch below 2^32)\n"
-         "    (void)tex; (void)gbits; (void)n_tx;\n"
+         "    (void)tex; (void)gbits; (void)n_tx;\n" + std::string(P.n_params ? "    unsigned long long mr_pbase = (unsigned long long)mr_par_tab;\n" + std::string(PARAM_POINTER) : "") +
          "    // guard jobs first in the grid (they are the long ones: the y-value jobs fill in behind them): job = the switch index\n"
          "    const unsigned mr_job = blockIdx.y < " + std::to_string(n_gjobs) + "u ? " + std::to_string(chunks.size()) + "u + blockIdx.y : blockIdx.y - " + std::to_string(n_gjobs) + "u;\n"
          "    if (mr_job < " + std::to_string(chunks.size()) + "u) {\n"
@@ -438,6 +453,7 @@ struct PixelSetup {
     {
         std::string &s = E.out;
         std::string tab = device_text;
+        if (E.P.n_params) tab += jit_param_table(E.P);
         if (!E.ktab_vals.empty()) {
             tab += "__constant__ __attribute__((aligned(64))) double mr_kc_tab[" + std::to_string(E.ktab_vals.size()) + "] = {";
             for (size_t j = 0; j < E.ktab_vals.size(); j++) { tab += (j % 6 ? " " : "\n    "); tab += lit(E.ktab_vals[j]); tab += ","; }
@@ -445,10 +461,11 @@ struct PixelSetup {
         }
         s.replace(s.find("/*MR_KTAB*/"), 11, tab);
         for (size_t at; (at = s.find("/*MR_KBASE*/")) != std::string::npos;)
-            s.replace(at, 12, E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n");
-        const std::string kc = E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
-                               "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
-                               "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n";
+            s.replace(at, 12, std::string(E.ktab_vals.empty() ? "" : "    unsigned long long mr_kbase = (unsigned long long)mr_kc_tab;\n") +
+                              (E.P.n_params ? "    unsigned long long mr_pbase = (unsigned long long)mr_par_tab;\n" : ""));
+        const std::string kc = std::string(E.ktab_vals.empty() ? "    asm volatile(\"\" ::: \"memory\");\n" :
+                                           "    asm volatile(\"\" : \"+s\"(mr_kbase) :: \"memory\");\n"
+                                           "    const mr_kptr mr_kc = (mr_kptr)mr_kbase;\n") + (E.P.n_params ? PARAM_POINTER : "");
         for (size_t at; (at = s.find("/*MR_KC*/")) != std::string::npos;) s.replace(at, 9, kc);
         return s;
     }

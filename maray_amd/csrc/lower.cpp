@@ -37,7 +37,7 @@ namespace maray {
 
 namespace {
 
-enum : uint8_t { D_CONST = 100, D_X = 101, D_Y = 102, D_XMAX = 103, D_XMIN = 104, D_YMAX = 105, D_YMIN = 106 };   // leaf kinds; ops use MARAY_OP_*  (XMIN..YMAX: the rectangle of pixels a guard bounds)
+enum : uint8_t { D_CONST = 100, D_X = 101, D_Y = 102, D_XMAX = 103, D_XMIN = 104, D_YMAX = 105, D_YMIN = 106, D_PARAM = 107 };   // leaf kinds; ops use MARAY_OP_*  (XMIN..YMAX: the rectangle of pixels a guard bounds; PARAM: aux = its number)
 enum : uint8_t { DEP_X = 1, DEP_Y = 2 };
 
 struct DNode {
@@ -76,6 +76,7 @@ struct Dag {
     std::vector<DNode> n;
     std::vector<int32_t> table;          // node id + 1, 0 = empty; size a power of two, at most half full
     uint32_t folded = 0;
+    std::vector<ParamDecl> params;       // the scene's declared parameters (D_PARAM leaves: aux = index)
     bool commute = true;
     bool fuse = true;
 
@@ -118,6 +119,11 @@ struct Dag {
         return intern(DNode{D_CONST, 0, 0, -1, -1, v});
     }
     int32_t leaf(uint8_t kind) { return intern(DNode{kind, (uint8_t)(kind == D_X ? DEP_X : kind == D_Y ? DEP_Y : 0), 0, -1, -1, 0.0}); }
+
+    // A run-time parameter: a leaf of its own kind, hash-consed by its number.  Not a constant -- nothing may use its value:
+    // every fold, and every rule that asks for a constant, tests op == D_CONST -- and not a coordinate: dep = 0 (uniform),
+    // so that what is computed from parameters alone goes where y-only work goes, the ROW section.
+    int32_t param(uint32_t p) { return intern(DNode{D_PARAM, 0, p, -1, -1, 0.0}); }
 
     int32_t unary(uint8_t op, int32_t a) {
         if (n[a].op == D_CONST) {
@@ -196,9 +202,13 @@ struct SymEval {
     FlatMap64 var_memo;                                 // (ctx, def index) -> dag node
     std::unordered_set<uint64_t> in_progress;
     std::unordered_map<uint64_t, int32_t> id_node;      // Var id -> dag node at its use sites (Cache transparency)
+    std::unordered_map<uint64_t, uint32_t> declared;    // Var id -> parameter number
     int depth = 0;
 
-    SymEval(const Scene &s_, Dag &g_) : s(s_), g(g_) { memo.reserve(s_.nodes.size()); }
+    SymEval(const Scene &s_, Dag &g_) : s(s_), g(g_) {
+        memo.reserve(s_.nodes.size());
+        for (size_t p = 0; p < s_.params.size(); p++) declared.emplace(s_.params[p].id, (uint32_t)p);
+    }
 
     int32_t var(uint64_t id, int32_t ctx) {
         int32_t r = -1;
@@ -216,7 +226,12 @@ struct SymEval {
                 break;
             }
         }
-        if (r < 0) r = g.konst(NAN);                                 // unknown variable (src/cache.rs:40)
+        if (r < 0) {
+            // no definition at this use site: a declared parameter's run-time value, else NaN (src/cache.rs:40).  The
+            // check below stays what it was: an id that is a parameter here and a Let's variable there is two nodes.
+            auto dp = declared.find(id);
+            r = dp != declared.end() ? g.param(dp->second) : g.konst(NAN);
+        }
         auto ins = id_node.emplace(id, r);
         if (!ins.second && ins.first->second != r)
             throw Error{MARAY_E_ALIASED, "variable id " + std::to_string(id) +
@@ -313,6 +328,11 @@ std::vector<Ival> intervals(const Dag &g, const std::vector<Ival> *have = nullpt
         switch (d.op) {
         case D_CONST: r = (d.cval != d.cval) ? Ival{-INFINITY, INFINITY, true} : Ival{d.cval, d.cval, false}; break;
         case D_X: case D_Y: case D_XMAX: case D_XMIN: case D_YMAX: case D_YMIN: r = Ival{0.0, dmax, false}; break;
+        case D_PARAM: {      // its declared range, which is enforced where values are set; (-inf, +inf) admits NaN too
+            const ParamDecl &pd = g.params[d.aux];
+            r = Ival{pd.lo, pd.hi, pd.lo == -INFINITY && pd.hi == INFINITY};
+            break;
+        }
         case MARAY_OP_MOV: r = a; break;
         case MARAY_OP_NEG: r = Ival{-a.hi, -a.lo, a.nan}; break;
         case MARAY_OP_ABS:
@@ -1133,6 +1153,7 @@ struct Lowerer {
             if (d.op == D_XMIN) return MARAY_REF(MARAY_K_SPEC, MARAY_SPEC_XMIN);
             if (d.op == D_YMAX) return MARAY_REF(MARAY_K_SPEC, MARAY_SPEC_YMAX);
             if (d.op == D_YMIN) return MARAY_REF(MARAY_K_SPEC, MARAY_SPEC_YMIN);
+            if (d.op == D_PARAM) return MARAY_REF(MARAY_K_SPEC, MARAY_SPEC_PARAM0 + d.aux);
             if (in_section[c]) {
                 if (acc_holder[j] == c) { sec.acc_operands++; return MARAY_REF(MARAY_K_SPEC, MARAY_SPEC_ACC); }
                 if (slot[c] < 0) throw Error{MARAY_E_INTERNAL, "operand without a slot"};
@@ -1200,6 +1221,7 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
     Dag g;
     g.commute = opts.plain_cse == 0;
     g.fuse = opts.no_fuse == 0;
+    g.params = s.params;
     SymEval ev(s, g);
     int32_t roots[3];
     for (int c = 0; c < 3; c++) roots[c] = ev.eval(s.color[c], -1);   // outer Context::new() is empty (src/render.rs:53)
@@ -1253,6 +1275,7 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
             switch (d.op) {
             case D_CONST: c = d.cval == d.cval && !std::signbit(d.cval); break;
             case D_X: case D_Y: case D_XMAX: case D_XMIN: case D_YMAX: case D_YMIN: c = true; break;
+            case D_PARAM: c = !std::signbit(g.params[d.aux].lo); break;       // (a range from +0.0 excludes -0.0: param_value_ok)
             case MARAY_OP_STEP: case MARAY_OP_STEPSIN: case MARAY_OP_APP: case MARAY_OP_TEXDIM: c = true; break;
             case MARAY_OP_ABS: c = !iv0[d.a].nan; break;                        // |-0| = +0
             case MARAY_OP_SQRT: case MARAY_OP_MOV: c = ca; break;                // sqrt(+0) = +0
@@ -1261,6 +1284,14 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
             }
             clear[i] = isb0[i] || (c && !iv0[i].nan);      // a boolean is +0.0 or 1.0 whatever it is made of (1 + -(b) passes through -1)
             finite[i] = clear[i] && iv0[i].hi < INFINITY;
+        }
+        // MARAY_TRACE_LOWER: shapes that a parameter moves and that got no guard (a rule above did not apply to the
+        // parameter: an infinite range is "may be NaN", a range that straddles zero has no sign)
+        std::vector<uint8_t> reads_param(trace ? N0 : 0, 0);
+        uint32_t lost_to_params = 0, conj_with_params = 0;
+        for (size_t i = 0; i < reads_param.size(); i++) {
+            const DNode &d = g.n[i];
+            reads_param[i] = d.op == D_PARAM || (d.a >= 0 && reads_param[d.a]) || (d.b >= 0 && reads_param[d.b]);
         }
         std::vector<uint32_t> shapes(N0, 1);          // operands of the max tree below a node
         for (size_t i = 0; i < N0; i++) {
@@ -1274,7 +1305,11 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
             if (!conj && !group) continue;
             const int32_t ub = isb0[i] ? rb.bounds((int32_t)i).ub : rb.zub((int32_t)i, clear, finite);
             if (g.n[ub].op < D_CONST) rowub[i] = ub;          // a real y-only op (not folded to a constant)
+            if (trace && conj && reads_param[i]) { conj_with_params++; lost_to_params += rowub[i] < 0; }
         }
+        if (trace && !g.params.empty())
+            fprintf(stderr, "maray lower: conjunctions that read a parameter: %u, of which %u got no bound over a row (a rule did not apply: an infinite range "
+                            "may be NaN, a range across zero has no sign)\n", conj_with_params, lost_to_params);
         // Second pass, over y: a guard that is built from booleans monotone in y as well is bounded over the rows
         // [YMIN, YMAX] the same way, and then holds for a rectangle of pixels -- an evaluator may compute it once for
         // several rows.  A guard that is not keeps reading Y: exact for its row, valid for that row only.
@@ -1304,7 +1339,7 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
             if (trace && getenv("MARAY_TRACE_GUARDS")) {
                 std::function<std::string(int32_t, int)> show = [&](int32_t i, int depth) -> std::string {
                     const DNode &d = g.n[i];
-                    static const char *leaf[] = {"", "X", "Y", "XMAX", "XMIN", "YMAX", "YMIN"};
+                    static const char *leaf[] = {"", "X", "Y", "XMAX", "XMIN", "YMAX", "YMIN", "PARAM"};
                     static const char *opn[] = {"nop", "mov", "neg", "abs", "recip", "sqrt", "step", "sin", "exp", "ln", "add", "mul", "max", "min", "app", "texdim", "out", "stepsin"};
                     if (d.op == D_CONST) { char b[32]; snprintf(b, sizeof b, "%g", d.cval); return b; }
                     if (d.op > D_CONST) return leaf[d.op - D_CONST];
@@ -1499,6 +1534,18 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
     if (t.consts.empty()) t.consts.push_back(0.0);
     t.row_ops = std::move(row.ops);
     t.pix_ops = std::move(pix.ops);
+    // A program some op of which reads a parameter carries the ranges of all the scene declares (one value array serves a
+    // scene); one that reads none is the version-2 program it always was.
+    t.param_ranges.clear();
+    bool reads = false;
+    for (const std::vector<uint64_t> *ops : {&t.row_ops, &t.pix_ops})
+        for (uint64_t ins : *ops) {
+            const uint32_t op = MARAY_INS_OP(ins);
+            if (op == MARAY_OP_NOP || op == MARAY_OP_TEXDIM) continue;
+            auto is_param = [](uint32_t r) { return MARAY_REF_KIND(r) == MARAY_K_SPEC && MARAY_REF_INDEX(r) >= MARAY_SPEC_PARAM0; };
+            reads |= is_param(MARAY_INS_A(ins)) || (op >= MARAY_OP_ADD && op <= MARAY_OP_APP && is_param(MARAY_INS_B(ins)));
+        }
+    if (reads) for (const ParamDecl &pd : s.params) { t.param_ranges.push_back(pd.lo); t.param_ranges.push_back(pd.hi); }
     info.n_consts = (uint32_t)t.consts.size();
     info.n_row_ops = (uint32_t)t.row_ops.size();
     info.n_row_slots = row.n_slots;

@@ -15,10 +15,13 @@ struct Tape {
     std::vector<uint64_t> row_ops;
     std::vector<uint64_t> pix_ops;
     maray_tape_info info;
+    std::vector<double> param_ranges;    // lo, hi per declared parameter; empty: no op reads a parameter (a version-2 program)
 
     maray_program program() const {
         maray_program p;
-        p.version = MARAY_TAPE_VERSION;
+        p.version = param_ranges.empty() ? MARAY_TAPE_VERSION : MARAY_TAPE_VERSION_PARAMS;
+        p.n_params = (uint32_t)(param_ranges.size() / 2);
+        p.param_ranges = param_ranges.empty() ? nullptr : param_ranges.data();
         p.n_consts = (uint32_t)consts.size();
         p.consts = consts.data();
         p.n_row_ops = (uint32_t)row_ops.size();
@@ -38,5 +41,11 @@ void lower_scene(const Scene &scene, const maray_lower_opts &opts, Tape &out);  
 // Validate a program handed in through the tape-level ABI (bounds of every
 // slot / constant / y-value / output reference); throws Error.
 void validate_program(const maray_program &p);
+// A program as the library holds it, from one handed in through the ABI: a version-2 struct ends at n_app and is not read
+// past it (n_params = 0).  Throws Error on a null pointer.
+maray_program load_program(const maray_program *p);
+// Is v a value parameter p of the program may take?  (Inside its declared range, zeros compared by sign as well: a range
+// that starts at +0.0 excludes -0.0, whose sign the lowering's "sign bit clear" statements would not survive.)
+bool param_value_ok(const double *ranges, uint32_t p, double v);
 
 }   // namespace maray

@@ -4,6 +4,7 @@
 // that only gate SKIP ops.  Both back-ends cut the tape by outputs (the cone of a set of OUT ops)
 // to run parts of it side by side or at a different granularity (guards per rectangle of pixels).
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -326,6 +327,29 @@ bool any_guard_reads_y(const maray_program &P)
     const uint32_t n_ynum = numeric_yvals(P);
     for (uint32_t o : d.outs) if (MARAY_INS_AUX(P.row_ops[o]) >= n_ynum && d.reads_y[o]) return true;
     return false;
+}
+
+// ---- parameters as the tail of the constant pool (the interpreter's view) ---------------------------------------------------
+ParamsAsConsts::ParamsAsConsts(const maray_program &P)
+    : consts(P.consts, P.consts + P.n_consts), row_ops(P.row_ops, P.row_ops + P.n_row_ops), pix_ops(P.pix_ops, P.pix_ops + P.n_pix_ops), prog(P)
+{
+    if ((uint64_t)P.n_consts + P.n_params > MARAY_MAX_INDEX + 1u) throw Error{MARAY_E_LIMIT, "constants and parameters together exceed 16384"};
+    consts.resize((size_t)P.n_consts + P.n_params, NAN);
+    auto fix = [&](uint32_t r) {
+        return (MARAY_REF_KIND(r) == MARAY_K_SPEC && MARAY_REF_INDEX(r) >= MARAY_SPEC_PARAM0)
+                   ? MARAY_REF(MARAY_K_CONST, P.n_consts + (MARAY_REF_INDEX(r) - MARAY_SPEC_PARAM0)) : r;
+    };
+    for (std::vector<uint64_t> *ops : {&row_ops, &pix_ops})
+        for (uint64_t &ins : *ops) {
+            const uint32_t op = MARAY_INS_OP(ins);
+            if (op == MARAY_OP_NOP || op == MARAY_OP_TEXDIM) continue;
+            const bool binary = op >= MARAY_OP_ADD && op <= MARAY_OP_APP;
+            ins = MARAY_INS(op, MARAY_INS_AUX(ins), MARAY_INS_DST(ins), fix(MARAY_INS_A(ins)), binary ? fix(MARAY_INS_B(ins)) : MARAY_INS_B(ins));
+        }
+    prog.version = MARAY_TAPE_VERSION;
+    prog.n_params = 0; prog.param_ranges = nullptr;
+    prog.n_consts = (uint32_t)consts.size(); prog.consts = consts.data();
+    prog.row_ops = row_ops.data(); prog.pix_ops = pix_ops.data();
 }
 
 }   // namespace maray

@@ -340,7 +340,7 @@ Scene scene_fixed(const Scene &s)
 {
     if (s.fixed) return s;
     Scene out;
-    out.w = s.w; out.h = s.h; out.legacy = s.legacy;
+    out.w = s.w; out.h = s.h; out.legacy = s.legacy; out.params = s.params;       // (free variables keep their ids, :31-36)
     Fixer f(s, out);                      // one VarFixer for all three channels (:76)
     Renames empty;
     for (int c = 0; c < 3; c++) out.color[c] = f.fix(s.color[c], empty);

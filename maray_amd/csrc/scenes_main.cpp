@@ -63,9 +63,11 @@ static Color textured(uint64_t w)
 
 // examples/chess.rs:5-50: an 8x8 grid of quads in perspective with a chess texture.  authored: with the example's
 // `.simplify(mem).compress(mem)` (:43) -- the file a user of the reference would save at this size; else the bare tree.
-static Color chess_board(uint64_t size, bool authored = false)
+// slide: the board under `translate` by (var("t"), 0) pixels -- a scene with a parameter: `maray -p t=...` / `--animate t=...`
+// give the free variable its value at render time (include/maray_hip.h, "scene parameters")
+static Color chess_board(uint64_t size, bool authored = false, bool slide = false)
 {
-    Point2 p = {div(x(), nat(size)), div(y(), nat(size))};
+    Point2 p = {div(slide ? sub(x(), var("t")) : x(), nat(size)), div(y(), nat(size))};
     Expr texture = set_unit_square(chess(8));
     Grid2 grid{8, 8};
     std::array<Point2, 4> quad = {Point2{recip(nat(5)), recip(nat(2))}, Point2{sub(nat(1), recip(nat(5))), recip(nat(2))},
@@ -145,6 +147,7 @@ int main(int argc, char **argv)
         // and compress are for -- a scene regenerated at a new size, not a stored one rescaled)
         {"chess_authored_1024", 1024, 1024, [] { return chess_board(1024, true); }},
         {"chess_authored_4096", 4096, 4096, [] { return chess_board(4096, true); }},
+        {"chess_slide_1024", 1024, 1024, [] { return chess_board(1024, false, true); }},
     };
     int written = 0;
     for (const Item &it : items) {
