@@ -67,6 +67,149 @@ def substituted(color, names, values):
     return out
 
 
+def substituted_exact(color, ids, values):
+    """The same for any double (edge_values.const builds every one exactly) and for numeric ids; NaN leaves the variable free."""
+    from edge_values import const
+    out = list(color)
+    for i, v in zip(ids, values):
+        out = [subst_free(c, i, None if v != v else const(v)) for c in out]
+    return out
+
+
+# ---- ranges and values of the parameter fuzz (tests/fuzz_scenes.py: param_scene and the parameterised soups) ---------------
+TINY, HUGE = 5e-324, 1e300
+RANGES = [(-64.0, 64.0),                                                  # symmetric, finite
+          (0.0, 1.0), (-0.0, 1.0), (-8.0, -0.0), (0.0, 0.0),              # the four zero ends
+          (3.5, 3.5),                                                     # degenerate, not zero
+          (0.25, 100.0), (-300.0, -0.5),                                  # strictly positive, strictly negative
+          (TINY, 1e-300), (-HUGE, HUGE),
+          (0.0, INF), (-INF, 0.0), (-INF, -1.0),                          # half-infinite
+          (-INF, INF)]
+
+
+def value_ok(v, lo, hi):
+    """param_value_ok of the library (api.cpp), restated: inside the range, the sign of a zero end counting."""
+    if lo == -INF and hi == INF:
+        return True
+    if not (lo <= v <= hi):
+        return False
+    neg0 = v == 0 and math.copysign(1.0, v) < 0
+    if v == 0 and lo == 0 and neg0 and math.copysign(1.0, lo) > 0:
+        return False
+    if v == 0 and hi == 0 and not neg0 and math.copysign(1.0, hi) < 0:
+        return False
+    return True
+
+
+def candidate_values(rng, lo, hi):
+    """The values a fuzz vector draws from for one range: both ends, the doubles next to them inward, both zeros where the
+    range admits them, interior doubles; the infinite end and 1e300 of a half-infinite range; NaN, +-inf, 2^40 and +-0 of
+    the full one."""
+    if lo == -INF and hi == INF:
+        return [math.nan, INF, -INF, 2.0 ** 40, 0.0, -0.0, rng.uniform(-100.0, 100.0), rng.choice([-1, 1]) * 10.0 ** rng.uniform(-8, 8)]
+    out = [lo, hi]
+    if lo != hi:
+        out += [math.nextafter(lo, hi), math.nextafter(hi, lo)]
+    for end, sign in ((lo, 1.0), (hi, -1.0)):
+        if math.isinf(end):
+            out.append(sign * -HUGE)
+    flo, fhi = max(lo, -HUGE), min(hi, HUGE)
+    for _ in range(3):
+        if math.isinf(lo) or math.isinf(hi):                 # a few decades away from the finite end
+            v = (hi - 10.0 ** rng.uniform(-3, 6)) if math.isinf(lo) else (lo + 10.0 ** rng.uniform(-3, 6))
+        else:
+            v = flo + (fhi - flo) * rng.random() if fhi - flo < INF else rng.uniform(-1.0, 1.0) * fhi
+        out.append(min(max(v, flo), fhi))
+    out += [0.0, -0.0]
+    out = [v for v in out if value_ok(v, lo, hi)]
+    assert out, (lo, hi)
+    return out
+
+
+def admits_negative_zero(lo, hi):
+    return value_ok(-0.0, lo, hi)
+
+
+def value_vectors(rng, decl, n):
+    """n vectors of values for decl = [(id, lo, hi), ...]; vector 1 has -0.0 in every parameter whose range admits it, vector
+    2 NaN in every parameter that may be anything."""
+    out = []
+    for k in range(n):
+        vec = []
+        for _, lo, hi in decl:
+            c = candidate_values(rng, lo, hi)
+            v = rng.choice(c)
+            if admits_negative_zero(lo, hi) and (k == 1 or rng.random() < 0.15):
+                v = -0.0
+            if k == 2 and lo == -INF and hi == INF:
+                v = math.nan
+            vec.append(v)
+        out.append(tuple(vec))
+    return out
+
+
+def declared_ids(data, decl):
+    """maray_amd.Scene of the encoded scene with decl = [(id, lo, hi), ...] declared in that order."""
+    import maray_amd as M
+    s = M.Scene(data)
+    for k, (i, lo, hi) in enumerate(decl):
+        assert s.declare_param(i, lo, hi) == k
+    return s
+
+
+def fuzz_check(color, decl, vectors, size, textures=None, yrows=(4, 8, 32), threads=None):
+    """One parameterised scene against the oracle (tests/test_fuzz_params.py, tools/gpu_fuzz_params.py --cpu).  Lowered ONCE;
+    for every vector the program (as_v2) under the numpy evaluator must equal the oracle's f64 planes and RGB8 of the
+    substituted scene: plain, with skips taken per wavefront, per 64-pixel span, and per rectangle of `yrows` rows where no
+    guard reads y; the guard-free lowering too; and lowering again with the values set gives the same arrays byte for byte.
+    Returns None for a scene the library refuses as aliased / self-referent, else a dict: version, guards, reading_y, differ
+    (two frames differ), failures (a list of (vector, what))."""
+    import os
+    import maray_amd as M
+    import tape_eval as TE
+    from oracle_ffi import Scene as OScene
+    w, h = size
+    data = encode(size, color)
+    scene = declared_ids(data, decl)
+    try:
+        tape = scene.lower()
+        bare = scene.lower(skips=False)
+    except M.MarayError as e:
+        if e.code in (-4, -5):
+            return None
+        raise
+    ids = [i for i, _, _ in decl]
+    n_guards, reading_y = TE.guards_reading_y(tape)
+    before = [a.tobytes() for a in tape.arrays()]
+    fails, frames = [], []
+    threads = threads or min(16, os.cpu_count() or 1)
+    for values in vectors:
+        want8, want64 = OScene(encode(size, substituted_exact(color, ids, values))).render_rows(w, h, 0, h, textures, threads=threads)
+        frames.append(want64)
+        v2 = as_v2(tape, values) if tape.param_count else tape
+
+        def check(what, got):
+            if not same_f64(got, want64):
+                fails.append((values, what))
+            elif what == 'plain' and not np.array_equal(TE.cast_u8(got), want8):
+                fails.append((values, 'rgb8'))
+        check('plain', TE.render_rows(v2, w, 0, h, textures))
+        if tape.info['skip_ops']:
+            check('skips per wavefront', TE.render_rows_waves(v2, w, 0, h, textures))
+            check('skips per span', TE.render_rows_waves(v2, w, 0, h, textures, tile=64))
+            if n_guards and not reading_y:
+                for yr in yrows:
+                    check('skips per rectangle of %d rows' % yr, TE.render_rows_waves(v2, w, 0, h, textures, tile=64, yrows=yr))
+        check('guard-free lowering', TE.render_rows(as_v2(bare, values) if bare.param_count else bare, w, 0, h, textures))
+        for k, v in enumerate(values):
+            scene.set_param(k, v)
+        if [a.tobytes() for a in scene.lower().arrays()] != before:
+            fails.append((values, 'lowered again'))
+    differ = any(not same_f64(frames[0], f) for f in frames[1:])
+    return dict(version=tape.program.version, param_count=tape.param_count, guards=n_guards, reading_y=reading_y, differ=differ,
+                failures=fails, info=tape.info)
+
+
 # ---- a parameterised program as a version-2 one ----------------------------------------------------------------------
 class TapeV2:
     """Stands in for maray_amd.Tape where tests/tape_eval.py wants one: every PARAM operand rewritten to a CONST operand on

@@ -68,14 +68,29 @@ def _cast_u32(v):
     return np.minimum(v, 4294967295.0).astype(np.uint64)
 
 
-def run_section(ops, consts, n_slots, X, Y, yvals, textures, n_out, honor_skips=False, w=None, span=None, yspan=None):
+def run_section(ops, consts, n_slots, X, Y, yvals, textures, n_out, honor_skips=False, w=None, span=None, yspan=None, waves=False):
     """Evaluate one section for a vector of items.  X, Y: float64 arrays (same
     shape); yvals: array [..., n_yvals] broadcastable per item or None.
-    honor_skips: take SKIPZ / SKIPNZ when the whole vector agrees (call per 64-item "wavefront")."""
+    honor_skips: take SKIPZ / SKIPNZ when the whole vector agrees (call per 64-item "wavefront").
+    waves (with honor_skips): X, Y hold one wavefront per row, (n, 64), and each takes its own skips: a wavefront that
+    skips gets the skip's value and sits out the ops it jumps over (its `resume` is behind them), the others go on."""
     shape = np.shape(Y)
     slots = [None] * max(n_slots, 1)
     outs = [None] * n_out
     acc = None
+    resume = np.zeros(shape[0], np.int64) if waves else None     # the op a wavefront takes part in again
+    on = None                                                    # (n, 1) mask of the wavefronts that take part in this op; None: all
+
+    def keep(new, old):          # `new` where a wavefront takes part, what it had elsewhere
+        return new if on is None else np.where(on, new, 0.0 if old is None else old)
+
+    def lanes(f, a):             # sin / exp / ln go through Python per item: only where it counts
+        if on is None:
+            return f(a)
+        r = np.zeros(shape)
+        m = np.broadcast_to(on, shape)
+        r[m] = f(a[m])
+        return r
 
     def fetch(ref):
         kind, idx = ref >> 14, ref & 0x3FFF
@@ -95,27 +110,39 @@ def run_section(ops, consts, n_slots, X, Y, yvals, textures, n_out, honor_skips=
             pc += 1
             op, aux, dst, ra, rb = decode(ops[pc])
             if op == OP['NOP']: continue
+            if waves:
+                active = resume <= pc
+                if not active.any():
+                    pc = int(resume.min()) - 1
+                    continue
+                on = None if active.all() else active[:, None]
             if op in (OP['SKIPZ'], OP['SKIPNZ']):
                 if not honor_skips: continue                                   # an evaluator may ignore the skips
                 gv = fetch(ra)
                 want = 0.0 if op == OP['SKIPZ'] else 1.0
-                if np.all(gv == want):
+                if waves:
+                    take = np.all(gv == want, axis=-1) & active
+                    if take.any():
+                        acc = np.where(take[:, None], want, np.zeros(shape) if acc is None else acc)
+                        if dst != DST_NONE: slots[dst] = np.where(take[:, None], want, np.zeros(shape) if slots[dst] is None else slots[dst])
+                        resume[take] = pc + aux + 1
+                elif np.all(gv == want):
                     acc = np.full(shape, want)
                     if dst != DST_NONE: slots[dst] = acc
                     pc += aux
                 continue
             if op == OP['OUT']:
-                outs[aux] = fetch(ra); continue
+                outs[aux] = keep(fetch(ra), outs[aux]); continue
             if op == OP['MOV']: r = fetch(ra)
             elif op == OP['NEG']: r = -fetch(ra)
             elif op == OP['ABS']: r = np.abs(fetch(ra))
             elif op == OP['RECIP']: r = 1.0 / fetch(ra)
             elif op == OP['SQRT']: r = np.sqrt(fetch(ra))
             elif op == OP['STEP']: r = np.where(fetch(ra) >= 0.0, 1.0, 0.0)
-            elif op == OP['SIN']: r = _sin(fetch(ra))
-            elif op == OP['STEPSIN']: r = np.where(_sin(fetch(ra)) >= 0.0, 1.0, 0.0)
-            elif op == OP['EXP']: r = _vexp(fetch(ra))
-            elif op == OP['LN']: r = _vlog(fetch(ra))
+            elif op == OP['SIN']: r = lanes(_sin, fetch(ra))
+            elif op == OP['STEPSIN']: r = np.where(lanes(_sin, fetch(ra)) >= 0.0, 1.0, 0.0)
+            elif op == OP['EXP']: r = lanes(_vexp, fetch(ra))
+            elif op == OP['LN']: r = lanes(_vlog, fetch(ra))
             elif op == OP['ADD']: r = fetch(ra) + fetch(rb)
             elif op == OP['MUL']: r = fetch(ra) * fetch(rb)
             elif op == OP['MAX']: r = _max(fetch(ra), fetch(rb))
@@ -126,16 +153,16 @@ def run_section(ops, consts, n_slots, X, Y, yvals, textures, n_out, honor_skips=
             elif op == OP['APP']:
                 t = textures[aux // 5]
                 a, b = fetch(ra), fetch(rb)
-                h, w = t.shape[0], t.shape[1]
+                th, tw = t.shape[0], t.shape[1]                               # (not `w`: XMAX of a whole row reads it)
                 xi, yi = _cast_u32(a), _cast_u32(b)
-                inb = ~((a < 0) | (b < 0)) & (xi < w) & (yi < h)
+                inb = ~((a < 0) | (b < 0)) & (xi < tw) & (yi < th)
                 r = np.zeros(shape)
                 r[inb] = t[yi[inb].astype(np.int64), xi[inb].astype(np.int64), aux % 5].astype(np.float64)
             else:
                 raise ValueError('bad opcode %d' % op)
-            acc = r
+            acc = keep(r, acc)
             if dst != DST_NONE:
-                slots[dst] = r
+                slots[dst] = keep(r, slots[dst])
     return outs
 
 
@@ -166,15 +193,18 @@ def render_rows_waves(tape, w, y0, y1, textures=None, tile=None, yrows=None):
                                    yspan=ysp)
                 yv_all[r0:r0 + len(ys)] = np.stack(outs, axis=-1)
         yv_span.append(yv_all)
-    for r in range(rows):
-        for x0 in range(0, w, 64):
-            yv_all = yv_span[x0 // tile if tile else 0]
-            X = np.arange(x0, x0 + 64, dtype=np.float64)        # lanes beyond w compute too, like on the device
-            Y = np.full(64, float(y0 + r))
-            yv = np.broadcast_to(yv_all[r][None, :], (64, info['n_yvals'])) if yv_all is not None else None
-            o = run_section(pix_ops, consts, info['n_pix_slots'], X, Y, yv, textures, 3, True)
-            n = min(64, w - x0)
-            out[r, x0:x0 + n] = np.stack(o, axis=-1)[:n]
+    # every wavefront of the image in one call, each taking its own skips (run_section, waves): (rows x wavefronts, 64)
+    x0s = np.arange(0, w, 64)
+    nw = len(x0s)
+    X = np.broadcast_to((x0s[:, None] + np.arange(64)[None, :]).astype(np.float64)[None], (rows, nw, 64)).reshape(-1, 64)   # lanes beyond w compute too, like on the device
+    Y = np.broadcast_to(np.arange(y0, y1, dtype=np.float64)[:, None, None], (rows, nw, 64)).reshape(-1, 64)
+    yv = None
+    if info['n_yvals']:
+        per_wave = np.stack([yv_span[int(x0) // tile if tile else 0] for x0 in x0s], axis=1)       # (rows, wavefronts, n_yvals)
+        yv = np.broadcast_to(per_wave.reshape(rows * nw, 1, info['n_yvals']), (rows * nw, 64, info['n_yvals']))
+    o = run_section(pix_ops, consts, info['n_pix_slots'], X, Y, yv, textures, 3, True, waves=True)
+    full = np.stack([np.broadcast_to(c, (rows * nw, 64)) for c in o], axis=-1).reshape(rows, nw * 64, 3)
+    out[:] = full[:, :w]
     return out
 
 
