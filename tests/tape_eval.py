@@ -166,17 +166,18 @@ def run_section(ops, consts, n_slots, X, Y, yvals, textures, n_out, honor_skips=
     return outs
 
 
-def render_rows_waves(tape, w, y0, y1, textures=None, tile=None, yrows=None):
+def render_rows_waves(tape, w, y0, y1, textures=None, tile=None, yrows=None, stale_guard_rows=None):
     """Like render_rows, but wavefront by wavefront (64 consecutive x of one row; the ROW section in
     groups of 64 rows) with SKIPZ / SKIPNZ honoured the way the device kernels do.  tile: evaluate
     the ROW section once per `tile` pixels of a row with XMIN / XMAX = that span (what the
     specialised kernels do for the guard values) instead of once per row.  yrows: additionally
     with YMIN / YMAX = the ends of the group of `yrows` rows a row belongs to (legal only for a
-    tape none of whose guards reads Y; the caller checks)."""
+    tape none of whose guards reads Y; the caller checks).  stale_guard_rows: see render_with_stale_guards."""
     consts, row_ops, pix_ops = tape.arrays()
     info = tape.info
     rows = y1 - y0
     out = np.zeros((rows, w, 3))
+    stale = sorted(guard_yvals(tape)) if stale_guard_rows else []
     spans = [None] if not tile else [(x0, min(w, x0 + tile) - 1) for x0 in range(0, w, tile)]
     yv_span = []
     for span in spans:
@@ -192,6 +193,9 @@ def render_rows_waves(tape, w, y0, y1, textures=None, tile=None, yrows=None):
                 outs = run_section(row_ops, consts, info['n_row_slots'], None, ys, None, textures, info['n_yvals'], True, w=w, span=span,
                                    yspan=ysp)
                 yv_all[r0:r0 + len(ys)] = np.stack(outs, axis=-1)
+            if stale:
+                first = (np.arange(rows) // stale_guard_rows) * stale_guard_rows
+                yv_all[:, stale] = yv_all[first][:, stale]
         yv_span.append(yv_all)
     # every wavefront of the image in one call, each taking its own skips (run_section, waves): (rows x wavefronts, 64)
     x0s = np.arange(0, w, 64)
@@ -206,6 +210,14 @@ def render_rows_waves(tape, w, y0, y1, textures=None, tile=None, yrows=None):
     full = np.stack([np.broadcast_to(c, (rows * nw, 64)) for c in o], axis=-1).reshape(rows, nw * 64, 3)
     out[:] = full[:, :w]
     return out
+
+
+def render_with_stale_guards(tape, w, y0, y1, yrows, tile, textures=None):
+    """What a kernel computes that wrongly takes a tape whose guards read Y for one with rectangle guards: operand y values
+    per row, every guard's value from the FIRST row of the group of `yrows` rows its row belongs to (groups counted from
+    y0, spans of `tile` pixels).  yrows = 1 is render_rows_waves(tile=tile).  The tests use it as a condition on their
+    scenes: one whose raster does not change under yrows = 8 or 32 could not show such a kernel."""
+    return render_rows_waves(tape, w, y0, y1, textures, tile=tile, stale_guard_rows=yrows)
 
 
 def render_rows(tape, w, y0, y1, textures=None):
@@ -231,10 +243,8 @@ def cast_u8(v):
     return np.minimum(v, 255.0).astype(np.uint8)
 
 
-def guards_reading_y(tape):
-    """How many guards (y values that only gate SKIP ops of the PIXEL section) have SPEC Y in their cone: those are
-    exact for one row and must be evaluated per row; a tape with none may have its guards evaluated for groups of rows
-    (YMIN / YMAX).  Returns (n_guards, n_reading_y)."""
+def guard_yvals(tape):
+    """The y values that only gate SKIP ops of the PIXEL section (no op reads them as an operand): the guards."""
     consts, row_ops, pix_ops = tape.arrays()
     used_as_operand, used_as_guard = set(), set()
     for ins in pix_ops:
@@ -245,7 +255,15 @@ def guards_reading_y(tape):
             (used_as_guard if op in (OP['SKIPZ'], OP['SKIPNZ']) else used_as_operand).add(ra & 0x3FFF)
         if OP['ADD'] <= op <= OP['APP'] and rb >> 14 == K_YVAL:
             used_as_operand.add(rb & 0x3FFF)
-    guards = used_as_guard - used_as_operand
+    return used_as_guard - used_as_operand
+
+
+def guards_reading_y(tape):
+    """How many guards (guard_yvals) have SPEC Y in their cone: those are
+    exact for one row and must be evaluated per row; a tape with none may have its guards evaluated for groups of rows
+    (YMIN / YMAX).  Returns (n_guards, n_reading_y)."""
+    consts, row_ops, pix_ops = tape.arrays()
+    guards = guard_yvals(tape)
     reads_y, slot_writer, acc = {}, {}, None
     n_reading = 0
 

@@ -53,8 +53,9 @@ def _launch_order(n):
     return [0, 1, 1] + list(range(2, n)) + [0]
 
 
-def run_cases(cases, min_cases):
-    """cases: dicts(name, color, decl, vectors, size, textures, narrow).  Lowered once each; per back-end one context, the
+def run_cases(cases, min_cases, lower_kw=None, on_tape=None):
+    """cases: dicts(name, color, decl, vectors, size, textures, narrow).  Lowered once each (lower_kw: keywords of
+    Scene.lower, the defaults if None; on_tape(case, scene, tape): a check of what was lowered); per back-end one context, the
     vectors launched in _launch_order; narrow: every launch once more with the f64 planes off (the four-pixels-per-lane path
     where the program is small enough)."""
     from marayb import encode
@@ -62,7 +63,9 @@ def run_cases(cases, min_cases):
     for c in cases:
         scene = PR.declared_ids(encode(c['size'], c['color']), c['decl'])
         try:
-            live.append((c, scene.lower()))
+            live.append((c, scene.lower(**(lower_kw or {}))))
+            if on_tape:
+                on_tape(c, scene, live[-1][1])
         except M.MarayError as e:
             if e.code not in (-4, -5):          # aliased ids / self reference: the reference itself is ill-defined there
                 raise
