@@ -112,6 +112,15 @@ int maray_scene_declare_param(maray_scene *s, uint64_t var_id, double lo, double
 int maray_scene_param_count(const maray_scene *s, uint32_t *n);
 int maray_scene_param_info(const maray_scene *s, uint32_t index, uint64_t *var_id, double *lo, double *hi, double *value);   /* any may be NULL */
 int maray_scene_set_param(maray_scene *s, uint32_t index, double value);      /* what gen / gen_to_image render with */
+/* Shutter, the scene layer (host only; see "shutter" below): every declared parameter has a span s >= 0, finite, 0 until
+ * set (else MARAY_E_ARG).  maray_scene_shutter_values writes the n x P matrix (frame-major; P = the declared count; n in
+ * {1, 2, 4, 8, 16, 32, 64}, else MARAY_E_ARG) of the n frames' values around the scene's current values v: frame i of a
+ * parameter with s > 0 is v + s * c_i, c_i = (2i + 1 - n) / (2n) -- exact in f64, then one multiply and one add, never
+ * fused; the samples are centred on the plain render's value like spatial samples on its point.  A parameter with s == 0
+ * has v itself in every frame, bit for bit (-0.0 and NaN included).  Spans, like values, are not part of a program's name. */
+int maray_scene_set_param_span(maray_scene *s, uint32_t index, double span);
+int maray_scene_param_span(const maray_scene *s, uint32_t index, double *span);
+int maray_scene_shutter_values(const maray_scene *s, uint32_t n, double *out /* n * P doubles */);
 
 /* ---- lowering: Expr -> tape ---------------------------------------------------
  * Replaces what the reference does per pixel in `Expr::eval2` + `Cache`
@@ -236,6 +245,37 @@ int maray_hip_render_rows(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uin
 typedef void (*maray_tile_fn)(void *user, uint32_t y0, uint32_t y1);
 int maray_hip_render_tiles(maray_ctx *c, uint32_t w, uint32_t h, const uint32_t *tiles_y0y1, uint32_t n_tiles,
                            uint8_t *rgb8_image, maray_tile_fn fn, void *user);
+/* ---- shutter (motion blur: a temporal box filter averaged on the device) ------------------------------------------
+ * A shutter render of n frames, n in {1, 2, 4, 8, 16, 32, 64} (else MARAY_E_ARG), takes `values`: an n x P matrix of
+ * parameter values, frame-major, P = the program's parameter count (maray_hip_ctx_param_count).
+ *   - frame i is exactly what the context renders in RGB8 after maray_hip_ctx_set_params(row i); on a samples = k context
+ *     that is the box-filtered frame;
+ *   - every output byte is (S + n/2) >> log2(n), S = the integer sum of that byte over the n frames (S <= 255 * 64: 16 bits
+ *     hold it).  An integer mean: the same in any order;
+ *   - RGB8 only: the shutter entry points take no f64 planes;
+ *   - every value of every frame is checked against its declared range by maray_hip_ctx_set_params' rule before anything
+ *     is enqueued: one bad value is MARAY_E_ARG, nothing is launched, nothing is written, the context's values stay;
+ *   - the values maray_hip_ctx_set_params set are unchanged after the call (a plain render after a shutter render shows
+ *     what it showed before), and a shutter call neither needs them nor counts as setting them: it is allowed on a context
+ *     whose values were never set, and a plain render on that context is still refused;
+ *   - n = 1 is the plain render with row 0; a program without parameters (P = 0) takes values = NULL, renders once and
+ *     returns the plain picture for any n;
+ *   - the device-pointer form enqueues everything on the caller's stream -- per frame the parameter copy and the ordinary
+ *     launches, per group of 8 frames one pass of maray_shutter_reduce -- and returns without a device synchronise (past
+ *     eight frames it may wait for its own earlier parameter copies); the host forms reduce each tile on the device and
+ *     copy ONE raster to the host, not n;
+ *   - scratch (frames and, above 8 frames, 16-bit partial sums) belongs to the context like its y-value and guard tables:
+ *     ordered by the stream, grown to the largest call -- min(n, 8) F + (n > 8 ? 2 F : 0) bytes, F = the rows' RGB8 bytes
+ *     + 16 rounded up to 256 -- and freed with the context.
+ * check_rows / samples limits as for the plain entry points.  d_rgb8 may have any alignment. */
+int maray_hip_render_rows_shutter(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint32_t y1, const double *values, uint32_t n,
+                                  uint8_t *rgb8);
+int maray_hip_render_rows_shutter_device(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint32_t y1, const double *values, uint32_t n,
+                                         void *d_rgb8, void *stream);
+int maray_hip_render_tiles_shutter(maray_ctx *c, uint32_t w, uint32_t h, const uint32_t *tiles_y0y1, uint32_t n_tiles,
+                                   const double *values, uint32_t n, uint8_t *rgb8_image, maray_tile_fn fn, void *user);
+/* The reduce on its own (measurements): average ms of the passes that reduce n >= 2 frames of `bytes` bytes in HBM. */
+int maray_hip_time_shutter_reduce(int device, size_t bytes, uint32_t n, int reps, float *ms_avg);
 /* Pinned (page-locked, DMA-able from every device) host memory for output rasters: what backs the `RgbImage` a
  * caller hands to gen_to_image (src/lib.rs:1210) when it wants the PCIe rate.  maray_host_register pins memory the
  * caller already owns (e.g. a Rust Vec<u8>) for the time between the two calls. */
@@ -307,7 +347,10 @@ typedef struct maray_gen_opts {
     uint32_t tile_rows;      /* rows per launch (0 = default) */
     uint32_t samples;        /* k x k samples per pixel (0 = 1): the scene is supersampled privately and rendered by
                                 contexts with samples = k; programs are kept per k */
-    uint32_t reserved[4];
+    uint32_t shutter;        /* n frames averaged over the scene's parameter spans (maray_scene_shutter_values; n in {0, 1, 2, 4,
+                                ..., 64}).  0, 1 or no span above 0: the plain render, exactly.  The program and its contexts are
+                                the plain render's: spans and n are not part of their name */
+    uint32_t reserved[3];
 } maray_gen_opts;
 
 /* gen_to_image: fills the caller's w*h*3 RGB8 buffer. */

@@ -51,7 +51,7 @@ class CtxOpts(C.Structure):
 
 class GenOpts(C.Structure):
     _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32), ('samples', C.c_uint32),
-                ('reserved', C.c_uint32 * 4)]
+                ('shutter', C.c_uint32), ('reserved', C.c_uint32 * 3)]
 
 
 class Report(C.Structure):
@@ -102,6 +102,13 @@ def lib():
         'maray_scene_param_count': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_scene_param_info': (C.c_int, [vp, u32, u64p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         'maray_scene_set_param': (C.c_int, [vp, u32, C.c_double]),
+        'maray_scene_set_param_span': (C.c_int, [vp, u32, C.c_double]),
+        'maray_scene_param_span': (C.c_int, [vp, u32, C.POINTER(C.c_double)]),
+        'maray_scene_shutter_values': (C.c_int, [vp, u32, vp]),
+        'maray_hip_render_rows_shutter': (C.c_int, [vp, u32, u32, u32, u32, vp, u32, vp]),
+        'maray_hip_render_rows_shutter_device': (C.c_int, [vp, u32, u32, u32, u32, vp, u32, vp, vp]),
+        'maray_hip_render_tiles_shutter': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, u32, vp, TILE_FN, vp]),
+        'maray_hip_time_shutter_reduce': (C.c_int, [C.c_int, C.c_size_t, u32, C.c_int, C.POINTER(C.c_float)]),
         'maray_tape_param_count': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_tape_param_range': (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         'maray_hip_ctx_set_params': (C.c_int, [vp, C.POINTER(C.c_double), u32]),
@@ -296,6 +303,24 @@ class Scene:
         k = self.param_index(index_or_name) if isinstance(index_or_name, str) else index_or_name
         _check(lib().maray_scene_set_param(self._h, k, value))
 
+    # ---- shutter (include/maray_hip.h, "shutter") ----
+    def set_param_span(self, name_or_index, span):
+        """The width of the interval of values, centred on the parameter's value, that the frames of a shutter render cover
+        (finite, >= 0; 0: every frame has the value itself)."""
+        k = self.param_index(name_or_index) if isinstance(name_or_index, str) else name_or_index
+        _check(lib().maray_scene_set_param_span(self._h, k, span))
+
+    def param_span(self, index):
+        v = C.c_double()
+        _check(lib().maray_scene_param_span(self._h, index, C.byref(v)))
+        return v.value
+
+    def shutter_values(self, n):
+        """The (n, P) float64 matrix of the n frames' parameter values around the scene's current ones."""
+        out = np.zeros((n, self.param_count), np.float64)
+        _check(lib().maray_scene_shutter_values(self._h, n, out.ctypes.data if out.size else None))
+        return out
+
     def lower(self, hoist_rows=True, plain_cse=False, fuse=True, skips=True, row_guards=True, private_regions=True, rebalance=True,
               y_spans=True):
         return Tape(self, hoist_rows, plain_cse, fuse, skips, row_guards, private_regions, rebalance, y_spans)
@@ -445,6 +470,38 @@ class Context:
         cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
         _check(lib().maray_hip_render_tiles(self._h, w, h, flat, len(tiles), image.ctypes.data, cb, None))
 
+    def _frames(self, frames):
+        """(n, pointer, keep-alive) of a shutter call's frames: an (n, P) matrix of values, or an int n for a program without
+        parameters (values = NULL)."""
+        if isinstance(frames, (int, np.integer)):
+            return int(frames), None, None
+        a = np.ascontiguousarray(frames, np.float64)
+        p = self.param_count
+        if a.ndim != 2 or a.shape[1] != p:
+            raise MarayError(-1, 'shutter frames must be an (n, %d) matrix: one column per parameter of the program' % p)
+        return a.shape[0], (a.ctypes.data if a.size else None), a
+
+    def render_rows_shutter(self, w, h, y0, y1, frames, out=None):
+        """Rows [y0, y1) as the integer mean of the frames that the rows of `frames` render (maray_hip_render_rows_shutter);
+        into `out`, a (y1-y0, w, 3) uint8 array, when given."""
+        n, vp_, keep = self._frames(frames)
+        rgb8 = np.zeros((y1 - y0, w, 3), np.uint8) if out is None else out
+        assert rgb8.dtype == np.uint8 and rgb8.flags['C_CONTIGUOUS'] and rgb8.size == (y1 - y0) * w * 3
+        _check(lib().maray_hip_render_rows_shutter(self._h, w, h, y0, y1, vp_, n, rgb8.ctypes.data))
+        return rgb8
+
+    def render_rows_shutter_device(self, w, h, y0, y1, frames, d_rgb8, stream=0):
+        n, vp_, keep = self._frames(frames)
+        _check(lib().maray_hip_render_rows_shutter_device(self._h, w, h, y0, y1, vp_, n, d_rgb8 or None, stream or None))
+
+    def render_tiles_shutter(self, w, h, tiles, frames, image, on_tile=None):
+        """render_tiles with every tile reduced from its frames on the device: one raster crosses to the host, not n."""
+        assert image.dtype == np.uint8 and image.flags['C_CONTIGUOUS'] and image.size == h * w * 3
+        n, vp_, keep = self._frames(frames)
+        flat = (C.c_uint32 * (2 * len(tiles)))(*[v for t in tiles for v in t])
+        cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
+        _check(lib().maray_hip_render_tiles_shutter(self._h, w, h, flat, len(tiles), vp_, n, image.ctypes.data, cb, None))
+
     def render_rows_device(self, w, h, y0, y1, d_rgb8=0, d_rgb64=0, stream=0):
         _check(lib().maray_hip_render_rows_device(self._h, w, h, y0, y1, d_rgb8 or None, d_rgb64 or None, stream or None))
 
@@ -471,19 +528,23 @@ class Context:
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,
-                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None):
+                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None, shutter=0, spans=None):
     """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
     samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling).
     params={name_or_id: value}: sets these declared parameters of the scene first (Scene.declare_param); the scene's
-    program and contexts are found again whatever the values."""
+    program and contexts are found again whatever the values.
+    shutter=n, spans={name_or_id: span}: motion blur, the integer mean of n frames whose parameters cover their spans around
+    the values (Scene.shutter_values), averaged on the device; spans are set on the scene first, like params."""
     for k, v in (params or {}).items():
         scene.set_param(scene.param_index(k), v)
+    for k, v in (spans or {}).items():
+        scene.set_param_span(scene.param_index(k), v)
     w, h = size if size else scene.size
     img = np.zeros((h, w, 3), np.uint8) if out is None else out
     assert img.shape == (h, w, 3) and img.dtype == np.uint8 and img.flags['C_CONTIGUOUS']
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.tile_rows, go.samples = backend, n_devices, tile_rows, samples
+    go.backend, go.n_devices, go.tile_rows, go.samples, go.shutter = backend, n_devices, tile_rows, samples, shutter
 
     def _cb(user, p, cw, ch, progress):
         if report:
@@ -494,11 +555,12 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     return img
 
 
-def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0):
-    """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased, as gen_to_image)."""
+def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0):
+    """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
+    parameter spans, as gen_to_image)."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.samples = backend, n_devices, samples
+    go.backend, go.n_devices, go.samples, go.shutter = backend, n_devices, samples, shutter
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
 
 

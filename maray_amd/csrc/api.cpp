@@ -18,6 +18,7 @@
 #include "expr.hpp"
 #include "lower.hpp"
 #include "maray_hip.h"
+#include "shutter.hpp"
 
 using namespace maray;
 
@@ -465,6 +466,47 @@ int maray_scene_set_param(maray_scene *s, uint32_t index, double value)
     });
 }
 
+// ---- shutter: the scene layer (host only) -------------------------------------------
+int maray_scene_set_param_span(maray_scene *s, uint32_t index, double span)
+{
+    return guard([&] {
+        REQUIRE(s && index < s->s.params.size(), "no such parameter");
+        REQUIRE(span >= 0.0 && std::isfinite(span), "a parameter's span is finite and >= 0");
+        s->s.params[index].span = span;
+    });
+}
+
+int maray_scene_param_span(const maray_scene *s, uint32_t index, double *span)
+{
+    return guard([&] {
+        REQUIRE(s && span && index < s->s.params.size(), "no such parameter");
+        *span = s->s.params[index].span;
+    });
+}
+
+int maray_scene_shutter_values(const maray_scene *s, uint32_t n, double *out)
+{
+    return guard([&] {
+        REQUIRE(s, "null argument");
+        REQUIRE(shutter_frames_ok(n), "shutter frames must be 1, 2, 4, 8, 16, 32 or 64");
+        const size_t P = s->s.params.size();
+        REQUIRE(out || !P, "null argument");
+        for (uint32_t i = 0; i < n; i++) {
+            // exact: |2i + 1 - n| < 64 over a power of two
+            const double c = (double)(2 * (int)i + 1 - (int)n) / (double)(2 * (int)n);
+            for (size_t p = 0; p < P; p++) {
+                const ParamDecl &pd = s->s.params[p];
+                double v = pd.value;            // span 0: the value itself, bit for bit (-0.0 and NaN stay what they are)
+                if (pd.span > 0.0) {
+                    const double step = pd.span * c;     // one multiply, one add, never fused (-ffp-contract=off)
+                    v = pd.value + step;
+                }
+                out[(size_t)i * P + p] = v;
+            }
+        }
+    });
+}
+
 int maray_scene_simplify(maray_scene *s)
 {
     return guard([&] { REQUIRE(s, "null argument"); s->key_valid = false; run_big_stack([&] { scene_simplify(s->s); }); });
@@ -644,9 +686,9 @@ static void check_rows(uint32_t w, uint32_t h, uint32_t y0, uint32_t y1)
 
 // A supersampling context evaluates k w x k h samples: the lowering's analysis covers sample indices below
 // MARAY_DOMAIN_MAX.  It writes RGB8 only.
-static void check_samples(const maray_ctx *c, uint32_t w, uint32_t h, bool want64)
+static void check_samples(const maray_ctx *c, uint32_t w, uint32_t h, bool want64, bool own_values = false)
 {
-    if (!c->params_ready) throw Error{MARAY_E_ARG, "the program's parameters have ranges that exclude NaN and no values yet: call maray_hip_ctx_set_params first"};
+    if (!c->params_ready && !own_values) throw Error{MARAY_E_ARG, "the program's parameters have ranges that exclude NaN and no values yet: call maray_hip_ctx_set_params first"};
     if (c->samples <= 1) return;
     if (want64) throw Error{MARAY_E_ARG, "a supersampling context renders RGB8 only (no f64 planes)"};
     if ((uint64_t)w * c->samples > MARAY_DOMAIN_MAX || (uint64_t)h * c->samples > MARAY_DOMAIN_MAX)
@@ -681,6 +723,75 @@ int maray_hip_render_tiles(maray_ctx *c, uint32_t w, uint32_t h, const uint32_t 
         std::function<void(uint32_t, uint32_t)> done;
         if (fn) done = [&](uint32_t a, uint32_t b) { fn(user, a, b); };
         c->backend->render_host_tiles(w, h, tiles, 0, rgb8_image, nullptr, done);
+    });
+}
+
+// ---- shutter ------------------------------------------------------------------------
+// n and every value of every frame, before anything is enqueued: one bad value and the call has done nothing
+static void check_shutter(const maray_ctx *c, const double *values, uint32_t n)
+{
+    REQUIRE(shutter_frames_ok(n), "shutter frames must be 1, 2, 4, 8, 16, 32 or 64");
+    const uint32_t P = (uint32_t)(c->param_ranges.size() / 2);
+    if (!P) return;
+    REQUIRE(values, "null argument: a program with parameters needs the frames' values");
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t p = 0; p < P; p++)
+            if (!param_value_ok(c->param_ranges.data(), p, values[(size_t)i * P + p]))
+                throw Error{MARAY_E_ARG, "frame " + std::to_string(i) + ": value of parameter " + std::to_string(p) + " is outside its declared range"};
+}
+
+int maray_hip_render_rows_shutter(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint32_t y1, const double *values, uint32_t n, uint8_t *rgb8)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend, "null context");
+        check_rows(w, h, y0, y1);
+        check_samples(c, w, h, false, true);
+        check_shutter(c, values, n);
+        if (y0 == y1 || w == 0 || !rgb8) return;
+        c->backend->render_host_tiles_shutter(w, h, cut_row_tiles(w, y0, y1, true, false), y0, values, n, rgb8, nullptr);
+    });
+}
+
+int maray_hip_render_rows_shutter_device(maray_ctx *c, uint32_t w, uint32_t h, uint32_t y0, uint32_t y1, const double *values, uint32_t n,
+                                         void *d_rgb8, void *stream)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend, "null context");
+        check_rows(w, h, y0, y1);
+        check_samples(c, w, h, false, true);
+        check_shutter(c, values, n);
+        if (y0 == y1 || w == 0) return;
+        REQUIRE(d_rgb8, "null argument");
+        c->backend->render_device_shutter(w, h, RowBlocks::range(y0, y1), values, n, d_rgb8, stream);
+    });
+}
+
+int maray_hip_render_tiles_shutter(maray_ctx *c, uint32_t w, uint32_t h, const uint32_t *tiles_y0y1, uint32_t n_tiles, const double *values, uint32_t n,
+                                   uint8_t *rgb8_image, maray_tile_fn fn, void *user)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend, "null context");
+        REQUIRE(n_tiles == 0 || tiles_y0y1, "null tile list");
+        std::vector<RowTile> tiles(n_tiles);
+        for (uint32_t i = 0; i < n_tiles; i++) {
+            tiles[i] = RowTile{tiles_y0y1[2 * i], tiles_y0y1[2 * i + 1]};
+            check_rows(w, h, tiles[i].y0, tiles[i].y1);
+            REQUIRE(tiles[i].y1 > tiles[i].y0, "empty tile");
+        }
+        check_samples(c, w, h, false, true);
+        check_shutter(c, values, n);
+        if (n_tiles == 0 || w == 0 || !rgb8_image) return;
+        std::function<void(uint32_t, uint32_t)> done;
+        if (fn) done = [&](uint32_t a, uint32_t b) { fn(user, a, b); };
+        c->backend->render_host_tiles_shutter(w, h, tiles, 0, values, n, rgb8_image, done);
+    });
+}
+
+int maray_hip_time_shutter_reduce(int device, size_t bytes, uint32_t n, int reps, float *ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        *ms_avg = shutter_time_reduce(device, bytes, n, reps);
     });
 }
 

@@ -39,6 +39,14 @@ struct Backend {
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
     virtual void set_params(const double *, uint32_t) { throw Error{MARAY_E_INTERNAL, "this program has no parameters"}; }
+    // Shutter (include/maray_hip.h, "shutter"): the integer mean of the n RGB8 frames that the rows of `values` (n x the
+    // program's parameter count, frame-major, every value inside its range: checked by the caller; null for a program
+    // without parameters) render, n in {1, 2, 4, ..., 64}.  Per frame set_params(row) and the ordinary launch into the
+    // context's scratch, per group of 8 frames one pass of maray_shutter_reduce on the same stream (shutter.hpp); the
+    // values set_params had before the call are put back (on the host) before it returns.
+    virtual void render_device_shutter(uint32_t w, uint32_t h, const RowBlocks &rb, const double *values, uint32_t n, void *d8, void *stream) = 0;
+    virtual void render_host_tiles_shutter(uint32_t w, uint32_t h, const std::vector<RowTile> &tiles, uint32_t row0, const double *values, uint32_t n,
+                                           uint8_t *rgb8, const std::function<void(uint32_t, uint32_t)> &done) = 0;
     // Tape interpreter only: re-evaluate the 256-pixel tiles of the device work list
     // {count, tile, tile, ...} (tile = row_in_launch * ceil(w/256) + x/256), reading the row
     // values from `yvals` instead of running the ROW section.  Enqueued on `stream`.

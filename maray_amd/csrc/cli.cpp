@@ -2,7 +2,8 @@
 //   maray -c N -i in.maray -o out.png [-t tex.png ...]        (:9-47)
 // plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), -p NAME=VALUE[:LO:HI] (a scene parameter:
 // the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
-// the one program and the contexts the first frame set up).  -c/--cpus is parsed and
+// the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
+// image the mean of N frames whose NAME covers SPAN around its value, averaged on the device).  -c/--cpus is parsed and
 // ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cmath>
 #include <cstdio>
@@ -28,7 +29,10 @@ static void usage()
             "  -p, --param <name=v[:lo:hi]> Value of the scene's free variable `name` (repeatable); lo:hi = the range it is\n"
             "                               declared with (default: any value)\n"
             "      --animate <name=a:b:n>   n images, `name` going from a to b in equal steps; --output needs a `%%d`\n"
-            "                               conversion (`frame%%03d.png`), numbered from 0\n");
+            "                               conversion (`frame%%03d.png`), numbered from 0\n"
+            "      --shutter <name=span>    Motion blur (repeatable): every image is the mean of N frames in which `name` covers\n"
+            "                               an interval of width span centred on its value; declares `name` if -p did not\n"
+            "      --shutter-samples <n>    N = 1, 2, 4, 8, 16, 32 or 64 (default: 8 once a --shutter is given)\n");
 }
 
 namespace {
@@ -75,6 +79,8 @@ int main(int argc, char **argv)
     std::vector<std::string> textures;
     std::vector<Param> params;
     Param anim; uint32_t frames = 0;
+    std::vector<Param> spans;           // --shutter: name, value = the span
+    uint32_t shutter_samples = 0;
     maray_gen_opts go;
     memset(&go, 0, sizeof go);
     go.backend = MARAY_BACKEND_AUTO;
@@ -108,6 +114,23 @@ int main(int argc, char **argv)
             }
             anim.value = n[0]; anim.hi = n[1]; frames = (uint32_t)n[2];
         }
+        else if (a == "--shutter") {
+            Param p; std::vector<double> n;
+            if (!split_name(val(), p.name, n) || n.size() != 1 || !(n[0] >= 0.0) || !std::isfinite(n[0])) {
+                fprintf(stderr, "Error: --shutter takes NAME=SPAN with a finite SPAN >= 0\n"); usage(); return 2;
+            }
+            p.value = n[0]; p.lo = p.hi = 0.0;
+            spans.push_back(p);
+        }
+        else if (a == "--shutter-samples") {
+            const std::string k = val();
+            if (k != "1" && k != "2" && k != "4" && k != "8" && k != "16" && k != "32" && k != "64") {
+                fprintf(stderr, "Error: --shutter-samples takes 1, 2, 4, 8, 16, 32 or 64, not `%s`\n", k.c_str());
+                usage();
+                return 2;
+            }
+            shutter_samples = (uint32_t)strtoul(k.c_str(), nullptr, 10);
+        }
         else if (a == "--backend") {
             std::string b = val();
             if (b == "tape") go.backend = MARAY_BACKEND_TAPE;
@@ -139,12 +162,39 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    // --animate and --shutter declare what -p did not: --animate the range its frames need, [FROM, TO] widened by half the
+    // name's span on both sides; --shutter alone any value, like -p.  A -p declaration stands as given: a frame outside an
+    // explicit LO:HI is the command line's mistake.
+    auto index_of = [&](const std::string &name, uint32_t &k) {
+        uint32_t n_par = 0;
+        maray_scene_param_count(scene, &n_par);
+        const uint64_t want = maray_var_id(name.c_str());
+        for (k = 0; k < n_par; k++) {
+            uint64_t id = 0;
+            maray_scene_param_info(scene, k, &id, nullptr, nullptr, nullptr);
+            if (id == want) return true;
+        }
+        return false;
+    };
     uint32_t anim_index = 0;
     const double from = anim.value, to = anim.hi;
-    if (frames && maray_scene_declare_param(scene, maray_var_id(anim.name.c_str()), std::fmin(from, to), std::fmax(from, to), &anim_index)) {
-        fprintf(stderr, "Error: --animate %s: %s\n", anim.name.c_str(), maray_last_error());
-        return 2;
+    if (frames && !index_of(anim.name, anim_index)) {
+        double half = 0.0;
+        for (const Param &sp : spans) if (sp.name == anim.name) half = sp.value / 2;
+        if (maray_scene_declare_param(scene, maray_var_id(anim.name.c_str()), std::fmin(from, to) - half, std::fmax(from, to) + half, &anim_index)) {
+            fprintf(stderr, "Error: --animate %s: %s\n", anim.name.c_str(), maray_last_error());
+            return 2;
+        }
     }
+    for (const Param &sp : spans) {
+        uint32_t k = 0;
+        if ((!index_of(sp.name, k) && maray_scene_declare_param(scene, maray_var_id(sp.name.c_str()), -INFINITY, INFINITY, &k)) ||
+            maray_scene_set_param_span(scene, k, sp.value)) {
+            fprintf(stderr, "Error: --shutter %s: %s\n", sp.name.c_str(), maray_last_error());
+            return 2;
+        }
+    }
+    if (!spans.empty()) go.shutter = shutter_samples ? shutter_samples : 8;
     maray_report rep{MARAY_REPORT_DURATION_MS, 500};   // Report::Duration(500 ms), examples/maray.rs:77-79
     int rc = 0;
     if (!frames) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());

@@ -48,6 +48,7 @@ struct ParamDecl {
     uint64_t id = 0;
     double lo = 0.0, hi = 0.0;      // declared range; -inf, +inf: any value, NaN included
     double value = 0.0;             // what gen / gen_to_image render with (NaN until set)
+    double span = 0.0;              // shutter: the frames of a shutter render cover [value - span/2, value + span/2] (0: every frame has `value`)
 };
 
 struct Scene {

@@ -226,6 +226,8 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail_with(MARAY_E_ARG, "samples must be 0, 1, 2, 4 or 8");
     if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
         return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
+    uint32_t shutter = opts && opts->shutter ? opts->shutter : 1u;
+    if (shutter > 64 || (shutter & (shutter - 1))) return fail_with(MARAY_E_ARG, "shutter must be 0, 1, 2, 4, 8, 16, 32 or 64");
     if (!w || !h) return MARAY_OK;
     // the program of this call: remembered from an earlier one, or lowered now
     std::string key;
@@ -315,6 +317,21 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
             if (const int rc = maray_scene_param_info(s, p, nullptr, nullptr, nullptr, &v)) return rc;
             param_values.push_back(v);
         }
+    // Shutter: the frames' values around the scene's current ones (maray_scene_shutter_values), handed to every worker with
+    // its tiles.  Without a span above 0 every frame would be the plain one: today's path, exactly.
+    std::vector<double> shutter_values;
+    if (shutter > 1) {
+        bool any_span = false;
+        for (uint32_t p = 0; p < (uint32_t)param_values.size(); p++) {
+            double sp = 0.0;
+            if (const int rc = maray_scene_param_span(s, p, &sp)) return rc;
+            any_span = any_span || sp > 0.0;
+        }
+        if (any_span) {
+            shutter_values.resize((size_t)shutter * param_values.size());
+            if (const int rc = maray_scene_shutter_values(s, shutter, shutter_values.data())) return rc;
+        }
+    }
 
     maray_ctx_opts co;
     memset(&co, 0, sizeof co);
@@ -341,7 +358,9 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         int r = ctx ? MARAY_OK : maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx);
         if (!r && !param_values.empty()) r = maray_hip_ctx_set_params(ctx, param_values.data(), (uint32_t)param_values.size());
         if (!r && !share[d].empty())
-            r = maray_hip_render_tiles(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), rgb8, on_tile, &tu);
+            r = shutter_values.empty() ? maray_hip_render_tiles(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), rgb8, on_tile, &tu)
+                                       : maray_hip_render_tiles_shutter(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), shutter_values.data(),
+                                                                        shutter, rgb8, on_tile, &tu);
         const std::string msg = r ? maray_last_error() : "";      // this thread's message, re-raised on the calling thread
         if (r) maray_hip_ctx_free(ctx);                           // (a context that failed is not kept)
         else gen_cache_give(*entry, dev, ctx, kept.ctx ? kept.hint_mpixels : co.hint_mpixels);      // (what it was CHOSEN for)

@@ -31,6 +31,7 @@
 #include "device_math.h"
 #include "host_pipe.hpp"
 #include "maray_hip.h"
+#include "shutter.hpp"
 
 namespace maray {
 
@@ -711,6 +712,7 @@ struct TapeBackend final : Backend {
     std::vector<double> param_values;
     bool params_dirty = false;
     ParamRing ring;
+    ShutterScratch shutter;             // frames and partial sums of the shutter entry points (shutter.hpp)
 
     ~TapeBackend() override {
         (void)hipSetDevice(device);
@@ -720,6 +722,7 @@ struct TapeBackend final : Backend {
         (void)hipFree(d_guard_ops); (void)hipFree(d_job_off); (void)hipFree(d_job_len); (void)hipFree(d_gbits);
         (void)hipFree(d_xtape_bits); (void)hipFree(d_xtape_rows); (void)hipFree(d_xrows); (void)hipFree(d_xguards);
         (void)hipFree(d_row_job_off); (void)hipFree(d_row_job_len); (void)hipFree(d_job_id); (void)hipFree(d_queue);
+        shutter.release();
         if (handover) (void)hipEventDestroy(handover);
         ring.release();
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
@@ -1027,6 +1030,34 @@ struct TapeBackend final : Backend {
         HIP_TRY(hipSetDevice(device));
         pipe->run(w, tiles, row0, rgb8, rgb64,
                  [&](const RowBlocks &rb, unsigned char *d8, double *d64, hipStream_t st) { launch(w, rb, d8, d64, st, true); }, done);
+    }
+
+    // One shutter picture into d8 (shutter.hpp): frames are ordinary launches on `st`, so the hand-over in launch() orders a
+    // call on another stream -- and the scratch with it -- like any other launch.  n = 1 or no parameters: the plain render.
+    void launch_shutter(uint32_t w, const RowBlocks &rb, const double *values, uint32_t n, unsigned char *d8, hipStream_t st) {
+        const uint32_t np = (uint32_t)param_values.size();
+        if (!np || n == 1) {
+            if (np) set_params(values, np);
+            launch(w, rb, d8, nullptr, st, true);
+            return;
+        }
+        shutter_render(shutter, values, n, np, (size_t)rb.n_rows * w * 3, d8, st,
+                       [&](const double *row) { set_params(row, np); },
+                       [&](unsigned char *frame) { launch(w, rb, frame, nullptr, st, true); });
+    }
+
+    void render_device_shutter(uint32_t w, uint32_t, const RowBlocks &rb, const double *values, uint32_t n, void *d8, void *stream) override {
+        HIP_TRY(hipSetDevice(device));
+        ShutterRestore<TapeBackend> keep{*this, param_values};
+        launch_shutter(w, rb, values, n, (unsigned char *)d8, (hipStream_t)stream);
+    }
+
+    void render_host_tiles_shutter(uint32_t w, uint32_t, const std::vector<RowTile> &tiles, uint32_t row0, const double *values, uint32_t n,
+                                   uint8_t *rgb8, const std::function<void(uint32_t, uint32_t)> &done) override {
+        HIP_TRY(hipSetDevice(device));
+        ShutterRestore<TapeBackend> keep{*this, param_values};
+        pipe->run(w, tiles, row0, rgb8, nullptr,
+                 [&](const RowBlocks &rb, unsigned char *d8, double *, hipStream_t st) { launch_shutter(w, rb, values, n, d8, st); }, done);
     }
 
     float time_rows(uint32_t w, uint32_t h, const RowBlocks &rb, void *d8, void *d64, int reps) override {

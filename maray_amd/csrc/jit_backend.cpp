@@ -23,6 +23,7 @@
 #include "host_pipe.hpp"
 #include "jit_parts.hpp"
 #include "maray_hip.h"
+#include "shutter.hpp"
 
 namespace maray {
 
@@ -73,6 +74,7 @@ struct JitBackend final : Backend {
     std::vector<double> param_values;
     bool params_dirty = false;
     ParamRing ring;
+    ShutterScratch shutter;             // frames and partial sums of the shutter entry points (shutter.hpp)
 
     ~JitBackend() override {
         (void)hipSetDevice(device);
@@ -85,6 +87,7 @@ struct JitBackend final : Backend {
         for (auto p : d_tex_rgb) (void)hipFree(p);
         (void)hipFree(d_order); (void)hipFree(d_rgb8);
         (void)hipFree(d_yvals); (void)hipFree(d_gbits);
+        shutter.release();
         if (handover) (void)hipEventDestroy(handover);
         ring.release();
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
@@ -389,6 +392,34 @@ struct JitBackend final : Backend {
         HIP_TRY(hipSetDevice(device));
         pipe->run(w, tiles, row0, rgb8, rgb64,
                  [&](const RowBlocks &rb, unsigned char *d8, double *d64, hipStream_t st) { launch(w, rb, d8, d64, st, true); }, done);
+    }
+
+    // One shutter picture into d8 (shutter.hpp): frames are ordinary launches on `st`, so the hand-over in launch() orders a
+    // call on another stream -- and the scratch with it -- like any other launch.  n = 1 or no parameters: the plain render.
+    void launch_shutter(uint32_t w, const RowBlocks &rb, const double *values, uint32_t n, unsigned char *d8, hipStream_t st) {
+        const uint32_t np = (uint32_t)param_values.size();
+        if (!np || n == 1) {
+            if (np) set_params(values, np);
+            launch(w, rb, d8, nullptr, st, true);
+            return;
+        }
+        shutter_render(shutter, values, n, np, (size_t)rb.n_rows * w * 3, d8, st,
+                       [&](const double *row) { set_params(row, np); },
+                       [&](unsigned char *frame) { launch(w, rb, frame, nullptr, st, true); });
+    }
+
+    void render_device_shutter(uint32_t w, uint32_t, const RowBlocks &rb, const double *values, uint32_t n, void *d8, void *stream) override {
+        HIP_TRY(hipSetDevice(device));
+        ShutterRestore<JitBackend> keep{*this, param_values};
+        launch_shutter(w, rb, values, n, (unsigned char *)d8, (hipStream_t)stream);
+    }
+
+    void render_host_tiles_shutter(uint32_t w, uint32_t, const std::vector<RowTile> &tiles, uint32_t row0, const double *values, uint32_t n,
+                                   uint8_t *rgb8, const std::function<void(uint32_t, uint32_t)> &done) override {
+        HIP_TRY(hipSetDevice(device));
+        ShutterRestore<JitBackend> keep{*this, param_values};
+        pipe->run(w, tiles, row0, rgb8, nullptr,
+                 [&](const RowBlocks &rb, unsigned char *d8, double *, hipStream_t st) { launch_shutter(w, rb, values, n, d8, st); }, done);
     }
 
     float time_rows(uint32_t w, uint32_t, const RowBlocks &rb, void *d8, void *d64, int reps) override {
