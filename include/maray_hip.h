@@ -196,7 +196,8 @@ typedef struct maray_ctx_opts {
                                this context; 0 = unknown / many.  The specialised kernels are worth their hiprtc build only
                                when that time is earned back (or when the code object cache already holds them). */
     uint32_t samples;       /* k x k samples per output pixel, k in {0, 1, 2, 4, 8} (0 = 1); see "supersampling" below */
-    uint32_t reserved[5];
+    uint32_t filter;        /* MARAY_FILTER_*: how the k x k samples become pixels; see "reconstruction filter" below */
+    uint32_t reserved[4];
 } maray_ctx_opts;
 
 /* ---- supersampling (anti-aliasing with an in-kernel box filter) ---------------------------------------------------
@@ -214,6 +215,38 @@ typedef struct maray_ctx_opts {
  * MARAY_DOMAIN_MAX: MARAY_E_LIMIT.  Every back-end has a supersampling kernel (maray_tape_pixels_ss, maray_jit_pixels_ss);
  * AUTO chooses between them as for a plain render.  k = 0 or 1 is the plain render, unchanged. */
 int maray_scene_supersample(maray_scene *s, uint32_t k);   /* X -> X/k - (k-1)/(2k), Y alike, size * k; k = 0 or 1: no change */
+
+/* ---- reconstruction filter (what turns the samples of a supersampled render into pixels) ---------------------------
+ * `filter` (maray_ctx_opts.filter, maray_gen_opts.filter) is MARAY_FILTER_BOX, the in-kernel mean described above and the
+ * default, or MARAY_FILTER_TENT, a tent (Bartlett) filter two output pixels wide whose footprint overlaps the neighbouring
+ * pixels'.  TENT needs samples = k in {2, 4, 8}: TENT with samples 0 or 1 is MARAY_E_ARG, any other filter value is
+ * MARAY_E_ARG.  A TENT context is created like a box one, from the SUPERSAMPLED program (maray_scene_supersample(s, k), then
+ * lower), and every render entry point takes output geometry.
+ *   - s(a, b, c) is the cast (`as u8`) sample of channel c at integer sample index (a, b) of the k w x k h sample raster:
+ *     what a plain context of the same program renders;
+ *   - per axis the footprint of pixel p is the 2k sample indices k p + u, u = -k/2 .. 3k/2 - 1, with the integer weights
+ *     t(u) = 2k - |2u + 1 - k| (k = 2: 1 3 3 1; k = 4: 1 3 5 7 7 5 3 1; k = 8: 1 3 .. 15 15 .. 3 1; their sum is 2 k^2);
+ *   - indices are clamped to the IMAGE: a -> min(max(a, 0), k w - 1), b alike with k h - 1 -- never to a launch's rows, a
+ *     band or a tile;
+ *   - out(px, py, c) = (SUM_u SUM_v t(u) t(v) s(clamp(k px + u), clamp(k py + v), c) + W/2) >> log2 W, W = 4 k^4
+ *     (64 / 1024 / 16384: a shift by 6 / 10 / 14).
+ * All arithmetic is integer (a horizontal partial sum is <= 255 * 2 k^2 = 32640: 16 bits; the full sum <= 255 * 16384: 32
+ * bits), so the picture is the same whatever the launch order, band size, tile cut or device split; a constant image comes
+ * out unchanged, and every sample's weights over all pixels sum to the same value.
+ * RGB8 only (f64 planes: MARAY_E_ARG); k w or k h above MARAY_DOMAIN_MAX: MARAY_E_LIMIT, as for box.
+ * Output rows [y0, y1) read the sample rows [k y0 - k/2, k y1 + k/2) clipped to [0, k h): every entry point renders that halo
+ * itself -- per row range, per row block, per host tile, per gen_to_image tile and worker.
+ * How it runs: the context is a plain back-end (samples = 1; any of the three, AUTO chooses as for box) of the program behind
+ * a wrapper that, per band of output rows, enqueues one ordinary launch of the band's sample rows plus halo into scratch of
+ * the context and then maray_filter_tent<k> on the same stream.  The scratch grows to the largest call, is ordered by the
+ * stream and freed with the context; the device-pointer forms return without a device synchronise.  A band holds about
+ * 128 MiB of samples; MARAY_FILTER_BAND_ROWS=<output rows>, read when the context is created, overrides that (measurements,
+ * tests).  maray_hip_ctx_set_params passes through; the shutter entry points average tent-filtered frames; maray_hip_time_rows
+ * / _blocks time launches plus filter; maray_hip_kernel_name is the inner kernel's name + "+maray_filter_tent<k>". */
+enum { MARAY_FILTER_BOX = 0, MARAY_FILTER_TENT = 1 };
+/* The filter kernel on its own (measurements): average ms of one pass over a w x rows output image (k w x k rows samples in
+ * scratch of the call's own, whatever they hold). */
+int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int reps, float *ms_avg);
 
 int maray_hip_device_count(int *n);
 /* Uploads tape, constants and textures to HBM once. */
@@ -350,7 +383,9 @@ typedef struct maray_gen_opts {
     uint32_t shutter;        /* n frames averaged over the scene's parameter spans (maray_scene_shutter_values; n in {0, 1, 2, 4,
                                 ..., 64}).  0, 1 or no span above 0: the plain render, exactly.  The program and its contexts are
                                 the plain render's: spans and n are not part of their name */
-    uint32_t reserved[3];
+    uint32_t filter;         /* MARAY_FILTER_* ("reconstruction filter"); TENT needs samples in {2, 4, 8}; programs and contexts
+                                are kept per (k, filter) */
+    uint32_t reserved[2];
 } maray_gen_opts;
 
 /* gen_to_image: fills the caller's w*h*3 RGB8 buffer. */
@@ -362,7 +397,7 @@ int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t 
  * it in a loop (examples/test*.rs) pays the lowering and the context creation once, not per frame.  This frees them. */
 void maray_gen_cache_clear(void);
 /* What is kept, one line per idle context: "<program key> device <d> kernel <name> hint_mpixels <n>" (NUL-terminated,
- * cut to cap).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
+ * cut to cap; " samples <k>" follows for k > 1 and " filter tent" after that for MARAY_FILTER_TENT).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
  * the call it was chosen for; contexts are kept per physical device. */
 int maray_gen_cache_info(char *out, size_t cap);
 /* gen: render and write a PNG (progress callback prints "%.2f %%" to stderr

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 OP_COUNT = 20
 BACKEND_TAPE, BACKEND_TAPE_SMEM, BACKEND_JIT, BACKEND_AUTO = 0, 1, 2, 3
 REPORT_NONE, REPORT_ROW, REPORT_DURATION_MS = 0, 1, 2
+FILTER_BOX, FILTER_TENT = 0, 1
 
 
 class MarayError(RuntimeError):
@@ -46,12 +47,12 @@ class LowerOpts(C.Structure):
 
 
 class CtxOpts(C.Structure):
-    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('samples', C.c_uint32), ('reserved', C.c_uint32 * 5)]
+    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('samples', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 4)]
 
 
 class GenOpts(C.Structure):
     _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32), ('samples', C.c_uint32),
-                ('shutter', C.c_uint32), ('reserved', C.c_uint32 * 3)]
+                ('shutter', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 2)]
 
 
 class Report(C.Structure):
@@ -109,6 +110,7 @@ def lib():
         'maray_hip_render_rows_shutter_device': (C.c_int, [vp, u32, u32, u32, u32, vp, u32, vp, vp]),
         'maray_hip_render_tiles_shutter': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, u32, vp, TILE_FN, vp]),
         'maray_hip_time_shutter_reduce': (C.c_int, [C.c_int, C.c_size_t, u32, C.c_int, C.POINTER(C.c_float)]),
+        'maray_hip_time_filter': (C.c_int, [C.c_int, u32, u32, u32, C.c_int, C.POINTER(C.c_float)]),
         'maray_tape_param_count': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_tape_param_range': (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         'maray_hip_ctx_set_params': (C.c_int, [vp, C.POINTER(C.c_double), u32]),
@@ -417,14 +419,17 @@ class PinnedRaster:
 
 class Context:
     """Device context: tape + constants + textures resident in HBM.  samples=k > 1: renders the program's raster in k x k
-    blocks and writes their means (RGB8 only); every render call then takes output geometry."""
+    blocks and writes their means (RGB8 only); every render call then takes output geometry.  filter=FILTER_TENT (needs
+    samples 2, 4 or 8): the samples are reduced by a tent filter two pixels wide instead (include/maray_hip.h,
+    "reconstruction filter")."""
 
-    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0):
+    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0, filter=FILTER_BOX):
         arr, n, keep = _textures(textures)
         o = CtxOpts()
         o.backend = backend
         o.hint_mpixels = hint_mpixels
         o.samples = samples
+        o.filter = filter
         h = C.c_void_p()
         _check(lib().maray_hip_ctx_create(device, C.byref(tape.program), arr, n, C.byref(o), C.byref(h)))
         self._h = h
@@ -528,9 +533,10 @@ class Context:
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,
-                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None, shutter=0, spans=None):
+                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None, shutter=0, spans=None, filter=FILTER_BOX):
     """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
-    samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling).
+    samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling); filter=FILTER_TENT: reduced
+    by a tent filter two pixels wide instead of the box (needs samples 2, 4 or 8).
     params={name_or_id: value}: sets these declared parameters of the scene first (Scene.declare_param); the scene's
     program and contexts are found again whatever the values.
     shutter=n, spans={name_or_id: span}: motion blur, the integer mean of n frames whose parameters cover their spans around
@@ -544,7 +550,7 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     assert img.shape == (h, w, 3) and img.dtype == np.uint8 and img.flags['C_CONTIGUOUS']
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.tile_rows, go.samples, go.shutter = backend, n_devices, tile_rows, samples, shutter
+    go.backend, go.n_devices, go.tile_rows, go.samples, go.shutter, go.filter = backend, n_devices, tile_rows, samples, shutter, filter
 
     def _cb(user, p, cw, ch, progress):
         if report:
@@ -555,13 +561,20 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     return img
 
 
-def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0):
+def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0, filter=FILTER_BOX):
     """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
-    parameter spans, as gen_to_image)."""
+    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; as gen_to_image)."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.samples, go.shutter = backend, n_devices, samples, shutter
+    go.backend, go.n_devices, go.samples, go.shutter, go.filter = backend, n_devices, samples, shutter, filter
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
+
+
+def time_filter(w, rows, k, device=0, reps=10):
+    """Average ms of maray_filter_tent<k> alone over a w x rows output image (maray_hip_time_filter)."""
+    ms = C.c_float()
+    _check(lib().maray_hip_time_filter(device, w, rows, k, reps, C.byref(ms)))
+    return ms.value
 
 
 def gen_cache_clear():

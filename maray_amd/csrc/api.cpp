@@ -16,6 +16,7 @@
 
 #include "backend.hpp"
 #include "expr.hpp"
+#include "filter.hpp"
 #include "lower.hpp"
 #include "maray_hip.h"
 #include "shutter.hpp"
@@ -599,8 +600,14 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
                         std::to_string(5u * n_tex) + " texture functions exist"};
         for (uint32_t i = 0; i < n_tex; i++) REQUIRE(tex[i].rgb || (uint64_t)tex[i].w * tex[i].h == 0, "null texture raster");
         const uint32_t backend = opts ? opts->backend : MARAY_BACKEND_TAPE;
-        const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
+        uint32_t samples = opts && opts->samples ? opts->samples : 1u;
         REQUIRE(samples == 1 || samples == 2 || samples == 4 || samples == 8, "samples must be 0, 1, 2, 4 or 8");
+        const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
+        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT, "unknown filter");
+        REQUIRE(filter != MARAY_FILTER_TENT || samples > 1, "the tent filter needs samples = 2, 4 or 8");
+        // a tent context is a plain back-end of the (supersampled) program behind the filter's wrapper (filter_backend.cpp)
+        const uint32_t k = samples;
+        if (filter == MARAY_FILTER_TENT) samples = 1;
         Backend *b = nullptr;
         switch (backend) {
         case MARAY_BACKEND_TAPE: b = make_tape_backend(device, *prog, tex, n_tex, true, samples); break;
@@ -637,10 +644,14 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         }
         default: throw Error{MARAY_E_ARG, "unknown backend"};
         }
+        if (filter == MARAY_FILTER_TENT) {
+            try { b = make_filter_backend(device, b, k, prog->n_params); }
+            catch (...) { delete b; throw; }
+        }
         maray_ctx *c = new maray_ctx();
         c->backend = b;
         c->n_tex = n_tex;
-        c->samples = samples;
+        c->samples = k;             // (a tent context too takes output geometry, RGB8 only, k w and k h within the domain)
         if (prog->n_params) c->param_ranges.assign(prog->param_ranges, prog->param_ranges + 2 * (size_t)prog->n_params);
         for (uint32_t p = 0; p < prog->n_params; p++) c->params_ready = c->params_ready && param_value_ok(c->param_ranges.data(), p, NAN);
         *out = c;
@@ -792,6 +803,14 @@ int maray_hip_time_shutter_reduce(int device, size_t bytes, uint32_t n, int reps
     return guard([&] {
         REQUIRE(ms_avg, "null argument");
         *ms_avg = shutter_time_reduce(device, bytes, n, reps);
+    });
+}
+
+int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int reps, float *ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        *ms_avg = filter_time_tent(device, w, rows, k, reps);
     });
 }
 

@@ -1,6 +1,7 @@
 // cli.cpp — `maray` command line (product code).  Mirrors examples/maray.rs:
 //   maray -c N -i in.maray -o out.png [-t tex.png ...]        (:9-47)
-// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), -p NAME=VALUE[:LO:HI] (a scene parameter:
+// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), --filter {box,tent} (how the samples become
+// pixels), -p NAME=VALUE[:LO:HI] (a scene parameter:
 // the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
 // the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
 // image the mean of N frames whose NAME covers SPAN around its value, averaged on the device).  -c/--cpus is parsed and
@@ -26,6 +27,7 @@ static void usage()
             "      --gpus <n>               Number of MI355X devices (default: all)\n"
             "      --backend <b>            auto | jit | tape | tape-smem (default: auto)\n"
             "  -s, --samples <k>            Anti-aliasing: k x k samples per pixel, box-filtered; k = 1, 2, 4 or 8 (default: 1)\n"
+            "      --filter <f>             box | tent (default: box); tent is two pixels wide and needs -s 2, 4 or 8\n"
             "  -p, --param <name=v[:lo:hi]> Value of the scene's free variable `name` (repeatable); lo:hi = the range it is\n"
             "                               declared with (default: any value)\n"
             "      --animate <name=a:b:n>   n images, `name` going from a to b in equal steps; --output needs a `%%d`\n"
@@ -101,6 +103,12 @@ int main(int argc, char **argv)
             }
             go.samples = (uint32_t)(k[0] - '0');
         }
+        else if (a == "--filter") {
+            const std::string f = val();
+            if (f == "box") go.filter = MARAY_FILTER_BOX;
+            else if (f == "tent") go.filter = MARAY_FILTER_TENT;
+            else { fprintf(stderr, "Error: --filter takes box or tent, not `%s`\n", f.c_str()); usage(); return 2; }
+        }
         else if (a == "-p" || a == "--param") {
             Param p; std::vector<double> n;
             if (!split_name(val(), p.name, n) || (n.size() != 1 && n.size() != 3)) { fprintf(stderr, "Error: -p takes NAME=VALUE or NAME=VALUE:LO:HI\n"); usage(); return 2; }
@@ -142,6 +150,7 @@ int main(int argc, char **argv)
         else { usage(); return 2; }
     }
     if (input.empty() || output.empty()) { usage(); return 2; }
+    if (go.filter == MARAY_FILTER_TENT && go.samples < 2) { fprintf(stderr, "Error: --filter tent needs -s 2, 4 or 8\n"); usage(); return 2; }
     if (frames && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
 
     maray_scene *scene = nullptr;

@@ -1,0 +1,42 @@
+// filter.hpp — the tent reconstruction filter of a supersampled render (include/maray_hip.h, "reconstruction filter"):
+// a plain back-end of the supersampled program renders bands of the sample raster into scratch in HBM, and
+// maray_filter_tent<K> (filter.hip) turns each band into output rows.  Builds no program's kernels: not part of a code key.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "backend.hpp"
+#include "expr.hpp"
+#include "maray_hip.h"
+
+namespace maray {
+
+constexpr uint32_t FILTER_TILE_W = 64, FILTER_TILE_H = 8;      // output pixels a block computes
+constexpr size_t FILTER_PAD = 16;       // bytes in front of and behind a band that the kernel's dword loads may touch (never use)
+
+inline bool filter_samples_ok(uint32_t k) { return k == 2 || k == 4 || k == 8; }
+
+// One pass: output rows [oy0, oy0 + n_out) of a w-pixel-wide image from a band of its sample raster.  `src` is the first
+// byte of sample row band_row0 (image coordinates); the band holds band_rows rows of sw * 3 bytes, which must cover
+// [k oy0 - k/2, k (oy0 + n_out) + k/2) clipped to [0, sh); FILTER_PAD bytes in front of src and behind the band's last row
+// are readable.  dst: n_out packed rows of w * 3 bytes, any alignment.
+struct TentArgs {
+    const unsigned char *src;
+    unsigned char *dst;
+    uint32_t w;                     // output width
+    uint32_t sw, sh;                // the image's sample raster: k w x k h
+    uint32_t band_row0, band_rows;
+    uint32_t oy0, n_out;
+};
+
+void filter_tent(uint32_t k, const TentArgs &a, hipStream_t st);      // enqueues one pass; throws Error
+float filter_time_tent(int device, uint32_t w, uint32_t rows, uint32_t k, int reps);     // maray_hip_time_filter
+
+// The context behind MARAY_FILTER_TENT: takes over `inner`, a plain (samples = 1) back-end of the supersampled program on
+// `device`.  Throws Error (then `inner` is still the caller's).
+Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params);
+
+}   // namespace maray

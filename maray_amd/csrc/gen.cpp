@@ -96,6 +96,7 @@ struct IdleCtx {
 struct GenEntry {
     std::string key;
     uint32_t samples = 1;                     // the program is the scene supersampled k x k (maray_gen_opts.samples)
+    uint32_t filter = MARAY_FILTER_BOX;       // what its contexts reduce the samples with (maray_gen_opts.filter)
     maray_tape *tape = nullptr;
     std::multimap<int, IdleCtx> idle;         // per PHYSICAL device: contexts nobody is rendering with
     bool evicted = false;
@@ -208,7 +209,8 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
         for (auto &e : g_gen)
             for (auto &kv : e->idle)
                 t += e->key + " device " + std::to_string(kv.first) + " kernel " + maray_hip_kernel_name(kv.second.ctx) + " hint_mpixels " +
-                     std::to_string(kv.second.hint_mpixels) + (e->samples > 1 ? " samples " + std::to_string(e->samples) : std::string()) + "\n";
+                     std::to_string(kv.second.hint_mpixels) + (e->samples > 1 ? " samples " + std::to_string(e->samples) : std::string()) +
+                     (e->filter == MARAY_FILTER_TENT ? " filter tent" : "") + "\n";
     }
     snprintf(out, cap, "%s", t.c_str());
     return MARAY_OK;
@@ -226,6 +228,9 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail_with(MARAY_E_ARG, "samples must be 0, 1, 2, 4 or 8");
     if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
         return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
+    const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
+    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT) return fail_with(MARAY_E_ARG, "unknown filter");
+    if (filter == MARAY_FILTER_TENT && samples == 1) return fail_with(MARAY_E_ARG, "the tent filter needs samples = 2, 4 or 8");
     uint32_t shutter = opts && opts->shutter ? opts->shutter : 1u;
     if (shutter > 64 || (shutter & (shutter - 1))) return fail_with(MARAY_E_ARG, "shutter must be 0, 1, 2, 4, 8, 16, 32 or 64");
     if (!w || !h) return MARAY_OK;
@@ -244,6 +249,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         snprintf(buf, sizeof buf, "%016llx%016llx/%u/%u", (unsigned long long)h[0], (unsigned long long)h[1], n_tex, opts ? opts->backend : (uint32_t)MARAY_BACKEND_AUTO);
         key = buf;
         if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
+        if (filter == MARAY_FILTER_TENT) key += "/tent";             // (box keeps its key: the two are kept side by side)
     }
     int n_dev_avail = 0;
     maray_hip_device_count(&n_dev_avail);
@@ -302,7 +308,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         warm.clear();
         if (rc) return rc;
         auto fresh = std::make_shared<GenEntry>();
-        fresh->key = key; fresh->tape = tape; fresh->samples = samples;
+        fresh->key = key; fresh->tape = tape; fresh->samples = samples; fresh->filter = filter;
         entry = gen_cache_insert(fresh);
     } else pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
@@ -337,6 +343,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     memset(&co, 0, sizeof co);
     co.backend = opts ? opts->backend : MARAY_BACKEND_AUTO;
     co.samples = samples;
+    co.filter = filter;
     co.hint_mpixels = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (((uint64_t)w * h * samples * samples / n_dev) >> 20) + 1);      // samples it evaluates
 
     Progress P;
