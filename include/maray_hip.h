@@ -385,8 +385,11 @@ typedef struct maray_gen_opts {
                                 the plain render's: spans and n are not part of their name */
     uint32_t filter;         /* MARAY_FILTER_* ("reconstruction filter"); TENT needs samples in {2, 4, 8}; programs and contexts
                                 are kept per (k, filter) */
-    uint32_t reserved[2];
+    uint32_t encoder;        /* MARAY_ENCODER_* (offset 24): who writes maray_gen's PNG; see "device PNG encoder" below.  Any other value:
+                                MARAY_E_ARG.  maray_gen_to_image checks the word and otherwise ignores it */
+    uint32_t reserved[1];
 } maray_gen_opts;
+enum { MARAY_ENCODER_HOST = 0, MARAY_ENCODER_DEVICE = 1 };
 
 /* gen_to_image: fills the caller's w*h*3 RGB8 buffer. */
 int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
@@ -401,9 +404,64 @@ void maray_gen_cache_clear(void);
  * the call it was chosen for; contexts are kept per physical device. */
 int maray_gen_cache_info(char *out, size_t cap);
 /* gen: render and write a PNG (progress callback prints "%.2f %%" to stderr
- * and re-saves the partial image, like src/lib.rs:1203-1208). */
+ * and re-saves the partial image, like src/lib.rs:1203-1208).
+ * With opts->encoder = MARAY_ENCODER_DEVICE every worker renders its tiles with maray_hip_render_rows_device (or, for a shutter
+ * call, maray_hip_render_rows_shutter_device) into its encoder's band buffer, encodes them on its own device and hands over
+ * only the compressed segments; the calling thread puts the file together in row order (the same bytes for any n_devices and
+ * tile_rows).  With a report the percentage is still printed, but the partial file is NOT re-saved: there is no host raster.
+ * A scene of size 0 in x or y is MARAY_E_ARG with this encoder. */
 int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
               const maray_gen_opts *opts, maray_report report, const char *png_path);
+
+/* ---- device PNG encoder ------------------------------------------------------------------------------------------
+ * MARAY_ENCODER_DEVICE builds the zlib stream of the PNG on the device: the compressed stream crosses to the host, not the
+ * raster, and the host's zlib compression goes away.  PNG container bytes are an encoder's choice: the file decodes to the
+ * same RGB8 raster as the host writer's (maray_png_write: filter 0, zlib level 6, the default, unchanged), not to the same
+ * bytes.  The result is an ordinary PNG -- IHDR (8-bit truecolour, no interlace), IDAT chunks of at most 2^30 bytes, IEND,
+ * CRC-32 by zlib's crc32 -- around this stream:
+ *   - filtered data: row y is one filter byte followed by the row's 3 w bytes.  The encoder writes filter 0 (None) in every
+ *     row; a later one may write any type 0 .. 4 that a decoder accepts;
+ *   - segments: each row's 3 w + 1 filtered bytes are cut into segments of SEG = 256 pixels (the last of a row may be
+ *     shorter; the filter byte belongs to the row's first segment).  Segments are compressed independently: no match
+ *     reaches back over a segment's start;
+ *   - a segment is whole deflate blocks followed by an empty stored block that ends on a byte boundary: the 3 bits BFINAL = 0,
+ *     BTYPE = 00, zero bits to the byte, then 00 00 FF FF (the sync flush pigz uses);
+ *   - the stream is 78 01, the segments in row-major order, 01 00 00 FF FF (a final empty stored block), and the Adler-32 of
+ *     all filtered bytes, big-endian;
+ *   - the file's bytes are therefore a function of the raster alone: identical for every band height (MARAY_PNG_BAND_ROWS),
+ *     tile cut, stream and device split;
+ *   - coding: one fixed-Huffman block (BTYPE = 01) per segment.  Literals are the standard fixed codes; a run of pixels equal
+ *     to the pixel before them is coded as matches of distance 3 (distance code 2, no extra bits) whose length is a multiple
+ *     of 3 and at most 258 (here: at most 192, a run is closed every 64 pixels); Huffman codes go into the LSB-first bit
+ *     stream bit-reversed, extra bits as they are;
+ *   - Adler-32: per segment of n bytes b_0 .. b_(n-1) the device forms A = sum b_i and B = sum (n - i) b_i; from (s1, s2) =
+ *     (1, 0) the segments in order give s2 <- (s2 + n s1 + B) mod 65521, then s1 <- (s1 + A) mod 65521.  The device combines a
+ *     band's segments -- a run of segments is again such a triple (n, A, B), and a segment's share of its band's B is
+ *     B + A x (the band's bytes after the segment), so the shares add up in any order -- and three words modulo 65521 per
+ *     band come to the host, which combines the bands in order.  The raster never reaches the host;
+ *   - size: a segment of n bytes occupies at most ceil(9 n / 8) + 16 bytes (9-bit literals, block header, end-of-block, sync):
+ *     that is its scratch slot.  There is no stored-block fallback.
+ * How it runs: per band of rows (64 MiB of raster; MARAY_PNG_BAND_ROWS=<rows>, read when an encoder is created, overrides
+ * that) maray_png_compress (one wavefront per segment), maray_png_scan (offsets of the segments, the band's Adler part) and
+ * maray_png_gather (the contiguous stream) on one stream; then one copy of 24 bytes (the total and the Adler part) and one of
+ * exactly the stream's bytes into pinned staging.  Scratch -- slots, lengths, offsets, the gathered stream, a band buffer for
+ * the entry points that render -- belongs to an encoder, grows to the largest call and is freed with it; the library keeps
+ * up to two idle encoders per device.  All sizes and offsets past a band are 64-bit.
+ * Errors: a null pointer, w = 0 or h = 0: MARAY_E_ARG; a side above MARAY_DOMAIN_MAX or (3 w + 1) h above 2^34 (the host
+ * writer's limit): MARAY_E_LIMIT; nothing is launched in those cases. */
+/* A packed RGB8 raster in device memory (any byte alignment) -> a complete PNG in malloc'ed host memory (maray_free).  The
+ * kernels and copies are enqueued on `stream` (a hipStream_t, NULL = the null stream); the call waits for them, and for
+ * nothing else. */
+int maray_hip_png_encode_device(int device, const void *d_rgb8, uint32_t w, uint32_t h, void *stream, uint8_t **png_out, size_t *n_out);
+/* The whole w x h image of a context (any back-end, samples, filter) as a PNG: rendered band by band through the device
+ * entry points into the encoder's band buffer and encoded there; no raster crosses to the host.  values = NULL: the plain
+ * render (maray_hip_render_rows_device); else a shutter call of n_frames frames (maray_hip_render_rows_shutter_device, same
+ * checks, nothing launched when one fails). */
+int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint8_t **png_out, size_t *n_out);
+/* Measurements: average ms of the three kernels over the caller's raster as ONE band ((3 w + 1) h <= 2^30), and the bytes
+ * of its gathered stream; and the bytes the process' encoders have copied to the host so far (payloads and totals). */
+int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32_t h, int reps, float *ms_avg, uint64_t *stream_bytes);
+uint64_t maray_hip_png_bytes_to_host(void);
 
 /* PNG I/O used by gen and the CLI (`img.save`, `image::open(..).to_rgb8()`). */
 int maray_png_write(const char *path, const uint8_t *rgb8, uint32_t w, uint32_t h);

@@ -13,6 +13,7 @@ OP_COUNT = 20
 BACKEND_TAPE, BACKEND_TAPE_SMEM, BACKEND_JIT, BACKEND_AUTO = 0, 1, 2, 3
 REPORT_NONE, REPORT_ROW, REPORT_DURATION_MS = 0, 1, 2
 FILTER_BOX, FILTER_TENT = 0, 1
+ENCODER_HOST, ENCODER_DEVICE = 0, 1
 
 
 class MarayError(RuntimeError):
@@ -52,7 +53,7 @@ class CtxOpts(C.Structure):
 
 class GenOpts(C.Structure):
     _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32), ('samples', C.c_uint32),
-                ('shutter', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 2)]
+                ('shutter', C.c_uint32), ('filter', C.c_uint32), ('encoder', C.c_uint32), ('reserved', C.c_uint32 * 1)]
 
 
 class Report(C.Structure):
@@ -141,6 +142,10 @@ def lib():
         'maray_gen': (C.c_int, [vp, C.POINTER(Texture), u32, C.POINTER(GenOpts), Report, C.c_char_p]),
         'maray_gen_cache_clear': (None, []),
         'maray_gen_cache_info': (C.c_int, [C.c_char_p, C.c_size_t]),
+        'maray_hip_png_encode_device': (C.c_int, [C.c_int, vp, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_png': (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_png_encode': (C.c_int, [C.c_int, vp, u32, u32, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_hip_png_bytes_to_host': (C.c_uint64, []),
         'maray_png_write': (C.c_int, [C.c_char_p, vp, u32, u32]),
         'maray_png_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
         'maray_image_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
@@ -507,6 +512,14 @@ class Context:
         cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
         _check(lib().maray_hip_render_tiles_shutter(self._h, w, h, flat, len(tiles), vp_, n, image.ctypes.data, cb, None))
 
+    def render_png(self, w, h, frames=None):
+        """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png); frames: as
+        for render_rows_shutter (None: the plain render)."""
+        n, vp_, keep = (0, None, None) if frames is None else self._frames(frames)
+        p, sz = C.c_void_p(), C.c_size_t()
+        _check(lib().maray_hip_render_png(self._h, w, h, vp_, n, C.byref(p), C.byref(sz)))
+        return _take_bytes(p, sz)
+
     def render_rows_device(self, w, h, y0, y1, d_rgb8=0, d_rgb64=0, stream=0):
         _check(lib().maray_hip_render_rows_device(self._h, w, h, y0, y1, d_rgb8 or None, d_rgb64 or None, stream or None))
 
@@ -561,13 +574,42 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     return img
 
 
-def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0, filter=FILTER_BOX):
+def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0, filter=FILTER_BOX,
+        encoder=ENCODER_HOST):
     """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
-    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; as gen_to_image)."""
+    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; as gen_to_image).  encoder=ENCODER_DEVICE: the PNG's
+    zlib stream is built on the devices and no raster crosses to the host (include/maray_hip.h, "device PNG encoder")."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
-    go.backend, go.n_devices, go.samples, go.shutter, go.filter = backend, n_devices, samples, shutter, filter
+    go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.encoder = backend, n_devices, samples, shutter, filter, encoder
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
+
+
+def _take_bytes(p, sz):
+    try:
+        return C.string_at(p, sz.value)
+    finally:
+        lib().maray_free(p)
+
+
+def png_encode_device(d_ptr, w, h, device=0, stream=0):
+    """A packed (h, w, 3) uint8 raster in device memory (any alignment) -> the bytes of a PNG, encoded on the device
+    (maray_hip_png_encode_device); enqueued on `stream` and waited for."""
+    p, sz = C.c_void_p(), C.c_size_t()
+    _check(lib().maray_hip_png_encode_device(device, d_ptr or None, w, h, stream or None, C.byref(p), C.byref(sz)))
+    return _take_bytes(p, sz)
+
+
+def time_png_encode(d_ptr, w, h, device=0, reps=10):
+    """(average ms of the encoder's three kernels over the raster as one band, bytes of the stream they make)."""
+    ms, nb = C.c_float(), C.c_uint64()
+    _check(lib().maray_hip_time_png_encode(device, d_ptr or None, w, h, reps, C.byref(ms), C.byref(nb)))
+    return ms.value, nb.value
+
+
+def png_bytes_to_host():
+    """Bytes the device encoders of this process have copied to the host so far."""
+    return lib().maray_hip_png_bytes_to_host()
 
 
 def time_filter(w, rows, k, device=0, reps=10):

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
@@ -19,6 +20,7 @@
 #include "filter.hpp"
 #include "lower.hpp"
 #include "maray_hip.h"
+#include "png_device.hpp"
 #include "shutter.hpp"
 
 using namespace maray;
@@ -89,6 +91,10 @@ int guard(F f)
 }
 
 #define REQUIRE(c, what) do { if (!(c)) throw Error{MARAY_E_ARG, what}; } while (0)
+
+// The device of every live context: what maray_hip_render_png takes its encoder for (a Backend does not say where it lives)
+std::mutex g_ctx_device_mutex;
+std::map<const maray_ctx *, int> &g_ctx_device = *new std::map<const maray_ctx *, int>();
 
 }   // namespace
 
@@ -654,6 +660,7 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         c->samples = k;             // (a tent context too takes output geometry, RGB8 only, k w and k h within the domain)
         if (prog->n_params) c->param_ranges.assign(prog->param_ranges, prog->param_ranges + 2 * (size_t)prog->n_params);
         for (uint32_t p = 0; p < prog->n_params; p++) c->params_ready = c->params_ready && param_value_ok(c->param_ranges.data(), p, NAN);
+        { std::lock_guard<std::mutex> lk(g_ctx_device_mutex); g_ctx_device[c] = device; }
         *out = c;
     });
 }
@@ -683,6 +690,7 @@ int maray_hip_ctx_set_params(maray_ctx *c, const double *values, uint32_t n)
 void maray_hip_ctx_free(maray_ctx *c)
 {
     if (!c) return;
+    { std::lock_guard<std::mutex> lk(g_ctx_device_mutex); g_ctx_device.erase(c); }
     delete c->backend;
     delete c;
 }
@@ -813,6 +821,70 @@ int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int
         *ms_avg = filter_time_tent(device, w, rows, k, reps);
     });
 }
+
+// ---- device PNG encoder (include/maray_hip.h) ----------------------------------------------------------------
+static void png_hand_over(const std::vector<uint8_t> &file, uint8_t **png_out, size_t *n_out)
+{
+    uint8_t *p = (uint8_t *)malloc(file.size() ? file.size() : 1);
+    if (!p) throw Error{MARAY_E_INTERNAL, "out of memory"};
+    memcpy(p, file.data(), file.size());
+    *png_out = p; *n_out = file.size();
+}
+
+int maray_hip_png_encode_device(int device, const void *d_rgb8, uint32_t w, uint32_t h, void *stream, uint8_t **png_out, size_t *n_out)
+{
+    return guard([&] {
+        REQUIRE(png_out && n_out, "null argument");
+        *png_out = nullptr; *n_out = 0;
+        REQUIRE(d_rgb8, "null argument");
+        REQUIRE(w && h, "empty image");
+        png_check_size(w, h);
+        PngEncoderLease E(device);
+        PngPiece piece;
+        piece.y0 = 0; piece.y1 = h;
+        E->encode_rows((const unsigned char *)d_rgb8, w, h, (hipStream_t)stream, piece);
+        png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
+    });
+}
+
+int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint8_t **png_out, size_t *n_out)
+{
+    return guard([&] {
+        REQUIRE(png_out && n_out, "null argument");
+        *png_out = nullptr; *n_out = 0;
+        REQUIRE(c && c->backend, "null context");
+        REQUIRE(w && h, "empty image");
+        check_rows(w, h, 0, h);
+        png_check_size(w, h);
+        check_samples(c, w, h, false, values != nullptr);
+        if (values) check_shutter(c, values, n_frames);
+        int device = 0;
+        {
+            std::lock_guard<std::mutex> lk(g_ctx_device_mutex);
+            auto it = g_ctx_device.find(c);
+            if (it == g_ctx_device.end()) throw Error{MARAY_E_ARG, "unknown context"};
+            device = it->second;
+        }
+        PngEncoderLease E(device);
+        PngPiece piece;
+        piece.y0 = 0; piece.y1 = h;
+        E->encode_rendered(w, 0, h, E->own_stream, [&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
+            if (values) c->backend->render_device_shutter(w, h, RowBlocks::range(b0, b1), values, n_frames, d8, st);
+            else c->backend->render_device(w, h, RowBlocks::range(b0, b1), d8, nullptr, st);
+        }, piece);
+        png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
+    });
+}
+
+int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32_t h, int reps, float *ms_avg, uint64_t *stream_bytes)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        *ms_avg = png_time_kernels(device, (const unsigned char *)d_rgb8, w, h, reps, stream_bytes);
+    });
+}
+
+uint64_t maray_hip_png_bytes_to_host(void) { return png_bytes_to_host(); }
 
 int maray_host_alloc(size_t bytes, void **out)
 {

@@ -4,7 +4,8 @@
 // pixels), -p NAME=VALUE[:LO:HI] (a scene parameter:
 // the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
 // the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
-// image the mean of N frames whose NAME covers SPAN around its value, averaged on the device).  -c/--cpus is parsed and
+// image the mean of N frames whose NAME covers SPAN around its value, averaged on the device), --encoder {host,device} (who
+// writes the PNG: the host's zlib, or the device encoder, per --animate frame too).  -c/--cpus is parsed and
 // ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cmath>
 #include <cstdio>
@@ -34,7 +35,9 @@ static void usage()
             "                               conversion (`frame%%03d.png`), numbered from 0\n"
             "      --shutter <name=span>    Motion blur (repeatable): every image is the mean of N frames in which `name` covers\n"
             "                               an interval of width span centred on its value; declares `name` if -p did not\n"
-            "      --shutter-samples <n>    N = 1, 2, 4, 8, 16, 32 or 64 (default: 8 once a --shutter is given)\n");
+            "      --shutter-samples <n>    N = 1, 2, 4, 8, 16, 32 or 64 (default: 8 once a --shutter is given)\n"
+            "      --encoder <e>            host | device (default: host); device builds the PNG's compressed stream on the GPU,\n"
+            "                               so that no raster crosses to the host (same pixels, other file bytes)\n");
 }
 
 namespace {
@@ -108,6 +111,12 @@ int main(int argc, char **argv)
             if (f == "box") go.filter = MARAY_FILTER_BOX;
             else if (f == "tent") go.filter = MARAY_FILTER_TENT;
             else { fprintf(stderr, "Error: --filter takes box or tent, not `%s`\n", f.c_str()); usage(); return 2; }
+        }
+        else if (a == "--encoder") {
+            const std::string e = val();
+            if (e == "host") go.encoder = MARAY_ENCODER_HOST;
+            else if (e == "device") go.encoder = MARAY_ENCODER_DEVICE;
+            else { fprintf(stderr, "Error: --encoder takes host or device, not `%s`\n", e.c_str()); usage(); return 2; }
         }
         else if (a == "-p" || a == "--param") {
             Param p; std::vector<double> n;

@@ -12,6 +12,7 @@
 // device writes its rows by DMA (host_pipe.hpp); the progress callback runs on the calling thread,
 // like the reference's collector loop (src/render.rs:63-82).
 #include <chrono>
+#include <algorithm>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -28,6 +29,7 @@
 #include "host_pipe.hpp"
 #include "lower.hpp"
 #include "maray_hip.h"
+#include "png_device.hpp"
 
 using namespace maray;
 
@@ -80,6 +82,13 @@ struct ScopedPin {
 };
 
 int fail_with(int code, const std::string &m) { set_last_error(m); return code; }
+
+// maray_gen_opts.encoder = MARAY_ENCODER_DEVICE: what the workers hand over instead of rows in a raster -- per tile the
+// compressed segments of its rows and their Adler part (png_device.hpp), in whatever order the tiles finish
+struct PngCollect {
+    std::mutex m;
+    std::vector<std::unique_ptr<PngPiece>> pieces;
+};
 
 // ---- what the façade remembers between calls ------------------------------------------------------------------------
 // gen_to_image is called once per image (src/lib.rs:1177-1195), an animation calls it in a loop (examples/test*.rs), and
@@ -216,12 +225,15 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
     return MARAY_OK;
 }
 
-extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
-                                  const maray_gen_opts *opts, maray_report report, maray_report_fn fn, void *user,
-                                  uint8_t *rgb8, uint32_t w, uint32_t h)
+// gen_to_image; with `png` the tiles are rendered into each worker's encoder on its device and encoded there (rgb8 is null:
+// no raster crosses to the host), else they land in rgb8
+static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
+                   const maray_gen_opts *opts, maray_report report, maray_report_fn fn, void *user,
+                   uint8_t *rgb8, uint32_t w, uint32_t h, PngCollect *png)
 {
-    if (!s || !rgb8) return fail_with(MARAY_E_ARG, "null argument");
+    if (!s || (!rgb8 && !png)) return fail_with(MARAY_E_ARG, "null argument");
     return gen_guard([&]() -> int {
+    if (opts && opts->encoder != MARAY_ENCODER_HOST && opts->encoder != MARAY_ENCODER_DEVICE) return fail_with(MARAY_E_ARG, "unknown encoder");
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
     // supersampling (include/maray_hip.h): the program is the scene on a k x k finer grid, its contexts reduce it
     const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
@@ -292,7 +304,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     if (!entry) {
         std::vector<std::thread> warm;
         struct Joiner { std::vector<std::thread> &v; ~Joiner() { for (auto &t : v) if (t.joinable()) t.join(); } } joiner{warm};
-        if (n_dev_avail > 0) {
+        if (n_dev_avail > 0 && !png) {
             warm.emplace_back([&] { pin.pin(rgb8, (size_t)w * h * 3); });
             for (uint32_t d = 0; d < n_dev; d++)
                 warm.emplace_back(host_pipe_prewarm, device_of(d), w, std::min(tile_rows, h), (int)std::min<size_t>(3, share[d].size() / 2));
@@ -310,7 +322,7 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         auto fresh = std::make_shared<GenEntry>();
         fresh->key = key; fresh->tape = tape; fresh->samples = samples; fresh->filter = filter;
         entry = gen_cache_insert(fresh);
-    } else pin.pin(rgb8, (size_t)w * h * 3);
+    } else if (!png) pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
     maray_tape_program(entry->tape, &prog);
     // The scene's current parameter values: the program was found by its name (declarations in, values out), so a frame
@@ -364,11 +376,31 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
         maray_ctx *ctx = kept.ctx;
         int r = ctx ? MARAY_OK : maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx);
         if (!r && !param_values.empty()) r = maray_hip_ctx_set_params(ctx, param_values.data(), (uint32_t)param_values.size());
-        if (!r && !share[d].empty())
+        std::string thrown;
+        if (!r && !share[d].empty() && png) {
+            // device encoder: every tile through the existing device entry points into the encoder's band buffer, encoded there
+            try {
+                PngEncoderLease E(dev);
+                for (size_t t = 0; t + 1 < share[d].size(); t += 2) {
+                    std::unique_ptr<PngPiece> piece(new PngPiece());
+                    piece->y0 = share[d][t]; piece->y1 = share[d][t + 1];
+                    E->encode_rendered(w, piece->y0, piece->y1, E->own_stream, [&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
+                        const int rr = shutter_values.empty() ? maray_hip_render_rows_device(ctx, w, h, b0, b1, d8, nullptr, st)
+                                                              : maray_hip_render_rows_shutter_device(ctx, w, h, b0, b1, shutter_values.data(), shutter, d8, st);
+                        if (rr) throw Error{rr, maray_last_error()};
+                    }, *piece);
+                    const uint32_t y0 = piece->y0, y1 = piece->y1;
+                    { std::lock_guard<std::mutex> lk(png->m); png->pieces.push_back(std::move(piece)); }
+                    on_tile(&tu, y0, y1);
+                }
+            }
+            catch (const Error &e) { r = e.code; thrown = e.msg; }
+            catch (const std::exception &e) { r = MARAY_E_INTERNAL; thrown = e.what(); }
+        } else if (!r && !share[d].empty())
             r = shutter_values.empty() ? maray_hip_render_tiles(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), rgb8, on_tile, &tu)
                                        : maray_hip_render_tiles_shutter(ctx, w, h, share[d].data(), (uint32_t)(share[d].size() / 2), shutter_values.data(),
                                                                         shutter, rgb8, on_tile, &tu);
-        const std::string msg = r ? maray_last_error() : "";      // this thread's message, re-raised on the calling thread
+        const std::string msg = !thrown.empty() ? thrown : r ? maray_last_error() : "";      // this thread's message, re-raised on the calling thread
         if (r) maray_hip_ctx_free(ctx);                           // (a context that failed is not kept)
         else gen_cache_give(*entry, dev, ctx, kept.ctx ? kept.hint_mpixels : co.hint_mpixels);      // (what it was CHOSEN for)
         std::lock_guard<std::mutex> lk(P.m);
@@ -400,6 +432,14 @@ extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex
     });
 }
 
+extern "C" int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
+                                  const maray_gen_opts *opts, maray_report report, maray_report_fn fn, void *user,
+                                  uint8_t *rgb8, uint32_t w, uint32_t h)
+{
+    if (!s || !rgb8) return fail_with(MARAY_E_ARG, "null argument");
+    return gen_run(s, tex, n_tex, opts, report, fn, user, rgb8, w, h, nullptr);      // (the encoder word is checked, nothing more)
+}
+
 namespace {
 struct GenUser { std::string path; };
 void gen_report(void *user, uint8_t *rgb8, uint32_t w, uint32_t h, double progress)
@@ -408,6 +448,11 @@ void gen_report(void *user, uint8_t *rgb8, uint32_t w, uint32_t h, double progre
     fprintf(stderr, "%.2f %%\n", 100.0 * progress);   // src/lib.rs:1205
     fflush(stderr);
     maray_png_write(g->path.c_str(), rgb8, w, h);     // partial image re-saved (:1207)
+}
+void gen_report_device(void *, uint8_t *, uint32_t, uint32_t, double progress)
+{
+    fprintf(stderr, "%.2f %%\n", 100.0 * progress);   // the percentage as ever; there is no host raster to re-save
+    fflush(stderr);
 }
 }   // namespace
 
@@ -419,6 +464,24 @@ extern "C" int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_
     uint32_t w = 0, h = 0;
     maray_scene_size(s, &w, &h);
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
+    if (opts && opts->encoder == MARAY_ENCODER_DEVICE) {
+        if (!w || !h) return fail_with(MARAY_E_ARG, "empty image");
+        png_check_size(w, h);
+        PngCollect col;
+        if (const int rc = gen_run(s, tex, n_tex, opts, report, gen_report_device, nullptr, nullptr, w, h, &col)) return rc;
+        // the calling thread assembles the file in row order: segments are independent, so it is the single-device file
+        std::sort(col.pieces.begin(), col.pieces.end(), [](const std::unique_ptr<PngPiece> &a, const std::unique_ptr<PngPiece> &b) { return a->y0 < b->y0; });
+        std::vector<const PngPiece *> order;
+        for (auto &p : col.pieces) order.push_back(p.get());
+        const std::vector<uint8_t> out = png_assemble(w, h, order);
+        FILE *f = fopen(png_path, "wb");
+        if (!f) return fail_with(MARAY_E_IO, std::string("cannot create ") + png_path);
+        const size_t n = fwrite(out.data(), 1, out.size(), f);
+        fclose(f);
+        if (n != out.size()) return fail_with(MARAY_E_IO, "short write");
+        set_last_error("");
+        return MARAY_OK;
+    }
     const size_t bytes = (size_t)w * h * 3;
     // RgbImage::new (:1210) -- in pinned memory, so that the devices write it by DMA; zeroed like the reference's
     struct Raster {

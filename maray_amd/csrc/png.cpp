@@ -24,28 +24,13 @@
 
 #include "backend.hpp"
 #include "maray_hip.h"
+#include "png_container.hpp"
 
 using namespace maray;
 
 namespace {
 
-void put_be32(std::vector<uint8_t> &v, uint32_t x) { v.push_back(x >> 24); v.push_back(x >> 16); v.push_back(x >> 8); v.push_back(x); }
-
-void chunk(std::vector<uint8_t> &out, const char *type, const uint8_t *data, size_t n)
-{
-    put_be32(out, (uint32_t)n);
-    size_t start = out.size();
-    out.insert(out.end(), type, type + 4);
-    if (n) out.insert(out.end(), data, data + n);
-    uint32_t crc = (uint32_t)crc32(0L, out.data() + start, (uInt)(n + 4));
-    put_be32(out, crc);
-}
-
 uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-// Raster sizes this library will read or write: 2^20 pixels a side (the evaluators' own limit,
-// MARAY_DOMAIN_MAX) and 16 GiB of filtered scanlines.  A crafted IHDR beyond that is rejected, not allocated.
-const uint64_t MARAY_PNG_MAX_BYTES = 1ull << 34;
 
 template <typename F>
 int png_guard(F f)
@@ -82,16 +67,7 @@ extern "C" int maray_png_write(const char *path, const uint8_t *rgb8, uint32_t w
     uLongf zn = compressBound((uLong)raw.size());
     std::vector<uint8_t> z(zn);
     if (compress2(z.data(), &zn, raw.data(), (uLong)raw.size(), 6) != Z_OK) { set_last_error("zlib compress failed"); return MARAY_E_INTERNAL; }
-    std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    std::vector<uint8_t> ihdr;
-    put_be32(ihdr, w); put_be32(ihdr, h);
-    ihdr.push_back(8); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);   // 8-bit, truecolour
-    chunk(out, "IHDR", ihdr.data(), ihdr.size());
-    for (size_t off = 0; off < zn || off == 0; off += (size_t)1 << 30) {          // a chunk's length field holds 31 bits
-        chunk(out, "IDAT", z.data() + off, std::min<size_t>((size_t)1 << 30, zn - off));
-        if (zn == 0) break;
-    }
-    chunk(out, "IEND", nullptr, 0);
+    const std::vector<uint8_t> out = png_file(w, h, z.data(), zn);
     FILE *f = fopen(path, "wb");
     if (!f) { set_last_error(std::string("cannot create ") + path); return MARAY_E_IO; }
     size_t n = fwrite(out.data(), 1, out.size(), f);

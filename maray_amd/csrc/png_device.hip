@@ -1,0 +1,324 @@
+// png_device.hip — the kernels of the device PNG encoder (product code; include/maray_hip.h, "device PNG encoder").
+//
+//   maray_png_compress  one wavefront per segment (PNG_SEG pixels of one row), four segments per block.  In steps of 64
+//                       pixels: a lane loads its pixel (the aligned dwords that hold its three bytes, shifted into place),
+//                       compares all three channels with the pixel before it (lane 0: the last pixel of the step before;
+//                       a segment's first pixel is always a literal), __ballot gives the run mask, and every literal pixel
+//                       and the first lane of every run makes one token: three fixed-Huffman literals (24 .. 27 bits) or a
+//                       match of distance 3 over the run (length code, extra bits, distance code 2: 12 .. 18 bits).  A
+//                       run ends with its step, so a match is at most 192 bytes.  An exclusive scan of the tokens' bit
+//                       lengths gives every lane its place; lanes OR their bits into the wavefront's staging buffer in LDS
+//                       (ds_or_b32, one or two dwords each), which holds the whole segment and goes to the segment's slot
+//                       with coalesced dword stores at the end.  The same lanes sum the segment's Adler terms.
+//   maray_png_scan      one block: the segments' byte lengths summed in groups of 64, the groups' places in the stream (an
+//                       exclusive scan), and the sum of the segments' Adler shares, which is the band's Adler part.
+//   maray_png_gather    one wavefront per segment: its place (the group's plus the lengths before it in the group), and
+//                       its bytes from the slot to that place in the contiguous stream, in
+//                       dwords aligned to the destination (v_alignbyte_b32 on the source), bytes at the two ends.
+// No device-wide counter, no inline assembly, no scratch memory.  LDS: 4 x 896 bytes per block of maray_png_compress.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "png_device.hpp"
+
+namespace maray {
+
+namespace {
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            throw Error{MARAY_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)};           \
+    } while (0)
+
+constexpr int PC_WAVES = 4, PC_BLOCK = 64 * PC_WAVES;
+constexpr int STAGE_DW = PNG_SLOT_MAX / 4;            // dwords of a wavefront's staging buffer: a whole slot
+constexpr int SCAN_BLOCK = 1024;
+constexpr uint32_t SCAN_BATCH = 16;                   // groups whose loads the scan kernel keeps in flight together
+
+// bytes of segment s of a row of w pixels: its pixels and, in the row's first segment, the filter byte
+__device__ __forceinline__ uint32_t seg_pixels(uint32_t w, uint32_t s) { return min(PNG_SEG, w - s * PNG_SEG); }
+
+// the fixed-Huffman code of literal v, bit-reversed for the LSB-first stream; *nb = its length
+__device__ __forceinline__ uint32_t literal(uint32_t v, uint32_t *nb)
+{
+    const bool lo = v < 144u;
+    *nb = lo ? 8u : 9u;
+    return lo ? __brev(0x30u + v) >> 24 : __brev(0x190u + (v - 144u)) >> 23;
+}
+
+// a match of `len` bytes (3 .. 258) at distance 3: reversed length code, extra bits as they are, reversed distance code 2
+__device__ __forceinline__ uint32_t match3(uint32_t len, uint32_t *nb)
+{
+    const uint32_t l = len - 3u;
+    uint32_t code, eb, extra;
+    if (len == 258u) { code = 285u; eb = 0u; extra = 0u; }
+    else if (l < 8u) { code = 257u + l; eb = 0u; extra = 0u; }
+    else {
+        eb = 29u - (uint32_t)__clz((int)l);                 // floor(log2 l) - 2: 1 .. 5
+        code = 261u + 4u * eb + ((l >> eb) & 3u);
+        extra = l & ((1u << eb) - 1u);
+    }
+    uint32_t hb, hc;
+    if (code < 280u) { hb = 7u; hc = __brev(code - 256u) >> 25; }
+    else { hb = 8u; hc = __brev(0xC0u + (code - 280u)) >> 24; }
+    *nb = hb + eb + 5u;
+    return hc | (extra << hb) | (8u << (hb + eb));          // 00010 reversed = 01000
+}
+
+__device__ __forceinline__ void or_bits(uint32_t *stage, uint32_t bit, uint32_t value)
+{
+    const uint32_t d = bit >> 5, sh = bit & 31u;
+    const uint64_t v = (uint64_t)value << sh;
+    if (d < (uint32_t)STAGE_DW) atomicOr(&stage[d], (uint32_t)v);
+    if ((uint32_t)(v >> 32) && d + 1u < (uint32_t)STAGE_DW) atomicOr(&stage[d + 1u], (uint32_t)(v >> 32));
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress(const PngBandArgs a)
+{
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t *stage = stage_all + wave * STAGE_DW;
+    for (uint32_t i = lane; i < (uint32_t)STAGE_DW; i += 64u) stage[i] = 0u;
+    __syncthreads();
+    const uint32_t seg = blockIdx.x * PC_WAVES + wave;
+    const bool active = seg < a.n_segs;                     // (wave-uniform; nobody leaves before the second barrier)
+    uint32_t seg_len = 0u;
+    if (active) {
+        const uint32_t row = seg / a.nseg, s = seg - row * a.nseg;
+        const uint32_t npix = seg_pixels(a.w, s), first = s == 0u ? 1u : 0u;
+        const uint32_t n = 3u * npix + first;               // the segment's filtered bytes
+        const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
+        // block header BFINAL = 0, BTYPE = 01 (the bits 0, 1, 0), then in a row's first segment the filter byte 0 as a literal
+        uint32_t bitpos = 3u;
+        if (lane == 0u) {
+            or_bits(stage, 0u, 2u);
+            if (first) { uint32_t nb; const uint32_t c = literal(0u, &nb); or_bits(stage, 3u, c); }
+        }
+        if (first) bitpos += 8u;
+        uint32_t sum_a = 0u, sum_b = 0u, last = 0u;
+        for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
+            const uint32_t px = p0 + lane;
+            const bool valid = px < npix;
+            uint32_t pix = 0u;
+            if (valid) {
+                // the three bytes at src + 3 px from the aligned dwords that hold them (every dword read holds one of them)
+                const unsigned char *p = src + (size_t)px * 3;
+                const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+                const uint32_t *q = (const uint32_t *)(p - mis);
+                const uint32_t d0 = q[0], d1 = mis >= 2u ? q[1] : 0u;
+                pix = __builtin_amdgcn_alignbyte(d1, d0, mis) & 0xFFFFFFu;
+            }
+            uint32_t prev = (uint32_t)__shfl_up((int)pix, 1);
+            if (lane == 0u) prev = last;
+            const bool eq = valid && px != 0u && pix == prev;
+            const uint64_t m = __ballot(eq);
+            last = (uint32_t)__shfl((int)pix, 63);          // (only a full step is followed by another)
+            uint32_t tok = 0u, nb = 0u;
+            if (valid && !eq) {
+                uint32_t n0, n1, n2;
+                const uint32_t c0 = literal(pix & 255u, &n0), c1 = literal((pix >> 8) & 255u, &n1), c2 = literal(pix >> 16, &n2);
+                tok = c0 | (c1 << n0) | (c2 << (n0 + n1));
+                nb = n0 + n1 + n2;
+            } else if (eq && (lane == 0u || !((m >> (lane - 1u)) & 1ull))) {
+                const uint64_t rest = ~(m >> lane);         // (the shift fills with zeros: a one ends the run at 64 - lane at the latest)
+                const uint32_t run = rest ? (uint32_t)__ffsll((long long)rest) - 1u : 64u;
+                tok = match3(3u * run, &nb);
+            }
+            if (valid) {
+                // Adler terms: byte i of the segment weighs n - i
+                const uint32_t wgt = n - (first + 3u * px);
+                const uint32_t r = pix & 255u, g = (pix >> 8) & 255u, b = pix >> 16;
+                sum_a += r + g + b;
+                sum_b += wgt * r + (wgt - 1u) * g + (wgt - 2u) * b;
+            }
+            // exclusive scan of the bit lengths
+            uint32_t inc = nb;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t t = (uint32_t)__shfl_up((int)inc, d);
+                if (lane >= (uint32_t)d) inc += t;
+            }
+            if (nb) or_bits(stage, bitpos + inc - nb, tok);
+            bitpos += (uint32_t)__shfl((int)inc, 63);
+        }
+        // end-of-block (seven zero bits), the empty stored block (three zero bits, zeros to the byte), 00 00 FF FF
+        const uint32_t at = (bitpos + 7u + 3u + 7u) >> 3;
+        if (lane == 0u) or_bits(stage, 8u * (at + 2u), 0xFFFFu);
+        seg_len = at + 4u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            sum_a += (uint32_t)__shfl_xor((int)sum_a, d);
+            sum_b += (uint32_t)__shfl_xor((int)sum_b, d);
+        }
+        if (lane == 0u) {
+            // The segment's share of the band's Adler part: A, and B + A x (the band's bytes after this segment) -- a byte that
+            // weighs n - i in its segment weighs that many more in the band -- both modulo 65521 (a band has at most 2^30
+            // filtered bytes; residues' products stay below 2^32).  Shares add up in any order.
+            const uint32_t row_bytes = 3u * a.w + 1u;
+            const uint32_t after = (a.rows - 1u - row) * row_bytes + (row_bytes - (1u + 3u * (s * PNG_SEG + npix)));
+            const uint32_t ra = sum_a % PNG_ADLER_MOD;
+            a.lens[seg] = seg_len;
+            a.adler[2 * (size_t)seg] = ra;
+            a.adler[2 * (size_t)seg + 1] = (sum_b % PNG_ADLER_MOD + ra * (after % PNG_ADLER_MOD)) % PNG_ADLER_MOD;
+        }
+    }
+    __syncthreads();
+    if (active) {
+        uint32_t *slot = (uint32_t *)(a.slots + (size_t)seg * a.slot_bytes);
+        const uint32_t ndw = min((seg_len + 3u) >> 2, min(a.slot_bytes >> 2, (uint32_t)STAGE_DW));
+        for (uint32_t i = lane; i < ndw; i += 64u) slot[i] = stage[i];
+    }
+}
+
+// segments per group of the scan: a multiple of 64 that makes at most SCAN_BLOCK groups
+__host__ __device__ inline uint32_t scan_group(uint32_t n_segs) { return 64u * ((n_segs + 64u * SCAN_BLOCK - 1u) / (64u * SCAN_BLOCK)); }
+
+// x modulo 65521 without a 64-bit division (a bit-serial loop on this target): 2^32 = 225 modulo 65521
+__device__ __forceinline__ uint32_t mod_adler(uint64_t x)
+{
+    const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
+    return ((hi % PNG_ADLER_MOD) * 225u + lo % PNG_ADLER_MOD) % PNG_ADLER_MOD;
+}
+
+// One block of 16 wavefronts.  The segments are taken in groups of G (64 for up to 65,536 segments): wavefront v sums the
+// lengths of the groups 64 v .. 64 v + 63, one coalesced load and one wavefront reduction per 64 segments, independent from
+// group to group, and lane i keeps group 64 v + i's sum.  An exclusive scan of the at most 1024 sums (wavefront scans, the 16
+// totals through LDS) gives every group its place in the stream (offsets[g]); the gather kernel adds the lengths in front
+// of a segment inside its group itself.  All lanes also add up the segments' Adler shares (plain sums: the compress kernel
+// has put every segment's place in the band into its share).
+__global__ __launch_bounds__(SCAN_BLOCK) void maray_png_scan(const PngBandArgs a)
+{
+    constexpr uint32_t WAVES = SCAN_BLOCK / 64;
+    __shared__ uint64_t w_len[WAVES], w_a[WAVES], w_b[WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t G = scan_group(a.n_segs), n_groups = (a.n_segs + G - 1u) / G;
+    uint64_t mine = 0, sa = 0, sb = 0;                 // (shares are below 65521: 2^31 of them fit)
+    for (uint32_t i0 = 0; i0 < 64u; i0 += SCAN_BATCH) { // SCAN_BATCH groups at a time, their loads in flight together
+        uint64_t x[SCAN_BATCH];
+        uint32_t ya[SCAN_BATCH], yb[SCAN_BATCH];
+#pragma unroll
+        for (uint32_t u = 0; u < SCAN_BATCH; u++) {     // unconditional loads at a clamped index: no branch, no wait between them
+            const uint64_t j = (uint64_t)(wave * 64u + i0 + u) * G + lane;
+            const uint64_t jj = j < a.n_segs ? j : a.n_segs - 1u;
+            x[u] = a.lens[jj]; ya[u] = a.adler[2 * jj]; yb[u] = a.adler[2 * jj + 1];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < SCAN_BATCH; u++) {     // the first 64 segments of each group
+            const bool in = (uint64_t)(wave * 64u + i0 + u) * G + lane < a.n_segs;
+            x[u] = in ? x[u] : 0u;
+            sa += in ? ya[u] : 0u;
+            sb += in ? yb[u] : 0u;
+        }
+        if (G > 64u) {                                  // bands of more than 65,536 segments: the rest of each group
+            for (uint32_t u = 0; u < SCAN_BATCH; u++) {
+                const uint64_t j0 = (uint64_t)(wave * 64u + i0 + u) * G, j1 = j0 + G < a.n_segs ? j0 + G : a.n_segs;
+                for (uint64_t j = j0 + 64u + lane; j < j1; j += 64) {
+                    x[u] += a.lens[j];
+                    sa += a.adler[2 * j];
+                    sb += a.adler[2 * j + 1];
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < SCAN_BATCH; u++) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) x[u] += __shfl_xor(x[u], d);
+            if (lane == i0 + u) mine = x[u];
+        }
+    }
+    uint64_t inc = mine;                                // inclusive scan of the wavefront's 64 group sums
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up(inc, d);
+        if (lane >= (uint32_t)d) inc += t;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        sa += __shfl_xor(sa, d);
+        sb += __shfl_xor(sb, d);
+    }
+    if (lane == 63u) w_len[wave] = inc;
+    if (lane == 0u) { w_a[wave] = sa; w_b[wave] = sb; }
+    __syncthreads();
+    uint64_t base = 0;
+    for (uint32_t v = 0; v < wave; v++) base += w_len[v];
+    const uint32_t g = wave * 64u + lane;
+    if (g < n_groups) a.offsets[g] = base + inc - mine;
+    if (threadIdx.x == 0) {
+        uint64_t tl = 0;
+        uint32_t ta = 0, tb = 0;
+        for (uint32_t v = 0; v < WAVES; v++) { tl += w_len[v]; ta += mod_adler(w_a[v]); tb += mod_adler(w_b[v]); }
+        const uint32_t n = (a.rows * (3u * a.w + 1u)) % PNG_ADLER_MOD;       // (a band has at most 2^30 filtered bytes)
+        a.totals[0] = tl;
+        a.totals[1] = (uint64_t)n | ((uint64_t)(ta % PNG_ADLER_MOD) << 32);
+        a.totals[2] = tb % PNG_ADLER_MOD;
+    }
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_gather(const PngBandArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t seg = blockIdx.x * PC_WAVES + (threadIdx.x >> 6);
+    if (seg >= a.n_segs) return;
+    // where the segment starts: its group's place plus the lengths in front of it inside the group
+    const uint32_t G = scan_group(a.n_segs), g = seg / G;
+    uint32_t before = 0;
+    for (uint64_t j = (uint64_t)g * G + lane; j < seg; j += 64) before += a.lens[j];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += (uint32_t)__shfl_xor((int)before, d);
+    const uint32_t len = min(a.lens[seg], a.slot_bytes);
+    const unsigned char *src = a.slots + (size_t)seg * a.slot_bytes;
+    unsigned char *dst = a.stream + (a.offsets[g] + before);
+    const uint32_t head = min(len, (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u);
+    if (lane < head) dst[lane] = src[lane];
+    const uint32_t nd = (len - head) >> 2, r = head & 3u;
+    const uint32_t *s32 = (const uint32_t *)src;
+    uint32_t *d32 = (uint32_t *)(dst + head);
+    for (uint32_t k = lane; k < nd; k += 64u) {
+        const uint32_t q = (head + 4u * k) >> 2;            // (with r > 0 dword q + 1 holds byte head + 4 k + 3 < len: inside the slot)
+        const uint32_t lo = s32[q], hi = r ? s32[q + 1u] : 0u;
+        d32[k] = __builtin_amdgcn_alignbyte(hi, lo, r);
+    }
+    const uint32_t t0 = head + 4u * nd;
+    if (lane < len - t0) dst[t0 + lane] = src[t0 + lane];
+}
+
+void check_band(const PngBandArgs &a)
+{
+    if (!a.src || !a.slots || !a.lens || !a.adler || !a.offsets || !a.stream || !a.totals || !a.w || !a.rows ||
+        a.nseg != png_row_segments(a.w) || a.slot_bytes != png_slot_bytes(a.w) || a.slot_bytes > PNG_SLOT_MAX ||
+        (uint64_t)a.rows * a.nseg != a.n_segs || ((uintptr_t)a.slots & 15) ||
+        (uint64_t)a.rows * (3ull * a.w + 1ull) > (1ull << 30))
+        throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad band arguments"};
+}
+
+}   // namespace
+
+void png_band_compress(const PngBandArgs &a, hipStream_t st)
+{
+    check_band(a);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(maray_png_compress, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+}
+
+void png_band_scan(const PngBandArgs &a, hipStream_t st)
+{
+    check_band(a);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(maray_png_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+}
+
+void png_band_gather(const PngBandArgs &a, hipStream_t st)
+{
+    check_band(a);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(maray_png_gather, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+}
+
+}   // namespace maray

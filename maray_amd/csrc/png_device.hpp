@@ -1,0 +1,116 @@
+// png_device.hpp — the device PNG encoder (include/maray_hip.h, "device PNG encoder"): the kernels that turn RGB8 rows in HBM
+// into the segments of a zlib stream (png_device.hip) and the object that owns their scratch, brings the compressed bytes
+// to the host and wraps them in the container (png_device.cpp).  Builds no program's kernels: not part of a code key.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+#include "expr.hpp"
+#include "maray_hip.h"
+
+namespace maray {
+
+constexpr uint32_t PNG_SEG = 256;             // pixels per segment (SEG of the stream contract)
+constexpr uint32_t PNG_ADLER_MOD = 65521;
+
+// A segment of n filtered bytes occupies at most ceil(9 n / 8) + 16 bytes; a slot is that for the image's longest segment,
+// rounded up to 16 (the kernels store and load whole dwords).
+inline uint32_t png_slot_bytes(uint32_t w)
+{
+    const uint32_t n = 3 * (w < PNG_SEG ? w : PNG_SEG) + 1;
+    return ((9 * n + 7) / 8 + 16 + 15) / 16 * 16;
+}
+constexpr uint32_t PNG_SLOT_MAX = ((9 * (3 * PNG_SEG + 1) + 7) / 8 + 16 + 15) / 16 * 16;
+inline uint32_t png_row_segments(uint32_t w) { return (w + PNG_SEG - 1) / PNG_SEG; }
+
+// What a run of segments contributes to the Adler-32, as an element of a monoid: n bytes with A = sum b_i and
+// B = sum (n - i) b_i, all three modulo 65521.  (s1, s2) after the run = (s1 + A, s2 + n s1 + B).
+struct AdlerPart {
+    uint32_t n = 0, a = 0, b = 0;
+    void append(const AdlerPart &r) {        // this run followed by r
+        b = (uint32_t)(((uint64_t)b + (uint64_t)r.n * a + r.b) % PNG_ADLER_MOD);
+        a = (a + r.a) % PNG_ADLER_MOD;
+        n = (n + r.n) % PNG_ADLER_MOD;
+    }
+};
+
+// One band: `rows` rows of w pixels at src (packed RGB8, any alignment), segment j = row j / nseg, pixels
+// (j % nseg) * PNG_SEG ...  All pointers are the encoder's scratch.
+struct PngBandArgs {
+    const unsigned char *src;
+    unsigned char *slots;           // n_segs slots of slot_bytes each, 16-byte aligned
+    uint32_t *lens;                 // per segment: bytes of its slot in use
+    uint32_t *adler;                // per segment: its shares of the band's Adler part, modulo 65521: A, and B + A x (the band's
+                                    // bytes after the segment); the band's part is their sums
+    uint64_t *offsets;              // per group of segments (png_device.hip: 64 or more, at most 1024 groups): where its first
+                                    // segment starts in the gathered stream
+    unsigned char *stream;          // the gathered stream
+    uint64_t *totals;               // [0] = bytes of the stream, [1] = n | a << 32, [2] = b: the band's AdlerPart
+    uint32_t w, rows, nseg, slot_bytes;
+    uint32_t n_segs;                // rows * nseg
+};
+void png_band_compress(const PngBandArgs &a, hipStream_t st);       // maray_png_compress
+void png_band_scan(const PngBandArgs &a, hipStream_t st);           // maray_png_scan
+void png_band_gather(const PngBandArgs &a, hipStream_t st);         // maray_png_gather
+
+// The compressed segments of rows [y0, y1) of an image, on the host, with their Adler part
+struct PngPiece {
+    uint32_t y0 = 0, y1 = 0;
+    std::vector<uint8_t> z;
+    AdlerPart adler;
+};
+
+// Scratch, staging and a stream of one device.  One call at a time; every call waits for its own work before it returns, so
+// the scratch is idle between calls whatever streams they ran on.
+struct PngEncoder {
+    int device = 0;
+    uint32_t band_rows_env = 0;               // MARAY_PNG_BAND_ROWS when the encoder was created (0: the byte budget)
+    size_t band_bytes = (size_t)64 << 20;     // raster bytes of one band
+    hipStream_t own_stream = nullptr;         // for callers that bring none (maray_hip_render_png, gen)
+    unsigned char *slots = nullptr; size_t slots_cap = 0;
+    unsigned char *stream = nullptr; size_t stream_cap = 0;
+    unsigned char *meta = nullptr; size_t meta_cap = 0;         // lens, adler, offsets, totals
+    unsigned char *raster = nullptr; size_t raster_cap = 0;     // a band's rows, for the rendering entry points
+    unsigned char *staging = nullptr; size_t staging_cap = 0;   // pinned host
+    uint64_t *h_totals = nullptr;                                // pinned host, 3 words
+
+    explicit PngEncoder(int dev);
+    ~PngEncoder();
+    PngEncoder(const PngEncoder &) = delete;
+    uint32_t band_rows(uint32_t w) const;
+    // rows x w pixels at d_rgb8 (device memory, any alignment), enqueued on st and waited for; appends to `out`
+    void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out);
+    // rows [y0, y1) band by band: render(b0, b1, d8, st) enqueues the rows' RGB8 into d8 on st
+    void encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,
+                         const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out);
+};
+
+// An encoder of `device`: one an earlier call left, or a new one (MARAY_PNG_BAND_ROWS is read here: a kept encoder made
+// under another value is not handed out).  release() keeps up to two per device for the next call.
+PngEncoder *png_encoder_acquire(int device);
+void png_encoder_release(PngEncoder *e);
+struct PngEncoderLease {
+    PngEncoder *e;
+    explicit PngEncoderLease(int device) : e(png_encoder_acquire(device)) {}
+    ~PngEncoderLease() { png_encoder_release(e); }
+    PngEncoderLease(const PngEncoderLease &) = delete;
+    PngEncoder *operator->() const { return e; }
+};
+
+// bytes the process' encoders have copied to the host so far: payloads and totals (measurements)
+uint64_t png_bytes_to_host();
+// w, h within what the writers take (else Error MARAY_E_LIMIT), before anything is launched
+void png_check_size(uint32_t w, uint32_t h);
+// The file: 78 01, the pieces' segments in row order (they cover [0, h)), the final empty stored block, the Adler-32 combined
+// from the pieces' parts; in the container (png_container.hpp).
+std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces);
+// Average ms of compress + scan + gather over the caller's w x rows raster in device memory, as one band (measurements);
+// *stream_bytes = the bytes of the gathered stream.
+float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes);
+
+}   // namespace maray
