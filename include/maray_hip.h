@@ -197,7 +197,8 @@ typedef struct maray_ctx_opts {
                                when that time is earned back (or when the code object cache already holds them). */
     uint32_t samples;       /* k x k samples per output pixel, k in {0, 1, 2, 4, 8} (0 = 1); see "supersampling" below */
     uint32_t filter;        /* MARAY_FILTER_*: how the k x k samples become pixels; see "reconstruction filter" below */
-    uint32_t reserved[4];
+    uint32_t transfer;      /* MARAY_TRANSFER_* (offset 16): what the reduces (box, tent, shutter) average; see "transfer" below */
+    uint32_t reserved[3];
 } maray_ctx_opts;
 
 /* ---- supersampling (anti-aliasing with an in-kernel box filter) ---------------------------------------------------
@@ -247,6 +248,47 @@ enum { MARAY_FILTER_BOX = 0, MARAY_FILTER_TENT = 1 };
 /* The filter kernel on its own (measurements): average ms of one pass over a w x rows output image (k w x k rows samples in
  * scratch of the call's own, whatever they hold). */
 int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int reps, float *ms_avg);
+
+/* ---- transfer (what the reduces average: encoded bytes, or light) ---------------------------------------------------
+ * The RGB8 a context renders is shown as sRGB, so a mean of bytes is not a mean of light: a one-sample 0 / 255 checker
+ * reduces to 128 where half the light is 188.  `transfer` (maray_ctx_opts.transfer, maray_gen_opts.transfer) is
+ * MARAY_TRANSFER_NONE, the reduces described above and the default, or MARAY_TRANSFER_SRGB: every reduce -- box, tent,
+ * shutter -- decodes its samples to 16-bit linear light, averages those and encodes the mean.  Any other value is MARAY_E_ARG,
+ * reported before a device is looked for.  SRGB is defined by two tables, in integers throughout:
+ *   - decode D[256], uint16: the 256 literals of include/maray_transfer_table.h (D[v] = floor(65535 lin(v / 255) + 0.5) with
+ *     lin(c) = c / 12.92 for c <= 0.04045, else ((c + 0.055) / 1.055)^2.4; the literals are authoritative, not the formula).
+ *     D[0] = 0, D[255] = 65535, strictly increasing, steps of 19 .. 583;
+ *   - thresholds T[v] = (D[v - 1] + D[v] + 1) >> 1 for v = 1 .. 255 (T[0] = 0 in maray_transfer_table's output);
+ *   - encode E(M) = the number of v in 1 .. 255 with T[v] <= M: the byte whose light is nearest to M, the upper one at a tie.
+ *     E(D[v]) = v, so a constant region comes out unchanged.  T steps by at least 19: a 16-wide bin M >> 4 holds at most one
+ *     threshold, which is what the kernels' 4096-entry encode table relies on.
+ * Every reduce under SRGB computes out = E((SUM w_i D[s_i] + W/2) >> log2 W) with the samples s_i, weights w_i, footprints,
+ * clamps and W of its NONE contract: box W = k^2; tent weights t(u) t(v), W = 4 k^4, indices clamped to the image; shutter
+ * W = n.  All sums are integers, the largest the tent's at k = 8: 16384 * 65535 < 2^30, so the picture is the same for every
+ * launch order, band, tile and device split.
+ *   - a shutter call on a filtered SRGB context stays composable: frame i is exactly the RGB8 the context renders, and those
+ *     bytes are decoded, averaged and encoded again;
+ *   - with nothing to reduce (samples 0 or 1, no shutter call) an SRGB context renders exactly the plain bytes;
+ *   - the SRGB reduces are RGB8 only: f64 planes are refused exactly where NONE refuses them (a samples <= 1 context still
+ *     renders them);
+ *   - the output is still plain RGB8: no sRGB / gAMA chunk is written to a PNG, and no other transfer curve exists.
+ * How it runs: an SRGB context is a plain back-end (samples = 1; any of the three, AUTO chooses as ever) of the program behind
+ * the wrapper the tent filter uses (above).  Box: per band one launch of sample rows [k y0, k y1) -- no halo -- and
+ * maray_filter_box_lin<k>; the in-kernel box reduce is not used.  Tent: the band with its halo and maray_filter_tent_lin<k>
+ * (32-bit horizontal sums: they need 24 bits).  Shutter: maray_shutter_reduce_lin per group of 8 frames, with 32-bit partial
+ * sums between groups (64 * 65535 needs 22 bits): the context's shutter scratch is min(n, 8) F + (n > 8 ? 4 F : 0) bytes.
+ * The kernels keep D and the encode table in LDS, filled once per block.  maray_hip_kernel_name is the inner kernel's name +
+ * "+maray_filter_box_lin<k>" / "+maray_filter_tent_lin<k>" (samples <= 1: "+maray_shutter_reduce_lin"). */
+enum { MARAY_TRANSFER_NONE = 0, MARAY_TRANSFER_SRGB = 1 };
+/* The two tables of a transfer; needs no device.  NONE: the identity (decode[v] = thresholds[v] = v); SRGB: D and T as above,
+ * thresholds[0] = 0.  Any other transfer, or a null pointer: MARAY_E_ARG. */
+int maray_transfer_table(uint32_t transfer, uint16_t decode[256], uint16_t thresholds[256]);
+/* maray_hip_time_filter for any reduce kernel: (TENT, NONE) is maray_filter_tent<k>, (BOX, SRGB) maray_filter_box_lin<k>, (TENT,
+ * SRGB) maray_filter_tent_lin<k>; (BOX, NONE) has no kernel of its own (the reduce is inside the pixel kernel): MARAY_E_ARG.
+ * The measurement entry points fill their own sample buffers with one byte value, 0x5A; with MARAY_TIME_RANDOM_BYTES=1 in the
+ * environment (read at each call) with pseudo-random bytes: for the SRGB kernels the best and the worst case of their LDS
+ * tables (every read of a wavefront a broadcast; reads spread over all entries). */
+int maray_hip_time_filter_ex(int device, uint32_t w, uint32_t rows, uint32_t k, uint32_t filter, uint32_t transfer, int reps, float *ms_avg);
 
 int maray_hip_device_count(int *n);
 /* Uploads tape, constants and textures to HBM once. */
@@ -309,6 +351,8 @@ int maray_hip_render_tiles_shutter(maray_ctx *c, uint32_t w, uint32_t h, const u
                                    const double *values, uint32_t n, uint8_t *rgb8_image, maray_tile_fn fn, void *user);
 /* The reduce on its own (measurements): average ms of the passes that reduce n >= 2 frames of `bytes` bytes in HBM. */
 int maray_hip_time_shutter_reduce(int device, size_t bytes, uint32_t n, int reps, float *ms_avg);
+/* The same with a transfer ("transfer" above): SRGB times the passes of maray_shutter_reduce_lin. */
+int maray_hip_time_shutter_reduce_ex(int device, size_t bytes, uint32_t n, uint32_t transfer, int reps, float *ms_avg);
 /* Pinned (page-locked, DMA-able from every device) host memory for output rasters: what backs the `RgbImage` a
  * caller hands to gen_to_image (src/lib.rs:1210) when it wants the PCIe rate.  maray_host_register pins memory the
  * caller already owns (e.g. a Rust Vec<u8>) for the time between the two calls. */
@@ -387,7 +431,7 @@ typedef struct maray_gen_opts {
                                 are kept per (k, filter) */
     uint32_t encoder;        /* MARAY_ENCODER_* (offset 24): who writes maray_gen's PNG; see "device PNG encoder" below.  Any other value:
                                 MARAY_E_ARG.  maray_gen_to_image checks the word and otherwise ignores it */
-    uint32_t reserved[1];
+    uint32_t transfer;       /* MARAY_TRANSFER_* (offset 28; "transfer"): programs and contexts are kept per (k, filter, transfer) */
 } maray_gen_opts;
 enum { MARAY_ENCODER_HOST = 0, MARAY_ENCODER_DEVICE = 1 };
 
@@ -400,7 +444,8 @@ int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t 
  * it in a loop (examples/test*.rs) pays the lowering and the context creation once, not per frame.  This frees them. */
 void maray_gen_cache_clear(void);
 /* What is kept, one line per idle context: "<program key> device <d> kernel <name> hint_mpixels <n>" (NUL-terminated,
- * cut to cap; " samples <k>" follows for k > 1 and " filter tent" after that for MARAY_FILTER_TENT).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
+ * cut to cap; " samples <k>" follows for k > 1, " filter tent" after that for MARAY_FILTER_TENT and " transfer srgb" last for
+ * MARAY_TRANSFER_SRGB).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
  * the call it was chosen for; contexts are kept per physical device. */
 int maray_gen_cache_info(char *out, size_t cap);
 /* gen: render and write a PNG (progress callback prints "%.2f %%" to stderr

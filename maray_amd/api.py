@@ -14,6 +14,7 @@ BACKEND_TAPE, BACKEND_TAPE_SMEM, BACKEND_JIT, BACKEND_AUTO = 0, 1, 2, 3
 REPORT_NONE, REPORT_ROW, REPORT_DURATION_MS = 0, 1, 2
 FILTER_BOX, FILTER_TENT = 0, 1
 ENCODER_HOST, ENCODER_DEVICE = 0, 1
+TRANSFER_NONE, TRANSFER_SRGB = 0, 1
 
 
 class MarayError(RuntimeError):
@@ -48,12 +49,13 @@ class LowerOpts(C.Structure):
 
 
 class CtxOpts(C.Structure):
-    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('samples', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 4)]
+    _fields_ = [('backend', C.c_uint32), ('hint_mpixels', C.c_uint32), ('samples', C.c_uint32), ('filter', C.c_uint32), ('transfer', C.c_uint32),
+                ('reserved', C.c_uint32 * 3)]
 
 
 class GenOpts(C.Structure):
     _fields_ = [('backend', C.c_uint32), ('n_devices', C.c_uint32), ('tile_rows', C.c_uint32), ('samples', C.c_uint32),
-                ('shutter', C.c_uint32), ('filter', C.c_uint32), ('encoder', C.c_uint32), ('reserved', C.c_uint32 * 1)]
+                ('shutter', C.c_uint32), ('filter', C.c_uint32), ('encoder', C.c_uint32), ('transfer', C.c_uint32)]
 
 
 class Report(C.Structure):
@@ -112,6 +114,9 @@ def lib():
         'maray_hip_render_tiles_shutter': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, u32, vp, TILE_FN, vp]),
         'maray_hip_time_shutter_reduce': (C.c_int, [C.c_int, C.c_size_t, u32, C.c_int, C.POINTER(C.c_float)]),
         'maray_hip_time_filter': (C.c_int, [C.c_int, u32, u32, u32, C.c_int, C.POINTER(C.c_float)]),
+        'maray_hip_time_filter_ex': (C.c_int, [C.c_int, u32, u32, u32, u32, u32, C.c_int, C.POINTER(C.c_float)]),
+        'maray_hip_time_shutter_reduce_ex': (C.c_int, [C.c_int, C.c_size_t, u32, u32, C.c_int, C.POINTER(C.c_float)]),
+        'maray_transfer_table': (C.c_int, [u32, vp, vp]),
         'maray_tape_param_count': (C.c_int, [vp, C.POINTER(u32)]),
         'maray_tape_param_range': (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         'maray_hip_ctx_set_params': (C.c_int, [vp, C.POINTER(C.c_double), u32]),
@@ -426,15 +431,17 @@ class Context:
     """Device context: tape + constants + textures resident in HBM.  samples=k > 1: renders the program's raster in k x k
     blocks and writes their means (RGB8 only); every render call then takes output geometry.  filter=FILTER_TENT (needs
     samples 2, 4 or 8): the samples are reduced by a tent filter two pixels wide instead (include/maray_hip.h,
-    "reconstruction filter")."""
+    "reconstruction filter").  transfer=TRANSFER_SRGB: box, tent and shutter average linear light, not bytes ("transfer")."""
 
-    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0, filter=FILTER_BOX):
+    def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0, filter=FILTER_BOX,
+                 transfer=TRANSFER_NONE):
         arr, n, keep = _textures(textures)
         o = CtxOpts()
         o.backend = backend
         o.hint_mpixels = hint_mpixels
         o.samples = samples
         o.filter = filter
+        o.transfer = transfer
         h = C.c_void_p()
         _check(lib().maray_hip_ctx_create(device, C.byref(tape.program), arr, n, C.byref(o), C.byref(h)))
         self._h = h
@@ -546,14 +553,16 @@ class Context:
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,
-                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None, shutter=0, spans=None, filter=FILTER_BOX):
+                 report_kind=REPORT_NONE, report_value=0, out=None, samples=0, params=None, shutter=0, spans=None, filter=FILTER_BOX,
+                 transfer=TRANSFER_NONE):
     """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
     samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling); filter=FILTER_TENT: reduced
     by a tent filter two pixels wide instead of the box (needs samples 2, 4 or 8).
     params={name_or_id: value}: sets these declared parameters of the scene first (Scene.declare_param); the scene's
     program and contexts are found again whatever the values.
     shutter=n, spans={name_or_id: span}: motion blur, the integer mean of n frames whose parameters cover their spans around
-    the values (Scene.shutter_values), averaged on the device; spans are set on the scene first, like params."""
+    the values (Scene.shutter_values), averaged on the device; spans are set on the scene first, like params.
+    transfer=TRANSFER_SRGB: samples and frames are averaged in linear light (include/maray_hip.h, "transfer")."""
     for k, v in (params or {}).items():
         scene.set_param(scene.param_index(k), v)
     for k, v in (spans or {}).items():
@@ -564,6 +573,7 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
     arr, n, keep = _textures(textures)
     go = GenOpts()
     go.backend, go.n_devices, go.tile_rows, go.samples, go.shutter, go.filter = backend, n_devices, tile_rows, samples, shutter, filter
+    go.transfer = transfer
 
     def _cb(user, p, cw, ch, progress):
         if report:
@@ -575,13 +585,15 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
 
 
 def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0, filter=FILTER_BOX,
-        encoder=ENCODER_HOST):
+        encoder=ENCODER_HOST, transfer=TRANSFER_NONE):
     """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
-    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; as gen_to_image).  encoder=ENCODER_DEVICE: the PNG's
+    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; transfer=TRANSFER_SRGB: averaged in linear light; as
+    gen_to_image).  encoder=ENCODER_DEVICE: the PNG's
     zlib stream is built on the devices and no raster crosses to the host (include/maray_hip.h, "device PNG encoder")."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
     go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.encoder = backend, n_devices, samples, shutter, filter, encoder
+    go.transfer = transfer
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
 
 
@@ -612,11 +624,30 @@ def png_bytes_to_host():
     return lib().maray_hip_png_bytes_to_host()
 
 
-def time_filter(w, rows, k, device=0, reps=10):
-    """Average ms of maray_filter_tent<k> alone over a w x rows output image (maray_hip_time_filter)."""
+def time_filter(w, rows, k, device=0, reps=10, filter=FILTER_TENT, transfer=TRANSFER_NONE):
+    """Average ms of maray_filter_tent<k> alone over a w x rows output image (maray_hip_time_filter); with
+    transfer=TRANSFER_SRGB of maray_filter_tent_lin<k> or, filter=FILTER_BOX, maray_filter_box_lin<k> (maray_hip_time_filter_ex)."""
     ms = C.c_float()
-    _check(lib().maray_hip_time_filter(device, w, rows, k, reps, C.byref(ms)))
+    if filter == FILTER_TENT and transfer == TRANSFER_NONE:
+        _check(lib().maray_hip_time_filter(device, w, rows, k, reps, C.byref(ms)))
+    else:
+        _check(lib().maray_hip_time_filter_ex(device, w, rows, k, filter, transfer, reps, C.byref(ms)))
     return ms.value
+
+
+def time_shutter_reduce(nbytes, n, device=0, reps=10, transfer=TRANSFER_NONE):
+    """Average ms of the passes that reduce n frames of nbytes bytes: maray_shutter_reduce, or with transfer=TRANSFER_SRGB
+    maray_shutter_reduce_lin (maray_hip_time_shutter_reduce_ex)."""
+    ms = C.c_float()
+    _check(lib().maray_hip_time_shutter_reduce_ex(device, nbytes, n, transfer, reps, C.byref(ms)))
+    return ms.value
+
+
+def transfer_table(transfer=TRANSFER_SRGB):
+    """(decode D[256], thresholds T[256]) of a transfer as uint16 arrays (maray_transfer_table; T[0] = 0); needs no device."""
+    d, t = np.zeros(256, np.uint16), np.zeros(256, np.uint16)
+    _check(lib().maray_transfer_table(transfer, d.ctypes.data, t.ctypes.data))
+    return d, t
 
 
 def gen_cache_clear():

@@ -20,6 +20,7 @@
 #include "filter.hpp"
 #include "lower.hpp"
 #include "maray_hip.h"
+#include "maray_transfer_table.h"
 #include "png_device.hpp"
 #include "shutter.hpp"
 
@@ -611,9 +612,13 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
         REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT, "unknown filter");
         REQUIRE(filter != MARAY_FILTER_TENT || samples > 1, "the tent filter needs samples = 2, 4 or 8");
-        // a tent context is a plain back-end of the (supersampled) program behind the filter's wrapper (filter_backend.cpp)
+        const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
+        REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
+        // a tent context is a plain back-end of the (supersampled) program behind the filter's wrapper (filter_backend.cpp); so
+        // is every MARAY_TRANSFER_SRGB context: its box reduce is a kernel of the wrapper's, not the in-kernel one
         const uint32_t k = samples;
-        if (filter == MARAY_FILTER_TENT) samples = 1;
+        const bool wrapped = filter == MARAY_FILTER_TENT || transfer == MARAY_TRANSFER_SRGB;
+        if (wrapped) samples = 1;
         Backend *b = nullptr;
         switch (backend) {
         case MARAY_BACKEND_TAPE: b = make_tape_backend(device, *prog, tex, n_tex, true, samples); break;
@@ -650,8 +655,8 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         }
         default: throw Error{MARAY_E_ARG, "unknown backend"};
         }
-        if (filter == MARAY_FILTER_TENT) {
-            try { b = make_filter_backend(device, b, k, prog->n_params); }
+        if (wrapped) {
+            try { b = make_filter_backend(device, b, k, prog->n_params, filter, transfer); }
             catch (...) { delete b; throw; }
         }
         maray_ctx *c = new maray_ctx();
@@ -819,6 +824,40 @@ int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int
     return guard([&] {
         REQUIRE(ms_avg, "null argument");
         *ms_avg = filter_time_tent(device, w, rows, k, reps);
+    });
+}
+
+int maray_hip_time_filter_ex(int device, uint32_t w, uint32_t rows, uint32_t k, uint32_t filter, uint32_t transfer, int reps, float *ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT, "unknown filter");
+        REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
+        REQUIRE(filter == MARAY_FILTER_TENT || transfer == MARAY_TRANSFER_SRGB, "the plain box reduce has no kernel of its own");
+        *ms_avg = transfer == MARAY_TRANSFER_SRGB ? filter_time_lin(device, w, rows, k, filter, reps) : filter_time_tent(device, w, rows, k, reps);
+    });
+}
+
+int maray_hip_time_shutter_reduce_ex(int device, size_t bytes, uint32_t n, uint32_t transfer, int reps, float *ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
+        *ms_avg = shutter_time_reduce(device, bytes, n, reps, transfer);
+    });
+}
+
+// ---- transfer (include/maray_hip.h) ----------------------------------------------------------------------------------
+int maray_transfer_table(uint32_t transfer, uint16_t decode[256], uint16_t thresholds[256])
+{
+    return guard([&] {
+        REQUIRE(decode && thresholds, "null argument");
+        REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
+        static const uint16_t srgb[256] = {MARAY_SRGB_DECODE_LIST};
+        for (uint32_t v = 0; v < 256; v++) {
+            decode[v] = transfer == MARAY_TRANSFER_SRGB ? srgb[v] : (uint16_t)v;
+            thresholds[v] = !v ? 0 : transfer == MARAY_TRANSFER_SRGB ? (uint16_t)(((uint32_t)srgb[v - 1] + srgb[v] + 1) >> 1) : (uint16_t)v;
+        }
     });
 }
 

@@ -4,7 +4,8 @@
 // pixels), -p NAME=VALUE[:LO:HI] (a scene parameter:
 // the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
 // the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
-// image the mean of N frames whose NAME covers SPAN around its value, averaged on the device), --encoder {host,device} (who
+// image the mean of N frames whose NAME covers SPAN around its value, averaged on the device), --linear (samples and frames
+// are averaged in linear light: include/maray_hip.h, "transfer"), --encoder {host,device} (who
 // writes the PNG: the host's zlib, or the device encoder, per --animate frame too).  -c/--cpus is parsed and
 // ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cmath>
@@ -36,6 +37,8 @@ static void usage()
             "      --shutter <name=span>    Motion blur (repeatable): every image is the mean of N frames in which `name` covers\n"
             "                               an interval of width span centred on its value; declares `name` if -p did not\n"
             "      --shutter-samples <n>    N = 1, 2, 4, 8, 16, 32 or 64 (default: 8 once a --shutter is given)\n"
+            "      --linear                 Average samples (-s) and shutter frames in linear light: bytes are decoded as sRGB,\n"
+            "                               averaged and encoded again; alone it changes nothing\n"
             "      --encoder <e>            host | device (default: host); device builds the PNG's compressed stream on the GPU,\n"
             "                               so that no raster crosses to the host (same pixels, other file bytes)\n");
 }
@@ -86,6 +89,7 @@ int main(int argc, char **argv)
     Param anim; uint32_t frames = 0;
     std::vector<Param> spans;           // --shutter: name, value = the span
     uint32_t shutter_samples = 0;
+    bool linear = false;                // --linear
     maray_gen_opts go;
     memset(&go, 0, sizeof go);
     go.backend = MARAY_BACKEND_AUTO;
@@ -112,6 +116,7 @@ int main(int argc, char **argv)
             else if (f == "tent") go.filter = MARAY_FILTER_TENT;
             else { fprintf(stderr, "Error: --filter takes box or tent, not `%s`\n", f.c_str()); usage(); return 2; }
         }
+        else if (a == "--linear") linear = true;
         else if (a == "--encoder") {
             const std::string e = val();
             if (e == "host") go.encoder = MARAY_ENCODER_HOST;
@@ -213,6 +218,8 @@ int main(int argc, char **argv)
         }
     }
     if (!spans.empty()) go.shutter = shutter_samples ? shutter_samples : 8;
+    // --linear alone has nothing to reduce: the plain render, from the plain render's program and contexts
+    if (linear && (go.samples > 1 || go.shutter > 1)) go.transfer = MARAY_TRANSFER_SRGB;
     maray_report rep{MARAY_REPORT_DURATION_MS, 500};   // Report::Duration(500 ms), examples/maray.rs:77-79
     int rc = 0;
     if (!frames) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());

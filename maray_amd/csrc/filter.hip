@@ -21,6 +21,7 @@
 #include <string>
 
 #include "filter.hpp"
+#include "shutter.hpp"
 
 namespace maray {
 
@@ -168,7 +169,7 @@ float filter_time_tent(int device, uint32_t w, uint32_t rows, uint32_t k, int re
     const size_t src_bytes = (size_t)rows * k * w * k * 3, dst_bytes = (size_t)rows * w * 3;
     HIP_TRY(hipMalloc((void **)&o.src, src_bytes + 2 * FILTER_PAD));
     HIP_TRY(hipMalloc((void **)&o.dst, dst_bytes));
-    HIP_TRY(hipMemset(o.src, 0x5A, src_bytes + 2 * FILTER_PAD));
+    measurement_fill(o.src, src_bytes + 2 * FILTER_PAD);
     HIP_TRY(hipStreamCreate(&o.st));
     HIP_TRY(hipEventCreate(&o.e0)); HIP_TRY(hipEventCreate(&o.e1));
     const TentArgs a{o.src + FILTER_PAD, o.dst, w, w * k, rows * k, 0, rows * k, 0, rows};

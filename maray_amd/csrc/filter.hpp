@@ -35,8 +35,16 @@ struct TentArgs {
 void filter_tent(uint32_t k, const TentArgs &a, hipStream_t st);      // enqueues one pass; throws Error
 float filter_time_tent(int device, uint32_t w, uint32_t rows, uint32_t k, int reps);     // maray_hip_time_filter
 
-// The context behind MARAY_FILTER_TENT: takes over `inner`, a plain (samples = 1) back-end of the supersampled program on
-// `device`.  Throws Error (then `inner` is still the caller's).
-Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params);
+// The reduces in linear light (include/maray_hip.h, "transfer"; linear.hip): maray_filter_box_lin<K> and
+// maray_filter_tent_lin<K>, one pass each with TentArgs as above.  The box has no halo: its band covers [k oy0, k (oy0 + n_out)).
+// Blocks loop over tiles of rows, so a pass takes any number of rows.
+void filter_lin(uint32_t filter, uint32_t k, const TentArgs &a, hipStream_t st);      // enqueues one pass; throws Error
+float filter_time_lin(int device, uint32_t w, uint32_t rows, uint32_t k, uint32_t filter, int reps);     // maray_hip_time_filter_ex
+
+// The context behind MARAY_FILTER_TENT and behind MARAY_TRANSFER_SRGB: takes over `inner`, a plain (samples = 1) back-end of
+// the (supersampled) program on `device`.  k = 1 (SRGB only): nothing to filter, launches pass through; the wrapper is there
+// for the shutter's linear reduce.  Throws Error (then `inner` is still the caller's).
+Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params, uint32_t filter = MARAY_FILTER_TENT,
+                             uint32_t transfer = MARAY_TRANSFER_NONE);
 
 }   // namespace maray

@@ -5,6 +5,9 @@
 // then maray_filter_tent<k> (filter.hip) on the same stream.  A band's halo is cut from the image, not from the call: rows
 // [y0, y1) read sample rows [k y0 - k/2, k y1 + k/2) clipped to [0, k h), whatever row range, row block or host tile they
 // belong to, so the picture does not depend on how it was cut.
+// Also the context behind MARAY_TRANSFER_SRGB ("transfer"): the same wrapper with the reduces of linear.hip -- the tent in
+// linear light, the box as a kernel of the wrapper's on bands without halo, and the shutter's linear reduce; with samples <= 1
+// there is nothing to filter and every launch is the inner back-end's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -30,6 +33,12 @@ namespace {
 struct FilterBackend final : Backend {
     int device = 0;
     uint32_t k = 2;
+    // What turns a band into rows: (TENT, NONE) maray_filter_tent<k>; under MARAY_TRANSFER_SRGB (include/maray_hip.h, "transfer")
+    // maray_filter_tent_lin<k> or, for BOX, maray_filter_box_lin<k> on a band without halo.  k = 1 (SRGB only) filters nothing:
+    // launches go straight to `inner`, and only the shutter's reduce differs.
+    uint32_t filter = MARAY_FILTER_TENT, transfer = MARAY_TRANSFER_NONE;
+    bool tent() const { return filter == MARAY_FILTER_TENT; }
+    bool lin() const { return transfer == MARAY_TRANSFER_SRGB; }
     Backend *inner = nullptr;           // renders the sample raster: the program's plain context
     std::string name;
     // Samples of one band: 128 MiB, half of the 256 MiB last-level cache.  A band is a ROW pass, a pixel launch and a filter pass
@@ -70,7 +79,7 @@ struct FilterBackend final : Backend {
         // whole tiles of the filter kernel; one pass of it takes at most 65535 tiles of rows
         const uint64_t by_budget = band_bytes / ((uint64_t)w * 3 * k * k) / FILTER_TILE_H * FILTER_TILE_H;
         const uint64_t rows = band_rows_env ? band_rows_env : std::max<uint64_t>(FILTER_TILE_H, by_budget);
-        return (uint32_t)std::min<uint64_t>(rows, 65535u * (uint64_t)FILTER_TILE_H);
+        return (uint32_t)std::min<uint64_t>(rows, 65535u * (uint64_t)FILTER_TILE_H);        // (the linear kernels loop over tiles: any height)
     }
 
     static void grow(unsigned char *&p, size_t &cap, size_t want) {
@@ -85,6 +94,7 @@ struct FilterBackend final : Backend {
     void launch(uint32_t w, uint32_t h, const RowBlocks &rb, unsigned char *d8, hipStream_t st) {
         if (!rb.n_rows || !w) return;
         if (!d8) throw Error{MARAY_E_ARG, "null argument"};
+        if (k == 1) { inner->render_device(w, h, rb, d8, nullptr, st); return; }
         // the scratch is the context's: a launch on another stream than the last waits for what that one still holds
         if (have_last && st != last_stream) {
             HIP_TRY(hipEventRecord(handover, last_stream));
@@ -94,20 +104,24 @@ struct FilterBackend final : Backend {
         const uint32_t sw = k * w, sh = k * h, step = band_rows(w);
         const size_t row_bytes = (size_t)sw * 3;
         const uint32_t block_rows = std::max(1u, std::min(rb.block_rows, rb.n_rows));
-        grow(scratch, scratch_cap, ((size_t)k * std::min(step, block_rows) + k) * row_bytes + 2 * FILTER_PAD);
+        const uint32_t halo = tent() ? k / 2 : 0;           // (the box reads sample rows [k y0, k y1) and no others)
+        grow(scratch, scratch_cap, ((size_t)k * std::min(step, block_rows) + 2 * halo) * row_bytes + 2 * FILTER_PAD);
         for (uint32_t r0 = 0; r0 < rb.n_rows; r0 += block_rows) {
             const uint32_t rows = std::min(block_rows, rb.n_rows - r0);
             const uint32_t by0 = rb.y0 + (r0 / block_rows) * rb.block_stride;
             for (uint32_t o0 = by0; o0 < by0 + rows; o0 += step) {
                 const uint32_t o1 = std::min(by0 + rows, o0 + step);
-                const uint32_t s0 = k * o0 >= k / 2 ? k * o0 - k / 2 : 0, s1 = std::min(sh, k * o1 + k / 2);
+                const uint32_t s0 = k * o0 >= halo ? k * o0 - halo : 0, s1 = std::min(sh, k * o1 + halo);
                 inner->render_device(sw, sh, RowBlocks::range(s0, s1), scratch + FILTER_PAD, nullptr, st);
-                filter_tent(k, TentArgs{scratch + FILTER_PAD, d8 + ((size_t)r0 + (o0 - by0)) * w * 3, w, sw, sh, s0, s1 - s0, o0, o1 - o0}, st);
+                const TentArgs a{scratch + FILTER_PAD, d8 + ((size_t)r0 + (o0 - by0)) * w * 3, w, sw, sh, s0, s1 - s0, o0, o1 - o0};
+                if (lin()) filter_lin(filter, k, a, st);
+                else filter_tent(k, a, st);
             }
         }
     }
 
     void render_device(uint32_t w, uint32_t h, const RowBlocks &rb, void *d8, void *d64, void *stream) override {
+        if (k == 1) { inner->render_device(w, h, rb, d8, d64, stream); return; }       // nothing to reduce: the plain render, f64 planes included
         if (d64) throw Error{MARAY_E_ARG, "a filtered context renders RGB8 only (no f64 planes)"};
         HIP_TRY(hipSetDevice(device));
         launch(w, h, rb, (unsigned char *)d8, (hipStream_t)stream);
@@ -115,6 +129,7 @@ struct FilterBackend final : Backend {
 
     void render_host_tiles(uint32_t w, uint32_t h, const std::vector<RowTile> &tiles, uint32_t row0, uint8_t *rgb8, double *rgb64,
                            const std::function<void(uint32_t, uint32_t)> &done) override {
+        if (k == 1) { inner->render_host_tiles(w, h, tiles, row0, rgb8, rgb64, done); return; }
         if (rgb64) throw Error{MARAY_E_ARG, "a filtered context renders RGB8 only (no f64 planes)"};
         HIP_TRY(hipSetDevice(device));
         pipe->run(w, tiles, row0, rgb8, nullptr,
@@ -136,7 +151,7 @@ struct FilterBackend final : Backend {
         }
         shutter_render(shutter, values, n, np, (size_t)rb.n_rows * w * 3, d8, st,
                        [&](const double *row) { set_params(row, np); },
-                       [&](unsigned char *frame) { launch(w, h, rb, frame, st); });
+                       [&](unsigned char *frame) { launch(w, h, rb, frame, st); }, transfer);
     }
 
     void render_device_shutter(uint32_t w, uint32_t h, const RowBlocks &rb, const double *values, uint32_t n, void *d8, void *stream) override {
@@ -155,6 +170,7 @@ struct FilterBackend final : Backend {
 
     // the whole call: launches plus filter
     float time_rows(uint32_t w, uint32_t h, const RowBlocks &rb, void *d8, void *d64, int reps) override {
+        if (k == 1) return inner->time_rows(w, h, rb, d8, d64, reps);
         if (d64) throw Error{MARAY_E_ARG, "a filtered context renders RGB8 only (no f64 planes)"};
         HIP_TRY(hipSetDevice(device));
         unsigned char *p8 = (unsigned char *)d8;
@@ -180,12 +196,19 @@ struct FilterBackend final : Backend {
 
 }   // namespace
 
-Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params)
+Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params, uint32_t filter, uint32_t transfer)
 {
-    if (!inner || !filter_samples_ok(k)) throw Error{MARAY_E_INTERNAL, "tent filter: bad arguments"};
+    const bool lin = transfer == MARAY_TRANSFER_SRGB, tent = filter == MARAY_FILTER_TENT;
+    // what has a kernel here: the tent for k = 2, 4, 8; under SRGB also the box, and k = 1 (the shutter's reduce alone)
+    if (!inner || (!lin && transfer != MARAY_TRANSFER_NONE) || (!tent && (filter != MARAY_FILTER_BOX || !lin)) ||
+        !(filter_samples_ok(k) || (k == 1 && lin && !tent)))
+        throw Error{MARAY_E_INTERNAL, "filter context: bad arguments"};
     std::unique_ptr<FilterBackend> b(new FilterBackend());
     b->init(device, k, n_params);
-    b->name = std::string(inner->kernel_name()) + "+maray_filter_tent<" + std::to_string(k) + ">";
+    b->filter = filter; b->transfer = transfer;
+    b->name = std::string(inner->kernel_name()) +
+              (k == 1 ? std::string("+maray_shutter_reduce_lin")
+                      : std::string(tent ? "+maray_filter_tent" : "+maray_filter_box") + (lin ? "_lin<" : "<") + std::to_string(k) + ">");
     b->inner = inner;       // (last: a throw above leaves `inner` with the caller)
     return b.release();
 }

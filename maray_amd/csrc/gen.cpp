@@ -106,6 +106,7 @@ struct GenEntry {
     std::string key;
     uint32_t samples = 1;                     // the program is the scene supersampled k x k (maray_gen_opts.samples)
     uint32_t filter = MARAY_FILTER_BOX;       // what its contexts reduce the samples with (maray_gen_opts.filter)
+    uint32_t transfer = MARAY_TRANSFER_NONE;  // ... and in what: bytes, or linear light (maray_gen_opts.transfer)
     maray_tape *tape = nullptr;
     std::multimap<int, IdleCtx> idle;         // per PHYSICAL device: contexts nobody is rendering with
     bool evicted = false;
@@ -219,7 +220,7 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
             for (auto &kv : e->idle)
                 t += e->key + " device " + std::to_string(kv.first) + " kernel " + maray_hip_kernel_name(kv.second.ctx) + " hint_mpixels " +
                      std::to_string(kv.second.hint_mpixels) + (e->samples > 1 ? " samples " + std::to_string(e->samples) : std::string()) +
-                     (e->filter == MARAY_FILTER_TENT ? " filter tent" : "") + "\n";
+                     (e->filter == MARAY_FILTER_TENT ? " filter tent" : "") + (e->transfer == MARAY_TRANSFER_SRGB ? " transfer srgb" : "") + "\n";
     }
     snprintf(out, cap, "%s", t.c_str());
     return MARAY_OK;
@@ -234,6 +235,8 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
     if (!s || (!rgb8 && !png)) return fail_with(MARAY_E_ARG, "null argument");
     return gen_guard([&]() -> int {
     if (opts && opts->encoder != MARAY_ENCODER_HOST && opts->encoder != MARAY_ENCODER_DEVICE) return fail_with(MARAY_E_ARG, "unknown encoder");
+    const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
+    if (transfer != MARAY_TRANSFER_NONE && transfer != MARAY_TRANSFER_SRGB) return fail_with(MARAY_E_ARG, "unknown transfer");
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
     // supersampling (include/maray_hip.h): the program is the scene on a k x k finer grid, its contexts reduce it
     const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
@@ -262,6 +265,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
         key = buf;
         if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
         if (filter == MARAY_FILTER_TENT) key += "/tent";             // (box keeps its key: the two are kept side by side)
+        if (transfer == MARAY_TRANSFER_SRGB) key += "/srgb";         // (and so does NONE)
     }
     int n_dev_avail = 0;
     maray_hip_device_count(&n_dev_avail);
@@ -320,7 +324,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
         warm.clear();
         if (rc) return rc;
         auto fresh = std::make_shared<GenEntry>();
-        fresh->key = key; fresh->tape = tape; fresh->samples = samples; fresh->filter = filter;
+        fresh->key = key; fresh->tape = tape; fresh->samples = samples; fresh->filter = filter; fresh->transfer = transfer;
         entry = gen_cache_insert(fresh);
     } else if (!png) pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
@@ -356,6 +360,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
     co.backend = opts ? opts->backend : MARAY_BACKEND_AUTO;
     co.samples = samples;
     co.filter = filter;
+    co.transfer = transfer;
     co.hint_mpixels = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (((uint64_t)w * h * samples * samples / n_dev) >> 20) + 1);      // samples it evaluates
 
     Progress P;
@@ -460,6 +465,7 @@ extern "C" int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_
                          const maray_gen_opts *opts, maray_report report, const char *png_path)
 {
     if (!s || !png_path) return fail_with(MARAY_E_ARG, "null argument");
+    if (opts && opts->transfer != MARAY_TRANSFER_NONE && opts->transfer != MARAY_TRANSFER_SRGB) return fail_with(MARAY_E_ARG, "unknown transfer");   // before the raster is pinned
     return gen_guard([&]() -> int {
     uint32_t w = 0, h = 0;
     maray_scene_size(s, &w, &h);

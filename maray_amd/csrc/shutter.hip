@@ -7,7 +7,9 @@
 // and the last pass rounds, shifts and writes bytes.  No atomics: a lane owns its 16 bytes.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "shutter.hpp"
 
@@ -120,9 +122,9 @@ void shutter_reduce(const ShutterArgs &a, hipStream_t st)
     HIP_TRY(hipGetLastError());
 }
 
-void ShutterScratch::ensure(size_t bytes, uint32_t n)
+void ShutterScratch::ensure(size_t bytes, uint32_t n, bool lin)
 {
-    const size_t want = need(bytes, n);
+    const size_t want = need(bytes, n, lin);
     if (want <= cap) return;
     if (base) HIP_TRY(hipFree(base));
     base = nullptr; cap = 0;
@@ -136,7 +138,17 @@ void ShutterScratch::release()
     base = nullptr; cap = 0;
 }
 
-float shutter_time_reduce(int device, size_t bytes, uint32_t n, int reps)
+void measurement_fill(unsigned char *d_buf, size_t bytes)
+{
+    const char *e = getenv("MARAY_TIME_RANDOM_BYTES");
+    if (!e || e[0] != '1') { HIP_TRY(hipMemset(d_buf, 0x5A, bytes)); return; }
+    std::vector<uint64_t> host((bytes + 7) / 8);
+    uint64_t x = 0x9e3779b97f4a7c15ull;
+    for (uint64_t &w : host) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; w = x * 0x2545f4914f6cdd1dull; }      // xorshift64*: every byte of a word is used
+    HIP_TRY(hipMemcpy(d_buf, host.data(), bytes, hipMemcpyHostToDevice));
+}
+
+float shutter_time_reduce(int device, size_t bytes, uint32_t n, int reps, uint32_t transfer)
 {
     if (!shutter_frames_ok(n) || n < 2 || !bytes || reps <= 0) throw Error{MARAY_E_ARG, "shutter_time_reduce: n in 2 .. 64 (a power of two), bytes and reps > 0"};
     HIP_TRY(hipSetDevice(device));
@@ -145,11 +157,11 @@ float shutter_time_reduce(int device, size_t bytes, uint32_t n, int reps)
         ~Own() { s.release(); (void)hipFree(dst); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (st) (void)hipStreamDestroy(st); }
     } o;
     HIP_TRY(hipMalloc((void **)&o.dst, bytes));
-    o.s.ensure(bytes, n);
-    HIP_TRY(hipMemset(o.s.base, 0x5A, o.s.cap));
+    o.s.ensure(bytes, n, transfer == MARAY_TRANSFER_SRGB);
+    measurement_fill(o.s.base, o.s.cap);
     HIP_TRY(hipStreamCreate(&o.st));
     HIP_TRY(hipEventCreate(&o.e0)); HIP_TRY(hipEventCreate(&o.e1));
-    auto once = [&] { shutter_render(o.s, nullptr, n, 0, bytes, o.dst, o.st, [](const double *) {}, [](unsigned char *) {}); };
+    auto once = [&] { shutter_render(o.s, nullptr, n, 0, bytes, o.dst, o.st, [](const double *) {}, [](unsigned char *) {}, transfer); };
     once();
     HIP_TRY(hipEventRecord(o.e0, o.st));
     for (int i = 0; i < reps; i++) once();
