@@ -159,6 +159,8 @@ typedef struct maray_tape_info {
     uint32_t private_regions;  /* row regions that got private copies of the shared x-dependent values they read */
     uint32_t rebalanced_chains; /* boolean OR / AND chains rebuilt as balanced trees */
     uint32_t op_histogram[MARAY_OP_COUNT];   /* PIXEL section */
+    uint32_t row_params[2];    /* bit p of the 64-bit mask {low, high word}: an op of the ROW section reads PARAM p.  The ROW outputs
+                                * depend on these parameters' values only: a context keeps them while those are unchanged */
 } maray_tape_info;
 
 int maray_lower(const maray_scene *s, const maray_lower_opts *opts, maray_tape **out);
@@ -402,6 +404,11 @@ int maray_jit_code_key(const maray_program *prog, char *out33);
 int maray_jit_code_cached(const maray_program *prog, int *cached);
 /* Name of the dominant kernel (for matching rocprofv3 rows). */
 const char *maray_hip_kernel_name(const maray_ctx *c);
+/* How many ROW passes (maray_jit_rows) and launch-order kernels (maray_jit_order) the context has enqueued since it was
+ * created.  A MARAY_BACKEND_JIT context keeps a geometry's ROW outputs while the parameters the ROW section reads are
+ * unchanged (MARAY_JIT_ROW_REUSE=0 in the environment when the context is created: a ROW pass per launch), so a launch
+ * need not add to either; the interpreters' contexts report 0, 0. */
+int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

@@ -36,7 +36,8 @@ class TapeInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in
                 ('n_consts', 'n_row_ops', 'n_row_slots', 'n_yvals', 'n_pix_ops', 'n_pix_slots', 'n_app', 'alg_ops',
                  'alg_ops_xy', 'alg_ops_x', 'alg_ops_y', 'alg_ops_uniform', 'folded_ops', 'dag_nodes',
-                 'acc_operands', 'skip_ops', 'bool_ops', 'sin_ops', 'sin_bounded', 'private_regions', 'rebalanced_chains')] + [('op_histogram', C.c_uint32 * OP_COUNT)]
+                 'acc_operands', 'skip_ops', 'bool_ops', 'sin_ops', 'sin_bounded', 'private_regions', 'rebalanced_chains')] + \
+               [('op_histogram', C.c_uint32 * OP_COUNT), ('row_params_words', C.c_uint32 * 2)]
 
 
 class Texture(C.Structure):
@@ -140,6 +141,7 @@ def lib():
         'maray_hip_time_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp, C.c_int, C.POINTER(C.c_float)]),
         'maray_hip_time_blocks': (C.c_int, [vp, u32, u32, u32, u32, u32, u32, vp, vp, C.c_int, C.POINTER(C.c_float)]),
         'maray_hip_kernel_name': (C.c_char_p, [vp]),
+        'maray_hip_launch_counts': (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         'maray_jit_code_key': (C.c_int, [C.POINTER(Program), C.c_char_p]),
         'maray_jit_code_cached': (C.c_int, [C.POINTER(Program), C.POINTER(C.c_int)]),
         'maray_gen_to_image': (C.c_int, [vp, C.POINTER(Texture), u32, C.POINTER(GenOpts), Report, REPORT_FN, vp, vp,
@@ -359,8 +361,9 @@ class Tape:
         _check(lib().maray_tape_program(self._h, C.byref(self.program)))
         ti = TapeInfo()
         _check(lib().maray_tape_get_info(self._h, C.byref(ti)))
-        self.info = {n: getattr(ti, n) for n, _ in TapeInfo._fields_ if n != 'op_histogram'}
+        self.info = {n: getattr(ti, n) for n, _ in TapeInfo._fields_ if n not in ('op_histogram', 'row_params_words')}
         self.info['op_histogram'] = list(ti.op_histogram)
+        self.info['row_params'] = ti.row_params_words[0] | (ti.row_params_words[1] << 32)      # bit p: a ROW op reads PARAM p
 
     def __del__(self):
         if getattr(self, '_h', None):
@@ -550,6 +553,13 @@ class Context:
     @property
     def kernel_name(self):
         return lib().maray_hip_kernel_name(self._h).decode()
+
+    @property
+    def launch_counts(self):
+        """(ROW passes, launch-order kernels) this context has enqueued so far (maray_hip_launch_counts)."""
+        rows, order = C.c_uint64(), C.c_uint64()
+        _check(lib().maray_hip_launch_counts(self._h, C.byref(rows), C.byref(order)))
+        return rows.value, order.value
 
 
 def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_devices=0, tile_rows=0, report=None,

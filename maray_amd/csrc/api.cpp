@@ -1108,6 +1108,11 @@ int maray_jit_code_cached(const maray_program *prog, int *cached)
 
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }
 
+int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels)
+{
+    return guard([&] { REQUIRE(c && c->backend && row_passes && order_kernels, "null argument"); c->backend->launch_counts(row_passes, order_kernels); });
+}
+
 void maray_free(void *p) { free(p); }
 
 }   // extern "C"

@@ -35,6 +35,9 @@ struct Backend {
     // average ms per launch of the pixel kernel, HIP events on the launch stream
     virtual float time_rows(uint32_t w, uint32_t h, const RowBlocks &rb, void *d8, void *d64, int reps) = 0;
     virtual const char *kernel_name() const = 0;
+    // How many ROW passes (maray_jit_rows) and launch-order kernels (maray_jit_order) the context has enqueued so far: what
+    // the tests of the ROW tables' reuse (row_reuse.hpp) count.  The interpreters run their ROW stage per launch and count nothing.
+    virtual void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const { *row_passes = *order_kernels = 0; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
@@ -133,6 +136,9 @@ uint32_t reschedule_tape(std::vector<uint64_t> &tape);   // cone re-ordered dept
 // Does any guard (a y value that only gates SKIP ops) have SPEC Y in its cone?  If none does, guards may be evaluated
 // once for a group of rows (YMIN / YMAX, include/maray_tape.h).
 bool any_guard_reads_y(const maray_program &P);
+// Bit p is set when an op of the ROW section has PARAM p as an operand: the parameters whose values the ROW outputs (y values,
+// guard bits) depend on.  0 for a program without parameters.
+uint64_t row_param_mask(const maray_program &P);
 
 }   // namespace maray
 

@@ -192,6 +192,7 @@ struct FilterBackend final : Backend {
     }
 
     const char *kernel_name() const override { return name.c_str(); }
+    void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { inner->launch_counts(row_passes, order_kernels); }
 };
 
 }   // namespace

@@ -23,6 +23,7 @@
 #include "host_pipe.hpp"
 #include "jit_parts.hpp"
 #include "maray_hip.h"
+#include "row_reuse.hpp"
 #include "shutter.hpp"
 
 namespace maray {
@@ -39,6 +40,17 @@ namespace {
 
 struct DevTex { const unsigned char *rgb; unsigned w, h; };
 
+// The device memory of one set of ROW-stage tables (row_reuse.hpp has the sets' keys and decides which one a launch uses)
+struct RowTables {
+    double *yvals = nullptr; size_t yvals_cap = 0;
+    unsigned long long *gbits = nullptr; size_t gbits_cap = 0;
+    unsigned *order = nullptr; size_t order_cap = 0;          // the launch order computed from gbits (maray_jit_order)
+    void release() {
+        (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order);
+        *this = RowTables{};
+    }
+};
+
 struct JitBackend final : Backend {
     int device = 0;
     maray_program P{};
@@ -49,15 +61,17 @@ struct JitBackend final : Backend {
     std::shared_ptr<const std::vector<char>> code_ss;
     hipModule_t mod_ss = nullptr;
     hipFunction_t f_ss = nullptr;
-    unsigned *d_order = nullptr; size_t order_cap = 0;
-    uint64_t order_key[3] = {0, 0, 0};                     // the geometry d_order was computed for
-    uint64_t seen_key[3] = {0, 0, 0};                      // the geometry of the previous launch
     Backend *slow = nullptr;            // tape interpreter: evaluates the tiles the pixel kernel deferred
     unsigned *d_flags = nullptr; size_t flags_cap = 0;
     DevTex *d_tex = nullptr;
     std::vector<unsigned char *> d_tex_rgb;
-    double *d_yvals = nullptr; size_t yvals_cap = 0;          // ROW-stage tables (the context's, not a launch's: launches are ordered by their stream)
-    unsigned long long *d_gbits = nullptr; size_t gbits_cap = 0;
+    // ROW-stage tables (the context's, not a launch's: launches are ordered by their stream): set 0 is the scratch every
+    // one-off launch fills, the others are kept for keys that came back (row_reuse.hpp)
+    RowTables tabs[RowReuse::N_SETS];
+    RowReuse reuse;
+    int cur_set = -1;                   // the set the most recent launch used
+    uint64_t row_params = 0;            // bit p: a ROW op reads PARAM p (row_param_mask)
+    uint64_t n_row_passes = 0, n_order_kernels = 0;         // maray_jit_rows / maray_jit_order launches enqueued so far (launch_counts)
     unsigned char *d_rgb8 = nullptr; size_t rgb8_cap = 0;      // time_rows without a caller's buffer
     std::unique_ptr<HostPipe> pipe;     // streams + staging of the host-raster entry points (from the device's pool: host_pipe.hpp)
     hipStream_t own_stream = nullptr;   // = pipe's compute stream
@@ -85,8 +99,8 @@ struct JitBackend final : Backend {
         (void)hipFree(d_flags);
         (void)hipFree(d_tex);
         for (auto p : d_tex_rgb) (void)hipFree(p);
-        (void)hipFree(d_order); (void)hipFree(d_rgb8);
-        (void)hipFree(d_yvals); (void)hipFree(d_gbits);
+        (void)hipFree(d_rgb8);
+        for (RowTables &t : tabs) t.release();
         shutter.release();
         if (handover) (void)hipEventDestroy(handover);
         ring.release();
@@ -126,6 +140,9 @@ struct JitBackend final : Backend {
         has_sin = may_defer_tiles(prog);
         // (set below, from the code object's header: the guard plan is not recomputed per context)
         if (const char *e_ = getenv("MARAY_JIT_TILES")) if (atoi(e_) > 0) k_tiles = (unsigned)atoi(e_);
+        // MARAY_JIT_ROW_REUSE=0: a ROW pass per launch and one set of tables, as before the sets had keys (read once, here)
+        if (const char *e_ = getenv("MARAY_JIT_ROW_REUSE")) if (e_[0] == '0') reuse.enabled = false;
+        row_params = row_param_mask(prog);
         lap("device");
         code = jit_code_for(prog);                       // built by the first context of the process, or read from the cache
         lap("code objects");
@@ -202,15 +219,19 @@ struct JitBackend final : Backend {
     }
 
     // New values reach the tables on the launch's own stream: launches enqueued before the set_params call keep theirs.
-    // Three things assumed that a geometry's ROW outputs never change; with new values:
-    //  - launches without a ROW pass (time_rows): the y values and guard bits in the tables are the old values' -- wrong
-    //    pixels, not slow ones.  The launch that carries new values runs its ROW pass (the return value says so).
-    //  - the cached launch order: a permutation of rows from the guard bits of the values it was computed with.  Still a
-    //    permutation, so pixels stay right, but no longer "dearest first".  Dropped, and so is the memory of the geometry:
-    //    the order kernel costs more than ten launches' gain, so it runs again only once a geometry comes a second time
-    //    with the SAME values (a paused animation, a benchmark loop), never per frame of a moving one.
+    // Every changed value is sent -- the PIXEL module reads them all -- and nothing is dropped here: what depends on the
+    // values carries them in its key.  Three things read a geometry's ROW outputs; with new values:
+    //  - the ROW tables themselves (y values, guard bits): keyed on the geometry and on the bits of the values the ROW
+    //    section reads (row_params), so a change to one of those is another key -- its launch finds no set and runs the ROW
+    //    pass -- and a change to a parameter only PIXEL ops read is the same key: no ROW pass.  A launch without a ROW
+    //    pass of its own (time_rows) that carries new values asks for one (the return value says so) and gets it only
+    //    if no set holds the key.
+    //  - the launch order: a permutation of rows from the guard bits of one set, kept in that set and so under the same
+    //    key; computed when a key comes a second time (a paused animation, a benchmark loop, an animation of PIXEL-only
+    //    parameters), never per frame of one whose ROW-read values move: the order kernel costs more than ten launches'
+    //    gain.
     //  - deferred tiles: the interpreter behind this context has the values already (set_params) and sends them on the
-    //    same stream, in front of its kernel.
+    //    same stream, in front of its kernel; it reads the y values of the set the launch used.
     bool send_params(hipStream_t st) {
         if (!params_dirty) return false;
         double *slot = ring.take();
@@ -219,8 +240,63 @@ struct JitBackend final : Backend {
         for (hipDeviceptr_t p : d_par) HIP_TRY(hipMemcpyHtoDAsync(p, slot, bytes, st));
         ring.sent(st);
         params_dirty = false;
-        for (int i = 0; i < 3; i++) order_key[i] = seen_key[i] = 0;
         return true;
+    }
+
+    // The set of ROW tables a launch reads, filled by maray_jit_rows on `st` unless a set already holds the outputs of this
+    // launch's key: the geometry and the bits of the ROW-read parameters (with MARAY_JIT_ROW_REUSE=0 of all parameters, and
+    // a launch that asks for a ROW pass runs it whatever the tables hold).  rows_pass == false never runs the kernel: the
+    // set that holds the key, else the set of the previous launch as it is.  *matched: the set holds this launch's key.
+    // Called after the stream hand-over and send_params: every launch of the context is ordered behind the previous one,
+    // whichever streams they are on, so a set filled on one stream is complete for a reader on another.
+    int row_set(uint32_t w, uint32_t rows_total, unsigned y0, unsigned blk_rows, unsigned blk_stride, unsigned yrows, uint32_t n_groups,
+                bool want_order, hipStream_t st, bool rows_pass, bool *matched) {
+        RowKey key;
+        key.geometry(w, rows_total, y0, blk_rows, blk_stride, yrows);
+        key.params(param_values.data(), (uint32_t)param_values.size(), reuse.enabled ? row_params : ~0ull);
+        int s = reuse.find(key);
+        *matched = true;
+        if (s >= 0 && (reuse.enabled || !rows_pass)) {
+            reuse.touch(s);
+            return cur_set = s;
+        }
+        if (!rows_pass) {
+            if (cur_set < 0) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
+            *matched = false;
+            return cur_set;
+        }
+        const size_t yv_n = (size_t)rows_total * std::max<uint32_t>(P.n_yvals, 1);
+        const size_t gb_n = (size_t)n_groups * ((w + 255) / 256) * guard_sub * std::max<uint32_t>(n_gwords, 1);
+        const size_t od_n = want_order ? rows_total : 0;
+        const bool refill = s >= 0;             // reuse is off: the scratch holds this key and is written again
+        if (!refill)
+            s = reuse.place(key, yv_n * sizeof(double) + gb_n * sizeof(unsigned long long) + od_n * sizeof(unsigned),
+                            [&](int v) { return tabs[v].yvals_cap >= yv_n && tabs[v].gbits_cap >= gb_n && tabs[v].order_cap >= od_n; },
+                            [&](int v) { tabs[v].release(); });      // (hipFree waits for the device: at a promotion or an eviction only)
+        RowTables &t = tabs[s];
+        ensure(t.yvals, t.yvals_cap, yv_n);
+        const size_t had = t.gbits_cap;
+        ensure(t.gbits, t.gbits_cap, gb_n);
+        // A kept set gets its order table with the other two, whether or not an order is ever computed in it: fits() asks for
+        // all three, so a set whose keys rotate away before their second launch can still be taken over as it is (the
+        // scratch's grows in launch(), when an order is due)
+        if (s) ensure(t.order, t.order_cap, od_n);
+        // bits past the last guard belong to no job and are never written: zero them once per table (the pixel kernel tests whole words)
+        if (t.gbits_cap != had) HIP_TRY(hipMemsetAsync(t.gbits, 0, t.gbits_cap * sizeof(unsigned long long), st));
+        if (P.n_row_ops) {
+            unsigned rr = rows_total, ww = w, n_yvals = P.n_yvals;
+            unsigned n_tx_ = (w + 255) / 256 * guard_sub;
+            // guards: one item per rectangle (group of yrows rows, run of 256 / guard_sub pixels); y values: one per row
+            const uint64_t items = std::max<uint64_t>(n_gwords ? (uint64_t)n_groups * n_tx_ : 0, rows_total);
+            const unsigned bs = ROW_BLOCK;
+            if (items + bs > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
+            void *args[] = {&t.yvals, &t.gbits, &d_tex, &y0, &rr, &n_yvals, &ww, &n_tx_, &blk_rows, &blk_stride, &yrows};
+            unsigned gy = n_row_chunks + n_gjobs;
+            HIP_TRY(hipModuleLaunchKernel(f_rows, (unsigned)((items + bs - 1) / bs), gy, 1, bs, 1, 1, 0, st, args, nullptr));
+            n_row_passes++;
+        }
+        if (refill) reuse.touch(s); else reuse.filled(s);      // the set carries its key only now: the kernel that fills it is enqueued
+        return cur_set = s;
     }
 
     // Supersampling (maray_jit_pixels_ss): w_out and rb_out are output pixels and rows; the ROW stage covers the k x k times
@@ -239,24 +315,10 @@ struct JitBackend final : Backend {
         if (send_params(st)) rows_pass = true;
         unsigned yrows = (guard_rows > 1 && (blk_rows >= rows_total || blk_rows % guard_rows == 0)) ? guard_rows : 1u;
         const uint32_t n_groups = (rows_total + yrows - 1) / yrows;
-        if (rows_pass) {
-            ensure(d_yvals, yvals_cap, (size_t)rows_total * std::max<uint32_t>(P.n_yvals, 1));
-            const size_t had = gbits_cap;
-            ensure(d_gbits, gbits_cap, (size_t)n_groups * ((w + 255) / 256) * guard_sub * std::max<uint32_t>(n_gwords, 1));
-            if (gbits_cap != had) HIP_TRY(hipMemsetAsync(d_gbits, 0, gbits_cap * sizeof(unsigned long long), st));
-        }
-        if (!d_yvals || !d_gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
+        bool matched;
+        const RowTables &T = tabs[row_set(w, rows_total, y0, blk_rows, blk_stride, yrows, n_groups, false, st, rows_pass, &matched)];   // keyed on the sample grid
+        if (!T.yvals || !T.gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
         unsigned n_yvals = P.n_yvals;
-        if (rows_pass && P.n_row_ops) {
-            unsigned rr = rows_total, ww = w;
-            unsigned n_tx_ = (w + 255) / 256 * guard_sub;
-            const uint64_t items = std::max<uint64_t>(n_gwords ? (uint64_t)n_groups * n_tx_ : 0, rows_total);
-            const unsigned bs = ROW_BLOCK;
-            if (items + bs > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
-            void *args[] = {&d_yvals, &d_gbits, &d_tex, &y0, &rr, &n_yvals, &ww, &n_tx_, &blk_rows, &blk_stride, &yrows};
-            unsigned gy = n_row_chunks + n_gjobs;
-            HIP_TRY(hipModuleLaunchKernel(f_rows, (unsigned)((items + bs - 1) / bs), gy, 1, bs, 1, 1, 0, st, args, nullptr));
-        }
         // tiles per wavefront: the narrow rule of launch(), on the tiles of sample rows a launch evaluates
         const unsigned n_tx = (w + 255) / 256;
         const uint64_t n_tiles = (uint64_t)n_tx * rows_total, device_slots = (uint64_t)n_cu * 4 * 7;
@@ -267,8 +329,8 @@ struct JitBackend final : Backend {
         for (uint32_t r0 = 0; r0 < rb_out.n_rows; r0 += 65534u) {
             const uint32_t rows = std::min<uint32_t>(65534u, rb_out.n_rows - r0);
             unsigned ww = w, row_base = r0, ntx = n_tx, wo = w_out;
-            const double *yv = d_yvals;
-            const unsigned long long *gb = d_gbits;
+            const double *yv = T.yvals;
+            const unsigned long long *gb = T.gbits;
             void *args[] = {&d8, &yv, &d_tex, &gb, &ntx, &ww, &y0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &wo};
             HIP_TRY(hipModuleLaunchKernel(f_ss, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
@@ -297,49 +359,33 @@ struct JitBackend final : Backend {
         const uint32_t n_groups = (rows_total + yrows - 1) / yrows;
         // (the ROW stage on a stream of its own under the previous launch's PIXEL kernel was measured and lost: the two kernels
         // share the SIMDs and the events that order the streams cost a signal round trip each)
-        if (rows_pass) {
-            ensure(d_yvals, yvals_cap, (size_t)rows_total * std::max<uint32_t>(P.n_yvals, 1));
-            const size_t had = gbits_cap;
-            ensure(d_gbits, gbits_cap, (size_t)n_groups * ((w + 255) / 256) * guard_sub * std::max<uint32_t>(n_gwords, 1));
-            // bits past the last guard belong to no job and are never written: zero them once (the pixel kernel tests whole words)
-            if (gbits_cap != had) HIP_TRY(hipMemsetAsync(d_gbits, 0, gbits_cap * sizeof(unsigned long long), st));
-        }
-        if (!d_yvals || !d_gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
-        unsigned n_yvals = P.n_yvals;
-        if (rows_pass && P.n_row_ops) {
-            unsigned yy0 = y0, rr = rows_total, ww = w;
-            unsigned n_tx_ = (w + 255) / 256 * guard_sub;
-            // guards: one item per rectangle (group of yrows rows, run of 256 / guard_sub pixels); y values: one per row
-            const uint64_t items = std::max<uint64_t>(n_gwords ? (uint64_t)n_groups * n_tx_ : 0, rows_total);
-            const unsigned bs = ROW_BLOCK;
-            if (items + bs > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
-            void *args[] = {&d_yvals, &d_gbits, &d_tex, &yy0, &rr, &n_yvals, &ww, &n_tx_, &blk_rows, &blk_stride, &yrows};
-            unsigned gy = n_row_chunks + n_gjobs;
-            HIP_TRY(hipModuleLaunchKernel(f_rows, (unsigned)((items + bs - 1) / bs), gy, 1, bs, 1, 1, 0, st, args, nullptr));
-        }
-        // launch order of the PIXEL kernel (maray_jit_order): once per geometry, from the guard bits the ROW kernel just wrote;
-        // a cached order is used by every launch of that geometry, with or without a ROW pass (time_rows)
         const uint32_t rows_per_grid = 65534u;                         // gridDim.y limit (an even number of rows: whole 32-row groups)
-        // the order is a permutation of the launch's rows and every grid reads it from its first entry: a launch of more
-        // than one grid takes none
+        // the launch order is a permutation of the launch's rows and every grid reads it from its first entry: a launch of
+        // more than one grid takes none
+        const bool want_order = f_order && n_gwords && rows_total <= rows_per_grid && n_groups <= 4096 && n_groups > 1;
+        bool matched;
+        const int set = row_set(w, rows_total, y0, blk_rows, blk_stride, yrows, n_groups, want_order, st, rows_pass, &matched);
+        RowTables &T = tabs[set];
+        if (!T.yvals || !T.gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
+        unsigned n_yvals = P.n_yvals;
+        // launch order of the PIXEL kernel (maray_jit_order): once per key, from the set's guard bits, whether this launch
+        // ran the ROW kernel or found them there; used by every later launch of that key (time_rows too)
         const unsigned *row_order = nullptr;
-        if (f_order && n_gwords && rows_total <= rows_per_grid && n_groups <= 4096 && n_groups > 1) {
-            const uint64_t key[3] = {((uint64_t)w << 32) | rows_total, ((uint64_t)y0 << 32) | blk_rows, ((uint64_t)blk_stride << 32) | yrows};
-            const bool cached = key[0] == order_key[0] && key[1] == order_key[1] && key[2] == order_key[2];
-            // The order costs one 43 us kernel per geometry and saves ~2.6 us per launch: it is computed when a geometry
-            // comes a second time (an animation, a benchmark loop), never for the tiles of a one-shot render, each of
-            // which is a geometry of its own.
-            const bool again = key[0] == seen_key[0] && key[1] == seen_key[1] && key[2] == seen_key[2];
-            seen_key[0] = key[0]; seen_key[1] = key[1]; seen_key[2] = key[2];
-            if (!cached && rows_pass && again) {
-                order_key[0] = order_key[1] = order_key[2] = 0;     // no geometry owns d_order until the kernel below is enqueued
-                ensure(d_order, order_cap, (size_t)rows_total);
+        if (want_order && matched) {
+            RowReuse::Set &S = reuse.sets[set];
+            // The order costs one 43 us kernel per key and saves ~2.6 us per launch: it is computed by the first launch that
+            // finds the set holding its key (an animation, a benchmark loop: the second launch; a key that came back into
+            // a kept set: the launch after the one that filled it), never for the tiles of a one-shot render, each of
+            // which is a geometry of its own, nor for keys that rotate through more sets than a context keeps.
+            if (!S.order && S.launches >= 2) {
+                ensure(T.order, T.order_cap, (size_t)rows_total);
                 unsigned rr = rows_total, n_tx_ = (w + 255) / 256 * guard_sub;
-                void *oargs[] = {&d_gbits, &d_order, &rr, &n_tx_, &yrows};
+                void *oargs[] = {&T.gbits, &T.order, &rr, &n_tx_, &yrows};
                 HIP_TRY(hipModuleLaunchKernel(f_order, 1, 1, 1, 256, 1, 1, n_groups * 4, st, oargs, nullptr));
-                order_key[0] = key[0]; order_key[1] = key[1]; order_key[2] = key[2];
+                n_order_kernels++;
+                S.order = true;             // only now: the kernel that computes it is enqueued
             }
-            if (key[0] == order_key[0] && key[1] == order_key[1] && key[2] == order_key[2]) row_order = d_order;
+            if (S.order) row_order = T.order;
         }
         const unsigned n_tx = (w + 255) / 256;
         const uint64_t n_tiles = (uint64_t)n_tx * rows_total;
@@ -370,16 +416,16 @@ struct JitBackend final : Backend {
             uint32_t rows = std::min<uint32_t>(rows_per_grid, rows_total - r0);
             unsigned char *p8 = d8 ? d8 + (size_t)r0 * w * 3 : nullptr;
             double *p64 = d64 ? d64 + (size_t)r0 * w * 3 : nullptr;
-            const double *yv = d_yvals + (size_t)r0 * n_yvals;
+            const double *yv = T.yvals + (size_t)r0 * n_yvals;
             unsigned *fl = d_flags;
             unsigned ww = w, yy0 = y0, tile_base = r0 * n_tx, row_base = r0;
-            const unsigned long long *gb = d_gbits;              // indexed by the row of the whole call
+            const unsigned long long *gb = T.gbits;              // indexed by the row of the whole call
             unsigned ntx = n_tx;
             unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
             void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw};
             HIP_TRY(hipModuleLaunchKernel(f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
-        if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, d_yvals);   // no-op unless a tile was deferred
+        if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, T.yvals);   // no-op unless a tile was deferred
     }
 
     void render_device(uint32_t w, uint32_t, const RowBlocks &rb, void *d8, void *d64, void *stream) override {
@@ -444,6 +490,7 @@ struct JitBackend final : Backend {
     }
 
     const char *kernel_name() const override { return ss > 1 ? "maray_jit_pixels_ss" : "maray_jit_pixels"; }
+    void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { *row_passes = n_row_passes; *order_kernels = n_order_kernels; }
 };
 
 }   // namespace

@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include "backend.hpp"
 #include "maray_hip.h"
 
 namespace maray {
@@ -1555,6 +1556,8 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
     info.skip_ops = pix.n_skips;
     for (size_t i = 0; i < N; i++) if (is_pix[i] && L.isbool[i]) info.bool_ops++;
     for (uint64_t ins : t.pix_ops) info.op_histogram[MARAY_INS_OP(ins)]++;
+    const uint64_t row_params = row_param_mask(t.program());
+    info.row_params[0] = (uint32_t)row_params; info.row_params[1] = (uint32_t)(row_params >> 32);
 }
 
 }   // namespace maray

@@ -1,0 +1,141 @@
+// row_reuse.hpp — which ROW-stage tables a launch of the specialised backend uses, and whether they already hold what it
+// needs (product code; the policy only: includes no HIP, so that it can be compiled and exercised on a CPU).
+//
+// A context's ROW outputs (y values per row, guard words per rectangle, and the launch order derived from them) depend on
+// the program, the geometry of the launch and the values of the parameters that the ROW section reads -- nothing else.
+// A set of tables therefore carries a key made of exactly that, and a launch whose key a set already holds runs no ROW
+// kernel.  Set 0 is the context's scratch: whatever the most recent one-off launch filled.  Sets 1 .. are kept: a key
+// gets one only when it comes a second time (the seen-ring remembers recent keys as 64-bit hashes; a collision costs
+// memory, never a wrong pixel, because a hit compares whole keys), so the tiles of a one-shot render keep sharing the
+// scratch and allocate nothing.  Kept sets are bounded by count and by bytes and evicted least recently used; a set that
+// could not fit the byte budget is simply not kept.  jit_backend.cpp owns the device memory behind the set numbers.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "maray_tape.h"
+
+namespace maray {
+
+// Geometry words + the bit patterns of the ROW-read parameters' values (NaN payloads and the sign of zero count: the
+// ROW kernel sees bits).  Compared like set_params compares values: memcmp.
+struct RowKey {
+    uint64_t words[3 + MARAY_MAX_PARAMS];
+    uint32_t n = 0;
+
+    void geometry(uint32_t w, uint32_t rows_total, uint32_t y0, uint32_t blk_rows, uint32_t blk_stride, uint32_t yrows) {
+        words[0] = ((uint64_t)w << 32) | rows_total;
+        words[1] = ((uint64_t)y0 << 32) | blk_rows;
+        words[2] = ((uint64_t)blk_stride << 32) | yrows;
+        n = 3;
+    }
+    // the values of the parameters in `mask` (bit p = parameter p), in order of p
+    void params(const double *values, uint32_t n_params, uint64_t mask) {
+        for (uint32_t p = 0; p < n_params && p < MARAY_MAX_PARAMS; p++)
+            if ((mask >> p) & 1) memcpy(&words[n++], &values[p], sizeof(uint64_t));
+    }
+    bool same(const RowKey &o) const { return n == o.n && memcmp(words, o.words, (size_t)n * sizeof(uint64_t)) == 0; }
+    uint64_t hash() const {                     // FNV-1a over the words; never 0 (0 = an empty place in the seen-ring)
+        uint64_t h = 1469598103934665603ull;
+        for (uint32_t i = 0; i < n; i++)
+            for (int b = 0; b < 8; b++) { h ^= (words[i] >> (8 * b)) & 0xFF; h *= 1099511628211ull; }
+        return h ? h : 1;
+    }
+};
+
+struct RowReuse {
+    static constexpr int MAX_KEPT = 8;                      // design limits, not measurements
+    static constexpr size_t MAX_BYTES = (size_t)256 << 20;
+    static constexpr int N_SETS = 1 + MAX_KEPT;             // set 0 = scratch
+    static constexpr int SEEN = 32;
+
+    struct Set {
+        RowKey key;
+        bool keyed = false;         // the tables hold the ROW outputs of `key` (set only once the ROW kernel is enqueued)
+        bool order = false;         // ... and the launch order computed from its guard bits
+        uint32_t launches = 0;      // launches that used the set under this key: the second one (the first that found it filled) computes the order
+        uint64_t stamp = 0;         // last use (kept sets: least recently used goes first)
+        size_t bytes = 0;           // kept sets: device bytes accounted to the set (0 = not in use)
+    };
+
+    bool enabled = true;            // MARAY_JIT_ROW_REUSE=0: one scratch set, a ROW pass per launch that asks for one
+    int max_kept = MAX_KEPT;
+    size_t max_bytes = MAX_BYTES;
+    Set sets[N_SETS];
+    uint64_t seen[SEEN] = {};
+    int seen_next = 0;
+    uint64_t clock = 0;
+    size_t kept_bytes = 0;
+    int kept_sets = 0;
+
+    // The set that holds valid outputs for `key`, or -1.
+    int find(const RowKey &key) const {
+        for (int s = 0; s < N_SETS; s++)
+            if (sets[s].keyed && sets[s].key.same(key)) return s;
+        return -1;
+    }
+
+    // A launch uses set s, found by find().
+    void touch(int s) { sets[s].stamp = ++clock; sets[s].launches++; }
+
+    bool was_seen(uint64_t h) const {
+        for (uint64_t v : seen) if (v == h) return true;
+        return false;
+    }
+    void remember(uint64_t h) {
+        if (was_seen(h)) return;
+        seen[seen_next] = h;
+        seen_next = (seen_next + 1) % SEEN;
+    }
+
+    int lru() const {
+        int v = -1;
+        for (int s = 1; s <= max_kept; s++)
+            if (sets[s].bytes && (v < 0 || sets[s].stamp < sets[v].stamp)) v = s;
+        return v;
+    }
+    void drop(int s) {              // the caller frees the device memory of s
+        kept_bytes -= sets[s].bytes;
+        kept_sets--;
+        sets[s] = Set{};
+    }
+
+    // No set holds `key`: the set its ROW pass will fill.  `need` = device bytes of its tables; fits(s) = the tables kept
+    // set s has now are large enough for them (then s can be taken over without touching device memory); release(s) =
+    // free the device memory of kept set s.  The chosen set's key is withdrawn until filled() -- an exception in between
+    // leaves no key over tables that nothing filled.  Returns 0 (scratch) unless the key has come before.
+    template <typename Fits, typename Release>
+    int place(const RowKey &key, size_t need, Fits fits, Release release) {
+        const uint64_t h = key.hash();
+        const bool again = was_seen(h);
+        remember(h);
+        int s = 0;
+        if (enabled && again && max_kept > 0 && need <= max_bytes) {
+            int v = (kept_sets >= max_kept || kept_bytes + need > max_bytes) ? lru() : -1;
+            if (v >= 0 && fits(v)) {
+                // taken over as it is, new key: the set stays accounted with the bytes of its tables, which are what
+                // the device holds -- at least `need`, so the budget errs on the safe side
+                s = v;
+            } else {
+                if (kept_sets >= max_kept) { release(v); drop(v); }
+                while (kept_bytes + need > max_bytes) { v = lru(); release(v); drop(v); }
+                for (s = 1; sets[s].bytes; s++) {}
+                sets[s].bytes = need;
+                kept_bytes += need;
+                kept_sets++;
+            }
+        }
+        sets[s].keyed = false;
+        sets[s].order = false;
+        sets[s].launches = 0;                           // (touch() by filled() counts this launch)
+        sets[s].key = key;
+        return s;
+    }
+
+    // The ROW kernel that fills set s for the key given to place() has been enqueued.
+    void filled(int s) { sets[s].keyed = true; touch(s); }
+};
+
+}   // namespace maray

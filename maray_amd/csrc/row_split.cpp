@@ -27,6 +27,22 @@ uint32_t numeric_yvals(const maray_program &P)
     return n;
 }
 
+uint64_t row_param_mask(const maray_program &P)
+{
+    uint64_t mask = 0;
+    if (P.version < MARAY_TAPE_VERSION_PARAMS || !P.n_params) return 0;
+    for (uint32_t i = 0; i < P.n_row_ops; i++) {
+        const uint64_t ins = P.row_ops[i];
+        const uint32_t op = MARAY_INS_OP(ins);
+        if (op == MARAY_OP_NOP || op == MARAY_OP_TEXDIM) continue;
+        const uint32_t refs[2] = {MARAY_INS_A(ins), (op >= MARAY_OP_ADD && op <= MARAY_OP_APP) ? MARAY_INS_B(ins) : 0u};
+        for (uint32_t r : refs)
+            if (MARAY_REF_KIND(r) == MARAY_K_SPEC && MARAY_REF_INDEX(r) >= MARAY_SPEC_PARAM0 && MARAY_REF_INDEX(r) - MARAY_SPEC_PARAM0 < MARAY_MAX_PARAMS)
+                mask |= 1ull << (MARAY_REF_INDEX(r) - MARAY_SPEC_PARAM0);
+    }
+    return mask;
+}
+
 RowTapeDeps row_tape_deps(const maray_program &P)
 {
     const uint32_t n = P.n_row_ops;
