@@ -515,6 +515,60 @@ int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *val
 int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32_t h, int reps, float *ms_avg, uint64_t *stream_bytes);
 uint64_t maray_hip_png_bytes_to_host(void);
 
+/* ---- animation (one APNG, encoded on the device frame by frame) ----------------------------------------------------
+ * An animation is written as ONE file: an APNG, i.e. a PNG whose IDAT image is frame 0 (any PNG reader shows it) followed
+ * by the later frames, each a complete zlib stream -- the device PNG encoder's, above -- of a SUB-RECTANGLE of the canvas.
+ * The rectangle of frame i > 0 is the bounding box of the pixels in which it differs from frame i - 1, found on the device
+ * (maray_frame_delta): only that rectangle is compressed and copied to the host, plus the box's 16 bytes.
+ *   - container: signature; IHDR (w, h, 8, 2, 0, 0, 0); acTL (num_frames u32, num_plays u32; 0 plays = for ever); fcTL
+ *     (sequence 0, w x h at 0, 0) and frame 0's stream in IDAT chunks of at most 2^30 bytes; for every later frame fcTL and
+ *     fdAT chunks of a 4-byte sequence number and at most 2^30 - 4 bytes of the stream; IEND.  fcTL is 26 bytes: sequence,
+ *     width, height, x_offset, y_offset (u32 each), delay_num, delay_den (u16), dispose_op 0 (NONE), blend_op 0 (SOURCE).
+ *     Sequence numbers are shared by fcTL and fdAT: 0, 1, 2, ... without a gap.  All words big-endian, CRC-32 by zlib's crc32;
+ *   - a frame equal to the one before it is written as the 1 x 1 rectangle at (0, 0): APNG has no empty frame, and a SOURCE
+ *     blend of an unchanged pixel changes nothing;
+ *   - a frame's stream is closed like a still's: 78 01, its segments, 01 00 00 FF FF, the Adler-32 of its filtered bytes
+ *     (rows of one filter byte and 3 bw bytes, bw the rectangle's width);
+ *   - the file is a function of the frames' rasters, delay_num, delay_den and n_plays alone: the same bytes for every
+ *     MARAY_PNG_BAND_ROWS and every stream;
+ *   - every frame shows for delay_num / delay_den seconds (delay_den = 0 means 100, by the APNG specification).
+ * maray_frame_delta's contract: two packed RGB8 rasters of w x h pixels in device memory, row pitch exactly 3 w, any byte
+ * alignment, independently; box = x0, y0, x1, y1, the half-open bounding box of all pixels in which any of the three bytes
+ * differs, and 0, 0, 0, 0 when no byte differs.  Exact.  Nothing is written but the box (and the call's partial boxes).
+ * How it runs: the writer holds two whole-frame rasters on the device and swaps them between frames; per frame the render
+ * in the encoder's band steps, maray_frame_delta + maray_frame_delta_box, one copy of 16 bytes, a 2-D device-to-device copy
+ * of the box's rows into the encoder's band buffer (left out where the box is as wide as the canvas) and the encoder's
+ * kernels and copies per band.  One device per animation.
+ * Errors: n_images (n_frames) = 0, delay_num or delay_den above 65535, a null pointer, w = 0 or h = 0: MARAY_E_ARG; the
+ * device PNG encoder's size limits per frame, and a frame of more than 2^30 bytes (3 w h): MARAY_E_LIMIT; nothing is
+ * launched in those cases. */
+/* The kernel alone on the caller's rasters: enqueued on `stream` (NULL = the null stream) and waited for. */
+int maray_hip_frame_delta(int device, const void *d_prev, const void *d_cur, uint32_t w, uint32_t h, void *stream, uint32_t box[4]);
+/* n_frames packed frames, 3 w h bytes apart, already in device memory at any alignment -> a complete APNG in malloc'ed host
+ * memory (maray_free): the animation twin of maray_hip_png_encode_device. */
+int maray_hip_apng_encode_device(int device, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t delay_num,
+                                 uint32_t delay_den, uint32_t n_plays, void *stream, uint8_t **out, size_t *n_out);
+/* n_images images of a context (any back-end, samples, filter, transfer) as an APNG.  `values` is an (n_images * n_sub) x P
+ * matrix, P = the program's parameter count: image i is the shutter render ("shutter" above) over its n_sub rows; n_sub = 1
+ * is the plain render with that row, and n_sub is 1, 2, 4, ..., 64.  Every row is checked against the declared ranges
+ * before the first launch (MARAY_E_ARG, nothing rendered); the context's own values are unchanged afterwards.  A program
+ * without parameters takes values = NULL and renders n_images equal images. */
+int maray_hip_render_apng(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                          uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, uint8_t **out, size_t *n_out);
+/* Measurements: average ms of maray_frame_delta + maray_frame_delta_box over two w x h rasters of the call's own that
+ * differ in their first and last byte (maray_hip_time_filter's fill).  maray_hip_time_frame_delta_copy also times, in the
+ * same call, a device-to-device hipMemcpyAsync of one raster's bytes -- the same 2 x 3 w h bytes moved. */
+int maray_hip_time_frame_delta(int device, uint32_t w, uint32_t h, int reps, float *ms_avg);
+int maray_hip_time_frame_delta_copy(int device, uint32_t w, uint32_t h, int reps, float *ms_avg, float *copy_ms_avg);
+/* gen for an animation: image i is the scene with its parameters set to row i of `values` (n_images x the scene's declared
+ * parameter count), written to `path` as one APNG.  With opts->shutter = n > 1 each image's sub-frames are the scene's
+ * maray_scene_shutter_values around that row.  The tape and the context come from what maray_gen_to_image keeps, exactly as
+ * it finds them: a second animation of a scene pays no lowering.  One device: opts->n_devices > 1 is MARAY_E_ARG;
+ * opts->encoder is ignored (an animation is always encoded on the device); there are no progress reports.  The scene's
+ * current parameter values are as they were when the call returns, however it ends. */
+int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                        uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path);
+
 /* PNG I/O used by gen and the CLI (`img.save`, `image::open(..).to_rgb8()`). */
 int maray_png_write(const char *path, const uint8_t *rgb8, uint32_t w, uint32_t h);
 int maray_png_read(const char *path, uint8_t **rgb8_out, uint32_t *w, uint32_t *h);   /* free with maray_free */

@@ -153,6 +153,12 @@ def lib():
         'maray_hip_render_png': (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_time_png_encode': (C.c_int, [C.c_int, vp, u32, u32, C.c_int, C.POINTER(C.c_float), u64p]),
         'maray_hip_png_bytes_to_host': (C.c_uint64, []),
+        'maray_hip_frame_delta': (C.c_int, [C.c_int, vp, vp, u32, u32, vp, C.POINTER(u32)]),
+        'maray_hip_apng_encode_device': (C.c_int, [C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_apng': (C.c_int, [vp, u32, u32, vp, u32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_frame_delta': (C.c_int, [C.c_int, u32, u32, C.c_int, C.POINTER(C.c_float)]),
+        'maray_hip_time_frame_delta_copy': (C.c_int, [C.c_int, u32, u32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        'maray_gen_animation': (C.c_int, [vp, C.POINTER(Texture), u32, C.POINTER(GenOpts), vp, u32, u32, u32, u32, C.c_char_p]),
         'maray_png_write': (C.c_int, [C.c_char_p, vp, u32, u32]),
         'maray_png_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
         'maray_image_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
@@ -530,6 +536,19 @@ class Context:
         _check(lib().maray_hip_render_png(self._h, w, h, vp_, n, C.byref(p), C.byref(sz)))
         return _take_bytes(p, sz)
 
+    def render_apng(self, w, h, frames, sub=1, fps=(25, 1), loops=0):
+        """n images as the bytes of one APNG, rendered and encoded on the device (maray_hip_render_apng).  frames: an
+        (n * sub, P) matrix of values, image i the shutter render over its `sub` rows (sub = 1: the plain render with that row);
+        or an int n for a program without parameters.  fps = (N, D) or N: every image shows for D / N seconds; loops = 0: for
+        ever."""
+        rows, vp_, keep = self._frames(frames)
+        if sub < 1 or rows % sub:
+            raise MarayError(-1, 'render_apng: frames must hold a whole number of images of %d rows' % sub)
+        num, den = _delay(fps)
+        p, sz = C.c_void_p(), C.c_size_t()
+        _check(lib().maray_hip_render_apng(self._h, w, h, vp_, rows // sub, sub, num, den, loops, C.byref(p), C.byref(sz)))
+        return _take_bytes(p, sz)
+
     def render_rows_device(self, w, h, y0, y1, d_rgb8=0, d_rgb64=0, stream=0):
         _check(lib().maray_hip_render_rows_device(self._h, w, h, y0, y1, d_rgb8 or None, d_rgb64 or None, stream or None))
 
@@ -605,6 +624,70 @@ def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_ki
     go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.encoder = backend, n_devices, samples, shutter, filter, encoder
     go.transfer = transfer
     _check(lib().maray_gen(scene._h, arr, n, C.byref(go), Report(report_kind, report_value), os.fsencode(path)))
+
+
+def _delay(fps):
+    """(delay_num, delay_den) of fps = N or (N, D): D / N seconds an image."""
+    n, d = fps if isinstance(fps, (tuple, list)) else (fps, 1)
+    return int(d), int(n)
+
+
+def gen_animation(scene, path, frames, fps=(25, 1), loops=0, textures=None, backend=BACKEND_AUTO, n_devices=0, samples=0, shutter=0, spans=None,
+                  filter=FILTER_BOX, transfer=TRANSFER_NONE):
+    """An animation of the scene as one APNG at `path`, rendered and encoded on one device (maray_gen_animation).  frames: an
+    (n, P) matrix, one row of values per image and one column per declared parameter, or a dict {name_or_id: sequence} -- the
+    parameters it does not name keep their current value.  fps, loops: as Context.render_apng; the other options as gen's
+    (shutter=n with spans: every image the mean of n sub-frames around its values).  The scene's values are as they were
+    afterwards."""
+    for k, v in (spans or {}).items():
+        scene.set_param_span(scene.param_index(k), v)
+    P = scene.param_count
+    if isinstance(frames, dict):
+        lengths = {len(v) for v in frames.values()}
+        if len(lengths) != 1:
+            raise MarayError(-1, 'gen_animation: the sequences of `frames` must be equally long')
+        a = np.empty((lengths.pop(), P), np.float64)
+        for p in range(P):
+            a[:, p] = scene.param_info(p)[3]
+        for k, v in frames.items():
+            a[:, scene.param_index(k)] = np.asarray(v, np.float64)
+    else:
+        a = np.ascontiguousarray(frames, np.float64)
+        if a.ndim != 2 or a.shape[1] != P:
+            raise MarayError(-1, 'gen_animation: frames must be an (n, %d) matrix: one column per declared parameter' % P)
+    arr, n, keep = _textures(textures)
+    go = GenOpts()
+    go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.transfer = backend, n_devices, samples, shutter, filter, transfer
+    num, den = _delay(fps)
+    _check(lib().maray_gen_animation(scene._h, arr, n, C.byref(go), a.ctypes.data if a.size else None, a.shape[0], num, den, loops, os.fsencode(path)))
+
+
+def frame_delta(d_prev, d_cur, w, h, device=0, stream=0):
+    """(x0, y0, x1, y1): the half-open bounding box of the pixels in which two packed (h, w, 3) uint8 rasters in device memory
+    (any alignment) differ, (0, 0, 0, 0) when none does (maray_hip_frame_delta); enqueued on `stream` and waited for."""
+    box = (C.c_uint32 * 4)()
+    _check(lib().maray_hip_frame_delta(device, d_prev or None, d_cur or None, w, h, stream or None, box))
+    return tuple(box)
+
+
+def apng_encode_device(d_frames, n, w, h, fps=(25, 1), loops=0, device=0, stream=0):
+    """n packed (h, w, 3) uint8 frames, 3 w h bytes apart in device memory (any alignment) -> the bytes of an APNG, encoded on
+    the device (maray_hip_apng_encode_device); enqueued on `stream` and waited for."""
+    num, den = _delay(fps)
+    p, sz = C.c_void_p(), C.c_size_t()
+    _check(lib().maray_hip_apng_encode_device(device, d_frames or None, n, w, h, num, den, loops, stream or None, C.byref(p), C.byref(sz)))
+    return _take_bytes(p, sz)
+
+
+def time_frame_delta(w, h, device=0, reps=10, with_copy=False):
+    """Average ms of the frame-delta kernels over two w x h rasters (maray_hip_time_frame_delta); with_copy: (that, the
+    average ms of a device-to-device copy of one raster's bytes timed in the same call)."""
+    ms, cp = C.c_float(), C.c_float()
+    if not with_copy:
+        _check(lib().maray_hip_time_frame_delta(device, w, h, reps, C.byref(ms)))
+        return ms.value
+    _check(lib().maray_hip_time_frame_delta_copy(device, w, h, reps, C.byref(ms), C.byref(cp)))
+    return ms.value, cp.value
 
 
 def _take_bytes(p, sz):

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "apng_device.hpp"
 #include "backend.hpp"
 #include "expr.hpp"
 #include "filter.hpp"
@@ -924,6 +925,88 @@ int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32
 }
 
 uint64_t maray_hip_png_bytes_to_host(void) { return png_bytes_to_host(); }
+
+// ---- animation (include/maray_hip.h) ---------------------------------------------------------------------------
+int maray_hip_frame_delta(int device, const void *d_prev, const void *d_cur, uint32_t w, uint32_t h, void *stream, uint32_t box[4])
+{
+    return guard([&] {
+        REQUIRE(d_prev && d_cur && box, "null argument");
+        REQUIRE(w && h, "empty image");
+        apng_check_frame(w, h);
+        frame_delta_once(device, (const unsigned char *)d_prev, (const unsigned char *)d_cur, w, h, (hipStream_t)stream, box);
+    });
+}
+
+int maray_hip_apng_encode_device(int device, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t delay_num,
+                                 uint32_t delay_den, uint32_t n_plays, void *stream, uint8_t **out, size_t *n_out)
+{
+    return guard([&] {
+        REQUIRE(out && n_out, "null argument");
+        *out = nullptr; *n_out = 0;
+        REQUIRE(d_frames, "null argument");
+        apng_check_timing(n_frames, delay_num, delay_den);
+        REQUIRE(w && h, "empty image");
+        apng_check_frame(w, h);
+        PngEncoderLease E(device);
+        ApngWriter W(*E.e, w, h, n_frames, delay_num, delay_den, n_plays);
+        const size_t pitch = (size_t)w * 3;
+        for (uint32_t i = 0; i < n_frames; i++) {
+            const unsigned char *frame = (const unsigned char *)d_frames + (size_t)i * pitch * h;
+            W.add_frame([&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
+                const hipError_t e = hipMemcpyAsync(d8, frame + (size_t)b0 * pitch, (size_t)(b1 - b0) * pitch, hipMemcpyDeviceToDevice, st);
+                if (e != hipSuccess) throw Error{MARAY_E_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)};
+            }, (hipStream_t)stream);
+        }
+        png_hand_over(W.finish(), out, n_out);
+    });
+}
+
+int maray_hip_render_apng(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                          uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, uint8_t **out, size_t *n_out)
+{
+    return guard([&] {
+        REQUIRE(out && n_out, "null argument");
+        *out = nullptr; *n_out = 0;
+        REQUIRE(c && c->backend, "null context");
+        apng_check_timing(n_images, delay_num, delay_den);
+        REQUIRE(w && h, "empty image");
+        check_rows(w, h, 0, h);
+        apng_check_frame(w, h);
+        check_samples(c, w, h, false, true);
+        // every row of every image, before the first launch
+        const size_t P = c->param_ranges.size() / 2;
+        for (uint32_t i = 0; i < n_images; i++) check_shutter(c, values ? values + (size_t)i * n_sub * P : nullptr, n_sub);
+        int device = 0;
+        {
+            std::lock_guard<std::mutex> lk(g_ctx_device_mutex);
+            auto it = g_ctx_device.find(c);
+            if (it == g_ctx_device.end()) throw Error{MARAY_E_ARG, "unknown context"};
+            device = it->second;
+        }
+        PngEncoderLease E(device);
+        ApngWriter W(*E.e, w, h, n_images, delay_num, delay_den, n_plays);
+        for (uint32_t i = 0; i < n_images; i++) {
+            const double *rows = values ? values + (size_t)i * n_sub * P : nullptr;
+            W.add_frame([&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
+                c->backend->render_device_shutter(w, h, RowBlocks::range(b0, b1), rows, n_sub, d8, st);
+            }, E->own_stream);
+        }
+        png_hand_over(W.finish(), out, n_out);
+    });
+}
+
+int maray_hip_time_frame_delta_copy(int device, uint32_t w, uint32_t h, int reps, float *ms_avg, float *copy_ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        *ms_avg = frame_delta_time(device, w, h, reps, copy_ms_avg);
+    });
+}
+
+int maray_hip_time_frame_delta(int device, uint32_t w, uint32_t h, int reps, float *ms_avg)
+{
+    return maray_hip_time_frame_delta_copy(device, w, h, reps, ms_avg, nullptr);
+}
 
 int maray_host_alloc(size_t bytes, void **out)
 {

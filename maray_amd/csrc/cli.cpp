@@ -6,8 +6,9 @@
 // the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
 // image the mean of N frames whose NAME covers SPAN around its value, averaged on the device), --linear (samples and frames
 // are averaged in linear light: include/maray_hip.h, "transfer"), --encoder {host,device} (who
-// writes the PNG: the host's zlib, or the device encoder, per --animate frame too).  -c/--cpus is parsed and
-// ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
+// writes the PNG: the host's zlib, or the device encoder, per --animate frame too), --apng (--animate writes ONE file, an APNG
+// encoded on the device frame by frame: include/maray_hip.h, "animation"; --fps N[/D] and --loops N are its timing).
+// -c/--cpus is parsed and ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +35,11 @@ static void usage()
             "                               declared with (default: any value)\n"
             "      --animate <name=a:b:n>   n images, `name` going from a to b in equal steps; --output needs a `%%d`\n"
             "                               conversion (`frame%%03d.png`), numbered from 0\n"
+            "      --apng                   With --animate: one file, an animated PNG (APNG) whose frames are encoded on the GPU, of\n"
+            "                               every frame after the first only the rectangle that changed; --output takes no `%%d`,\n"
+            "                               --gpus must be 1 or absent\n"
+            "      --fps <n[/d]>            --apng: n / d images per second (default: 25)\n"
+            "      --loops <n>              --apng: how often the animation plays; 0 = for ever (default: 0)\n"
             "      --shutter <name=span>    Motion blur (repeatable): every image is the mean of N frames in which `name` covers\n"
             "                               an interval of width span centred on its value; declares `name` if -p did not\n"
             "      --shutter-samples <n>    N = 1, 2, 4, 8, 16, 32 or 64 (default: 8 once a --shutter is given)\n"
@@ -90,6 +96,8 @@ int main(int argc, char **argv)
     std::vector<Param> spans;           // --shutter: name, value = the span
     uint32_t shutter_samples = 0;
     bool linear = false;                // --linear
+    bool apng = false;                  // --apng
+    uint32_t fps_num = 25, fps_den = 1, loops = 0;
     maray_gen_opts go;
     memset(&go, 0, sizeof go);
     go.backend = MARAY_BACKEND_AUTO;
@@ -117,6 +125,29 @@ int main(int argc, char **argv)
             else { fprintf(stderr, "Error: --filter takes box or tent, not `%s`\n", f.c_str()); usage(); return 2; }
         }
         else if (a == "--linear") linear = true;
+        else if (a == "--apng") apng = true;
+        else if (a == "--fps") {
+            const std::string f = val();
+            char *rest = nullptr;
+            const unsigned long n = strtoul(f.c_str(), &rest, 10);
+            unsigned long d = 1;
+            bool ok = !f.empty() && f[0] >= '0' && f[0] <= '9' && rest && (*rest == 0 || *rest == '/');
+            if (ok && *rest == '/') {
+                const char *t = rest + 1;
+                ok = *t >= '0' && *t <= '9';
+                d = strtoul(t, &rest, 10);
+                ok = ok && rest && !*rest;
+            }
+            if (!ok || n < 1 || n > 65535 || d < 1 || d > 65535) { fprintf(stderr, "Error: --fps takes N or N/D with N and D in 1 .. 65535, not `%s`\n", f.c_str()); usage(); return 2; }
+            fps_num = (uint32_t)n; fps_den = (uint32_t)d;
+        }
+        else if (a == "--loops") {
+            const std::string f = val();
+            char *rest = nullptr;
+            const unsigned long n = strtoul(f.c_str(), &rest, 10);
+            if (f.empty() || f[0] < '0' || f[0] > '9' || !rest || *rest || n > 0xFFFFFFFFul) { fprintf(stderr, "Error: --loops takes a count >= 0, not `%s`\n", f.c_str()); usage(); return 2; }
+            loops = (uint32_t)n;
+        }
         else if (a == "--encoder") {
             const std::string e = val();
             if (e == "host") go.encoder = MARAY_ENCODER_HOST;
@@ -165,7 +196,10 @@ int main(int argc, char **argv)
     }
     if (input.empty() || output.empty()) { usage(); return 2; }
     if (go.filter == MARAY_FILTER_TENT && go.samples < 2) { fprintf(stderr, "Error: --filter tent needs -s 2, 4 or 8\n"); usage(); return 2; }
-    if (frames && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
+    if (apng && !frames) { fprintf(stderr, "Error: --apng writes an animation: it needs --animate NAME=FROM:TO:FRAMES\n"); return 2; }
+    if (apng && output.find('%') != std::string::npos) { fprintf(stderr, "Error: --apng writes one file: --output must not contain a `%%d` conversion\n"); return 2; }
+    if (apng && go.n_devices > 1) { fprintf(stderr, "Error: --apng renders and encodes on one device: --gpus must be 1\n"); return 2; }
+    if (frames && !apng && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
 
     maray_scene *scene = nullptr;
     if (maray_scene_open(input.c_str(), &scene)) { fprintf(stderr, "Error: %s\n", maray_last_error()); return 1; }
@@ -223,9 +257,23 @@ int main(int argc, char **argv)
     maray_report rep{MARAY_REPORT_DURATION_MS, 500};   // Report::Duration(500 ms), examples/maray.rs:77-79
     int rc = 0;
     if (!frames) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());
-    for (uint32_t f = 0; f < frames && !rc; f++) {
-        // FROM + i (TO - FROM) / (FRAMES - 1) in f64; the last frame is TO itself (the range's end, whatever the rounding)
-        const double v = frames == 1 ? from : f == frames - 1 ? to : from + (double)f * (to - from) / (double)(frames - 1);
+    // FROM + i (TO - FROM) / (FRAMES - 1) in f64; the last frame is TO itself (the range's end, whatever the rounding)
+    auto frame_value = [&](uint32_t f) { return frames == 1 ? from : f == frames - 1 ? to : from + (double)f * (to - from) / (double)(frames - 1); };
+    if (apng) {
+        // one row of values per image: the animated parameter's, and every other parameter's current value
+        uint32_t n_par = 0;
+        maray_scene_param_count(scene, &n_par);
+        std::vector<double> values((size_t)frames * n_par);
+        for (uint32_t f = 0; f < frames; f++)
+            for (uint32_t k = 0; k < n_par; k++) {
+                double v = 0.0;
+                maray_scene_param_info(scene, k, nullptr, nullptr, nullptr, &v);
+                values[(size_t)f * n_par + k] = k == anim_index ? frame_value(f) : v;
+            }
+        rc = maray_gen_animation(scene, tex.data(), (uint32_t)tex.size(), &go, values.data(), frames, fps_den, fps_num, loops, output.c_str());
+    }
+    for (uint32_t f = 0; !apng && f < frames && !rc; f++) {
+        const double v = frame_value(f);
         char path[4096];
         snprintf(path, sizeof path, output.c_str(), (int)f);
         rc = maray_scene_set_param(scene, anim_index, v);

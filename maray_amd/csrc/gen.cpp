@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "apng_device.hpp"
 #include "backend.hpp"
 #include "host_pipe.hpp"
 #include "lower.hpp"
@@ -226,6 +227,28 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
     return MARAY_OK;
 }
 
+// The name a call's program and contexts are kept under: the scene's name, the textures' sizes and bytes, the back-end asked
+// for and what the contexts reduce with.  A texture without a raster: MARAY_E_ARG.
+static int gen_program_key(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, uint32_t samples,
+                           uint32_t filter, uint32_t transfer, std::string &key)
+{
+    uint64_t h[2];
+    scene_cache_key(s, h);
+    for (uint32_t i = 0; i < n_tex; i++) {
+        const uint32_t dims[2] = {tex[i].w, tex[i].h};
+        hash128(dims, sizeof dims, h);
+        if (!tex[i].rgb && (uint64_t)tex[i].w * tex[i].h) return fail_with(MARAY_E_ARG, "null texture raster");
+        hash128(tex[i].rgb, (size_t)tex[i].w * tex[i].h * 3, h);
+    }
+    char buf[64];
+    snprintf(buf, sizeof buf, "%016llx%016llx/%u/%u", (unsigned long long)h[0], (unsigned long long)h[1], n_tex, opts ? opts->backend : (uint32_t)MARAY_BACKEND_AUTO);
+    key = buf;
+    if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
+    if (filter == MARAY_FILTER_TENT) key += "/tent";             // (box keeps its key: the two are kept side by side)
+    if (transfer == MARAY_TRANSFER_SRGB) key += "/srgb";         // (and so does NONE)
+    return MARAY_OK;
+}
+
 // gen_to_image; with `png` the tiles are rendered into each worker's encoder on its device and encoded there (rgb8 is null:
 // no raster crosses to the host), else they land in rgb8
 static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
@@ -251,22 +274,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
     if (!w || !h) return MARAY_OK;
     // the program of this call: remembered from an earlier one, or lowered now
     std::string key;
-    {
-        uint64_t h[2];
-        scene_cache_key(s, h);
-        for (uint32_t i = 0; i < n_tex; i++) {
-            const uint32_t dims[2] = {tex[i].w, tex[i].h};
-            hash128(dims, sizeof dims, h);
-            if (!tex[i].rgb && (uint64_t)tex[i].w * tex[i].h) return fail_with(MARAY_E_ARG, "null texture raster");
-            hash128(tex[i].rgb, (size_t)tex[i].w * tex[i].h * 3, h);
-        }
-        char buf[64];
-        snprintf(buf, sizeof buf, "%016llx%016llx/%u/%u", (unsigned long long)h[0], (unsigned long long)h[1], n_tex, opts ? opts->backend : (uint32_t)MARAY_BACKEND_AUTO);
-        key = buf;
-        if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
-        if (filter == MARAY_FILTER_TENT) key += "/tent";             // (box keeps its key: the two are kept side by side)
-        if (transfer == MARAY_TRANSFER_SRGB) key += "/srgb";         // (and so does NONE)
-    }
+    if (const int rc = gen_program_key(s, tex, n_tex, opts, samples, filter, transfer, key)) return rc;
     int n_dev_avail = 0;
     maray_hip_device_count(&n_dev_avail);
     uint32_t n_dev = opts && opts->n_devices ? opts->n_devices : (uint32_t)(n_dev_avail > 0 ? n_dev_avail : 1);
@@ -502,5 +510,114 @@ extern "C" int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_
     int rc = maray_gen_to_image(s, tex, n_tex, opts, report, gen_report, &g, img.p, w, h);
     if (rc) return rc;
     return maray_png_write(png_path, img.p, w, h);   // :1212
+    });
+}
+
+// ---- gen for an animation (include/maray_hip.h, "animation") --------------------------------------------------------
+extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                                   uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path)
+{
+    if (!s || !path) return fail_with(MARAY_E_ARG, "null argument");
+    if (!n_images) return fail_with(MARAY_E_ARG, "an animation needs at least one image");
+    if (delay_num > 65535 || delay_den > 65535) return fail_with(MARAY_E_ARG, "delay_num and delay_den must fit 16 bits");
+    return gen_guard([&]() -> int {
+    // the option words, as gen_to_image checks them
+    const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
+    if (transfer != MARAY_TRANSFER_NONE && transfer != MARAY_TRANSFER_SRGB) return fail_with(MARAY_E_ARG, "unknown transfer");
+    const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
+    if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail_with(MARAY_E_ARG, "samples must be 0, 1, 2, 4 or 8");
+    const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
+    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT) return fail_with(MARAY_E_ARG, "unknown filter");
+    if (filter == MARAY_FILTER_TENT && samples == 1) return fail_with(MARAY_E_ARG, "the tent filter needs samples = 2, 4 or 8");
+    const uint32_t shutter = opts && opts->shutter ? opts->shutter : 1u;
+    if (shutter > 64 || (shutter & (shutter - 1))) return fail_with(MARAY_E_ARG, "shutter must be 0, 1, 2, 4, 8, 16, 32 or 64");
+    if (opts && opts->n_devices > 1) return fail_with(MARAY_E_ARG, "an animation is rendered and encoded on one device: n_devices must be 0 or 1");
+    uint32_t w = 0, h = 0;
+    maray_scene_size(s, &w, &h);
+    if (!w || !h) return fail_with(MARAY_E_ARG, "empty image");
+    if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
+    if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
+        return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
+    apng_check_frame(w, h);
+    uint32_t n_par = 0;
+    if (const int rc = maray_scene_param_count(s, &n_par)) return rc;
+    if (n_par && !values) return fail_with(MARAY_E_ARG, "null argument: a scene with parameters needs the images' values");
+
+    // the program: the entry maray_gen_to_image keeps for this scene, or lowered now and kept
+    std::string key;
+    if (const int rc = gen_program_key(s, tex, n_tex, opts, samples, filter, transfer, key)) return rc;
+    std::shared_ptr<GenEntry> entry = gen_cache_find(key);
+    if (!entry) {
+        maray_tape *tape = nullptr;
+        int rc;
+        if (samples > 1) {
+            std::unique_ptr<maray_scene, void (*)(maray_scene *)> ss(scene_supersampled_copy(s, samples), maray_scene_free);
+            rc = maray_lower(ss.get(), nullptr, &tape);
+        } else
+            rc = maray_lower(s, nullptr, &tape);
+        if (rc) return rc;
+        auto fresh = std::make_shared<GenEntry>();
+        fresh->key = key; fresh->tape = tape; fresh->samples = samples; fresh->filter = filter; fresh->transfer = transfer;
+        entry = gen_cache_insert(fresh);
+    }
+    maray_program prog;
+    maray_tape_program(entry->tape, &prog);
+    const uint32_t P = prog.version == MARAY_TAPE_VERSION_PARAMS ? prog.n_params : 0u;      // the scene's count, or 0: no op reads one
+    if (P && P != n_par) return fail_with(MARAY_E_INTERNAL, "the program's parameter count is not the scene's");
+
+    // Every image's rows of values, before anything is launched.  With a shutter the sub-frames are the scene's
+    // maray_scene_shutter_values around the image's row: the row is set on the scene (which checks it against the declared
+    // ranges), and the values the scene had are put back however the call ends.
+    bool any_span = false;
+    for (uint32_t p = 0; p < n_par; p++) {
+        double sp = 0.0;
+        if (const int rc = maray_scene_param_span(s, p, &sp)) return rc;
+        any_span = any_span || sp > 0.0;
+    }
+    const uint32_t n_sub = shutter > 1 && any_span && P ? shutter : 1u;
+    std::vector<double> rows;
+    if (P && n_sub == 1) rows.assign(values, values + (size_t)n_images * P);
+    else if (P) {
+        struct Restore {
+            maray_scene *s; std::vector<double> saved;
+            ~Restore() { for (uint32_t p = 0; p < (uint32_t)saved.size(); p++) (void)maray_scene_set_param(s, p, saved[p]); }
+        } keep{const_cast<maray_scene *>(s), std::vector<double>(n_par)};
+        for (uint32_t p = 0; p < n_par; p++)
+            if (const int rc = maray_scene_param_info(s, p, nullptr, nullptr, nullptr, &keep.saved[p])) { keep.saved.resize(p); return rc; }
+        rows.resize((size_t)n_images * n_sub * P);
+        for (uint32_t i = 0; i < n_images; i++) {
+            for (uint32_t p = 0; p < n_par; p++)
+                if (maray_scene_set_param(keep.s, p, values[(size_t)i * n_par + p]))
+                    return fail_with(MARAY_E_ARG, "image " + std::to_string(i) + ": " + maray_last_error());
+            if (const int rc = maray_scene_shutter_values(s, n_sub, rows.data() + (size_t)i * n_sub * P)) return rc;
+        }
+    }
+
+    // the context: the one an earlier call left for device 0, or a new one; kept for the next call
+    maray_ctx_opts co;
+    memset(&co, 0, sizeof co);
+    co.backend = opts ? opts->backend : MARAY_BACKEND_AUTO;
+    co.samples = samples;
+    co.filter = filter;
+    co.transfer = transfer;
+    co.hint_mpixels = (uint32_t)std::min<uint64_t>(0xFFFFFFFFu, (((uint64_t)w * h * samples * samples) >> 20) + 1);
+    const int dev = 0;
+    const IdleCtx kept = gen_cache_take(*entry, dev, co.backend == MARAY_BACKEND_AUTO, co.hint_mpixels);
+    maray_ctx *ctx = kept.ctx;
+    if (!ctx)
+        if (const int rc = maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx)) return rc;
+    uint8_t *bytes = nullptr;
+    size_t n_bytes = 0;
+    const int rc = maray_hip_render_apng(ctx, w, h, P ? rows.data() : nullptr, n_images, n_sub, delay_num, delay_den, n_plays, &bytes, &n_bytes);
+    if (rc) { const std::string msg = maray_last_error(); maray_hip_ctx_free(ctx); return fail_with(rc, msg); }      // (a context that failed is not kept)
+    gen_cache_give(*entry, dev, ctx, kept.ctx ? kept.hint_mpixels : co.hint_mpixels);
+    std::unique_ptr<uint8_t, void (*)(void *)> own(bytes, maray_free);
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail_with(MARAY_E_IO, std::string("cannot create ") + path);
+    const size_t n = fwrite(bytes, 1, n_bytes, f);
+    fclose(f);
+    if (n != n_bytes) return fail_with(MARAY_E_IO, "short write");
+    set_last_error("");
+    return MARAY_OK;
     });
 }

@@ -45,4 +45,56 @@ inline std::vector<uint8_t> png_file(uint32_t w, uint32_t h, const uint8_t *z, s
     return out;
 }
 
+// ---- APNG (the animation writer, apng_device.cpp): a PNG whose IDAT image is frame 0 and whose later frames are complete
+// zlib streams of sub-rectangles in fdAT chunks.  fcTL and fdAT share one run of sequence numbers, 0, 1, 2, ...
+constexpr size_t PNG_CHUNK_MAX = (size_t)1 << 30;
+
+inline void put_be16(std::vector<uint8_t> &v, uint32_t x) { v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x); }
+
+// signature, IHDR, acTL
+inline void apng_begin(std::vector<uint8_t> &out, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t n_plays)
+{
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    out.insert(out.end(), sig, sig + 8);
+    std::vector<uint8_t> d;
+    put_be32(d, w); put_be32(d, h);
+    d.push_back(8); d.push_back(2); d.push_back(0); d.push_back(0); d.push_back(0);
+    chunk(out, "IHDR", d.data(), d.size());
+    d.clear();
+    put_be32(d, n_frames); put_be32(d, n_plays);
+    chunk(out, "acTL", d.data(), d.size());
+}
+
+// fcTL of a bw x bh frame at (x, y): dispose NONE, blend SOURCE; takes the next sequence number
+inline void apng_fctl(std::vector<uint8_t> &out, uint32_t &seq, uint32_t bw, uint32_t bh, uint32_t x, uint32_t y, uint32_t delay_num, uint32_t delay_den)
+{
+    std::vector<uint8_t> d;
+    put_be32(d, seq++); put_be32(d, bw); put_be32(d, bh); put_be32(d, x); put_be32(d, y);
+    put_be16(d, delay_num); put_be16(d, delay_den);
+    d.push_back(0); d.push_back(0);
+    chunk(out, "fcTL", d.data(), d.size());
+}
+
+// frame 0's stream: IDAT chunks of at most `limit` bytes
+inline void apng_idat(std::vector<uint8_t> &out, const uint8_t *z, size_t zn, size_t limit = PNG_CHUNK_MAX)
+{
+    for (size_t off = 0; off < zn; off += limit) chunk(out, "IDAT", z + off, std::min(limit, zn - off));
+}
+
+// a later frame's stream: fdAT chunks of at most `limit` bytes, each a sequence number and then up to limit - 4 bytes of it
+inline void apng_fdat(std::vector<uint8_t> &out, uint32_t &seq, const uint8_t *z, size_t zn, size_t limit = PNG_CHUNK_MAX)
+{
+    std::vector<uint8_t> d;
+    for (size_t off = 0; off < zn; off += limit - 4) {
+        const size_t n = std::min(limit - 4, zn - off);
+        d.clear();
+        d.reserve(n + 4);
+        put_be32(d, seq++);
+        d.insert(d.end(), z + off, z + off + n);
+        chunk(out, "fdAT", d.data(), d.size());
+    }
+}
+
+inline void apng_end(std::vector<uint8_t> &out) { chunk(out, "IEND", nullptr, 0); }
+
 }   // namespace maray

@@ -95,6 +95,13 @@ uint32_t PngEncoder::band_rows(uint32_t w) const
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, ((uint64_t)1 << 30) / row));
 }
 
+unsigned char *PngEncoder::band_buffer(size_t bytes)
+{
+    HIP_TRY(hipSetDevice(device));
+    grow(raster, raster_cap, bytes);
+    return raster;
+}
+
 void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out)
 {
     if (!rows || !w) return;
@@ -177,6 +184,7 @@ void png_encoder_release(PngEncoder *e)
 }
 
 uint64_t png_bytes_to_host() { return g_bytes_to_host.load(); }
+void png_count_bytes_to_host(uint64_t n) { g_bytes_to_host += n; }
 
 void png_check_size(uint32_t w, uint32_t h)
 {
@@ -184,16 +192,16 @@ void png_check_size(uint32_t w, uint32_t h)
         throw Error{MARAY_E_LIMIT, "image too large for the PNG writer"};
 }
 
-std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces)
+std::vector<uint8_t> png_close_stream(uint32_t h_end, const std::vector<const PngPiece *> &pieces)
 {
     size_t zn = 2 + 5 + 4;
-    uint32_t y = 0;
+    uint32_t y = pieces.empty() ? 0 : pieces.front()->y0;
     for (const PngPiece *p : pieces) {
         if (p->y0 != y || p->y1 <= p->y0) throw Error{MARAY_E_INTERNAL, "device PNG encoder: the pieces do not cover the image in row order"};
         y = p->y1;
         zn += p->z.size();
     }
-    if (y != h) throw Error{MARAY_E_INTERNAL, "device PNG encoder: the pieces do not cover the image"};
+    if (pieces.empty() || y != h_end) throw Error{MARAY_E_INTERNAL, "device PNG encoder: the pieces do not cover the image"};
     std::vector<uint8_t> z;
     z.reserve(zn);
     z.push_back(0x78); z.push_back(0x01);
@@ -206,6 +214,13 @@ std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<cons
     static const uint8_t last[5] = {0x01, 0x00, 0x00, 0xFF, 0xFF};       // the final, empty stored block
     z.insert(z.end(), last, last + 5);
     put_be32(z, (s2 << 16) | s1);
+    return z;
+}
+
+std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces)
+{
+    if (!pieces.empty() && pieces.front()->y0 != 0) throw Error{MARAY_E_INTERNAL, "device PNG encoder: the pieces do not cover the image in row order"};
+    const std::vector<uint8_t> z = png_close_stream(h, pieces);
     return png_file(w, h, z.data(), z.size());
 }
 

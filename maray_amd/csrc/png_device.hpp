@@ -83,6 +83,7 @@ struct PngEncoder {
     ~PngEncoder();
     PngEncoder(const PngEncoder &) = delete;
     uint32_t band_rows(uint32_t w) const;
+    unsigned char *band_buffer(size_t bytes);                    // `raster`, grown to hold `bytes` (the animation writer's crops)
     // rows x w pixels at d_rgb8 (device memory, any alignment), enqueued on st and waited for; appends to `out`
     void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out);
     // rows [y0, y1) band by band: render(b0, b1, d8, st) enqueues the rows' RGB8 into d8 on st
@@ -106,8 +107,12 @@ struct PngEncoderLease {
 uint64_t png_bytes_to_host();
 // w, h within what the writers take (else Error MARAY_E_LIMIT), before anything is launched
 void png_check_size(uint32_t w, uint32_t h);
-// The file: 78 01, the pieces' segments in row order (they cover [0, h)), the final empty stored block, the Adler-32 combined
-// from the pieces' parts; in the container (png_container.hpp).
+// payload bytes another writer on an encoder's device has copied to the host (the animation writer's boxes)
+void png_count_bytes_to_host(uint64_t n);
+// The zlib stream of rows [pieces.front()->y0, h_end) : 78 01, the pieces' segments in row order (each starts where the one
+// before it ended, the last ends at h_end), the final empty stored block, the Adler-32 combined from the pieces' parts.
+std::vector<uint8_t> png_close_stream(uint32_t h_end, const std::vector<const PngPiece *> &pieces);
+// The file: png_close_stream of pieces that cover [0, h), in the container (png_container.hpp).
 std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces);
 // Average ms of compress + scan + gather over the caller's w x rows raster in device memory, as one band (measurements);
 // *stream_bytes = the bytes of the gathered stream.
