@@ -171,6 +171,9 @@ int maray_tape_get_info(const maray_tape *t, maray_tape_info *out);
  * version-2 one the scene always had); and the range that travels with it. */
 int maray_tape_param_count(const maray_tape *t, uint32_t *n);
 int maray_tape_param_range(const maray_tape *t, uint32_t index, double *lo, double *hi);
+/* The program's REFINE section (include/maray_tape.h, maray_refine); n_ops = 0 when it has none.  Pointers valid until
+ * maray_tape_free. */
+int maray_tape_refine(const maray_tape *t, maray_refine *out);
 
 /* ---- tape-level device ABI (what a Rust `RenderMethod::Hip` arm binds) --------
  * Replaces par_gen_to_image / wasm_par_gen_to_image (src/render.rs:35-192) and
@@ -409,6 +412,33 @@ const char *maray_hip_kernel_name(const maray_ctx *c);
  * unchanged (MARAY_JIT_ROW_REUSE=0 in the environment when the context is created: a ROW pass per launch), so a launch
  * need not add to either; the interpreters' contexts report 0, 0. */
 int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels);
+
+/* ---- guard refinement (include/maray_tape.h, maray_refine) ----------------------------------------------------------
+ * maray_hip_ctx_create with the program's REFINE section beside it (NULL, or n_ops = 0: exactly maray_hip_ctx_create).
+ * A MARAY_BACKEND_JIT context then runs maray_jit_refine behind every ROW pass, on the same stream and into the same
+ * guard words, in place: on the rectangles whose geometric bit is set it evaluates the section and clears the bits it
+ * proves zero.  The words belong to the set of ROW outputs the pass filled, so the refinement is kept, reused and
+ * dropped with them.  MARAY_JIT_GUARD_REFINE=0 in the environment when the context is created: no such launch (rasters
+ * are identical either way; not part of a code key).  The interpreters ignore the section. */
+int maray_hip_ctx_create_refined(int device, const maray_program *prog, const maray_refine *refine, const maray_texture *tex, uint32_t n_tex,
+                                 const maray_ctx_opts *opts, maray_ctx **out);
+/* Source of maray_jit_refine for a program and its REFINE section (free with maray_free); the empty string when the
+ * section gives no kernel (no section, or no guard words).  Needs no GPU. */
+int maray_jit_source_refine(const maray_program *prog, const maray_refine *refine, char **src_out);
+/* ... and its gfx950 code object (free with maray_free; *len_out = 0 when there is no kernel), built once and kept like
+ * the other modules', under a key of its own made of its text.  Needs no GPU. */
+int maray_jit_build_refine(const maray_program *prog, const maray_refine *refine, void **code_out, size_t *len_out);
+/* Test access: how MARAY_BACKEND_JIT keeps the program's guards.  pos[g] = the bit of guard g (y value n_yvals - *n_guards + g)
+ * in a rectangle's words, -1 for a guard derived from other guards' bits (at most `cap` entries are written); *n_words =
+ * 64-bit words per rectangle (0: the guards are not kept as bits), *gw x *gh = the rectangle in pixels x rows.  Needs no GPU. */
+int maray_jit_guard_layout(const maray_program *prog, int32_t *pos, uint32_t cap, uint32_t *n_guards, uint32_t *n_words, uint32_t *gw, uint32_t *gh);
+/* How many maray_jit_refine passes the context has enqueued since it was created (0 for an interpreter's context). */
+int maray_hip_refine_count(const maray_ctx *c, uint64_t *refine_passes);
+/* Test access: the guard words of the set of ROW outputs the most recent launch used, copied to the host after everything
+ * enqueued on the context so far has completed.  *n_words = words in the set (rectangles x words per rectangle, the
+ * rectangles of a group of rows adjacent), *words_per_rect = words per rectangle; at most `cap` words are copied.
+ * MARAY_E_ARG for a context without guard words or before its first launch. */
+int maray_hip_debug_guard_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

@@ -140,4 +140,26 @@ typedef struct maray_program {
     const double *param_ranges;   /* n_params pairs lo, hi (lo <= hi, no NaN; -inf, +inf = any value, NaN included) */
 } maray_program;
 
+/* The REFINE section of a lowered program: a third straight-line section, with a constant pool of its own, that an
+ * evaluator which keeps the guards as bits per rectangle of pixels may run behind the ROW section's guards.  Same op set
+ * and operands as the ROW section (XMIN / XMAX / YMIN / YMAX = the rectangle; no Y, no X, no YVAL).  OUT k, k the index
+ * of a guard y value, writes a SECOND upper bound of what guard k guards, over the same rectangle: 0 proves the guarded
+ * conjunction +0.0 on every pixel of the rectangle, like the guard's own 0 does.  The bit an evaluator keeps for guard
+ * k may be ANDed with (OUT k != 0); a guard without an OUT keeps its bit.
+ * It bounds the factors the ROW section's guards treat as unknown -- Step(Sin(a)) with a proven NaN-free and inside the
+ * bounded-Sin range: with [lo, hi] the interval of a over the rectangle, the factor is 0 throughout when
+ * fl(hi - lo) < 3.0 and sin(lo) < 0 and sin(hi) < 0, and 1 throughout when both are > 0 -- so it costs libm bodies and
+ * is meant for the rectangles whose guard bit is set.  It reads only parameters that the ROW section reads too
+ * (row_param_mask): what is valid for a set of ROW outputs is valid for their refinement.
+ * It travels beside maray_program, not inside it (the struct above is what version 2 and 3 callers hand in, byte for
+ * byte); a program has one or has none (n_ops = 0), and every evaluator may ignore it: results are identical. */
+typedef struct maray_refine {
+    uint32_t n_consts;
+    const double *consts;
+    uint32_t n_ops;
+    const uint64_t *ops;
+    uint32_t n_slots;
+    uint32_t n_outs;         /* OUT ops: guards that have a second bound */
+} maray_refine;
+
 #endif

@@ -23,6 +23,12 @@ class MarayError(RuntimeError):
         self.code = code
 
 
+class Refine(C.Structure):
+    """maray_refine (include/maray_tape.h): a program's REFINE section, beside its Program (whose layout is unchanged)."""
+    _fields_ = [('n_consts', C.c_uint32), ('consts', C.POINTER(C.c_double)), ('n_ops', C.c_uint32), ('ops', C.POINTER(C.c_uint64)),
+                ('n_slots', C.c_uint32), ('n_outs', C.c_uint32)]
+
+
 class Program(C.Structure):
     _fields_ = [('version', C.c_uint32), ('n_consts', C.c_uint32), ('consts', C.POINTER(C.c_double)),
                 ('n_row_ops', C.c_uint32), ('row_ops', C.POINTER(C.c_uint64)), ('n_row_slots', C.c_uint32),
@@ -129,6 +135,14 @@ def lib():
         'maray_hip_device_count': (C.c_int, [C.POINTER(C.c_int)]),
         'maray_hip_ctx_create': (C.c_int, [C.c_int, C.POINTER(Program), C.POINTER(Texture), u32, C.POINTER(CtxOpts),
                                            C.POINTER(vp)]),
+        'maray_hip_ctx_create_refined': (C.c_int, [C.c_int, C.POINTER(Program), C.POINTER(Refine), C.POINTER(Texture), u32, C.POINTER(CtxOpts),
+                                                   C.POINTER(vp)]),
+        'maray_tape_refine': (C.c_int, [vp, C.POINTER(Refine)]),
+        'maray_jit_source_refine': (C.c_int, [C.POINTER(Program), C.POINTER(Refine), C.POINTER(vp)]),
+        'maray_jit_build_refine': (C.c_int, [C.POINTER(Program), C.POINTER(Refine), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_jit_guard_layout': (C.c_int, [C.POINTER(Program), vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+        'maray_hip_refine_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_hip_debug_guard_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
         'maray_hip_ctx_free': (None, [vp]),
         'maray_hip_render_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
         'maray_hip_render_tiles': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, TILE_FN, vp]),
@@ -370,6 +384,8 @@ class Tape:
         self.info = {n: getattr(ti, n) for n, _ in TapeInfo._fields_ if n not in ('op_histogram', 'row_params_words')}
         self.info['op_histogram'] = list(ti.op_histogram)
         self.info['row_params'] = ti.row_params_words[0] | (ti.row_params_words[1] << 32)      # bit p: a ROW op reads PARAM p
+        self.refine = Refine()          # the REFINE section (n_ops = 0: none); a Context made from this tape takes it along
+        _check(lib().maray_tape_refine(self._h, C.byref(self.refine)))
 
     def __del__(self):
         if getattr(self, '_h', None):
@@ -400,6 +416,42 @@ class Tape:
         v = C.c_int()
         _check(lib().maray_jit_code_cached(C.byref(self.program), C.byref(v)))
         return bool(v.value)
+
+    def jit_build_refine(self):
+        """The gfx950 code object of maray_jit_refine (bytes; b'' when there is no kernel).  Needs no GPU."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(lib().maray_jit_build_refine(C.byref(self.program), C.byref(self.refine), C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value) if n.value else b''
+        finally:
+            if p:
+                lib().maray_free(p)
+
+    def guard_layout(self):
+        """(pos, words, gw, gh) of maray_jit_guard_layout: pos[g] = bit of guard g in a rectangle's words (-1: derived), 64-bit
+        words per rectangle, and the rectangle in pixels x rows."""
+        n, nw, gw, gh = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().maray_jit_guard_layout(C.byref(self.program), None, 0, C.byref(n), C.byref(nw), C.byref(gw), C.byref(gh)))
+        pos = np.zeros(n.value, np.int32)
+        _check(lib().maray_jit_guard_layout(C.byref(self.program), pos.ctypes.data, n.value, C.byref(n), C.byref(nw), C.byref(gw), C.byref(gh)))
+        return pos, nw.value, gw.value, gh.value
+
+    def refine_arrays(self):
+        """(consts, ops, n_slots) of the REFINE section as numpy copies; None when the program has none."""
+        r = self.refine
+        if not r.n_ops:
+            return None
+        return (np.ctypeslib.as_array(r.consts, shape=(r.n_consts,)).copy(), np.ctypeslib.as_array(r.ops, shape=(r.n_ops,)).copy(), r.n_slots)
+
+    @property
+    def jit_source_refine(self):
+        """Source of maray_jit_refine; '' when the program gives none (maray_jit_source_refine)."""
+        p = C.c_void_p()
+        _check(lib().maray_jit_source_refine(C.byref(self.program), C.byref(self.refine), C.byref(p)))
+        try:
+            return C.string_at(p).decode()
+        finally:
+            lib().maray_free(p)
 
     def arrays(self):
         """(consts, row_ops, pix_ops) as numpy copies."""
@@ -452,7 +504,9 @@ class Context:
         o.filter = filter
         o.transfer = transfer
         h = C.c_void_p()
-        _check(lib().maray_hip_ctx_create(device, C.byref(tape.program), arr, n, C.byref(o), C.byref(h)))
+        refine = getattr(tape, 'refine', None)          # (a hand-made program has none)
+        _check(lib().maray_hip_ctx_create_refined(device, C.byref(tape.program), C.byref(refine) if refine is not None else None, arr, n,
+                                                  C.byref(o), C.byref(h)))
         self._h = h
         self._tape = tape
 
@@ -572,6 +626,22 @@ class Context:
     @property
     def kernel_name(self):
         return lib().maray_hip_kernel_name(self._h).decode()
+
+    @property
+    def refine_count(self):
+        """maray_jit_refine passes this context has enqueued so far (maray_hip_refine_count)."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_refine_count(self._h, C.byref(n)))
+        return n.value
+
+    def debug_guard_words(self):
+        """Test access (maray_hip_debug_guard_words): the guard words of the set the last launch used, (rectangles, words per
+        rectangle) uint64, the rectangles of a group of rows adjacent."""
+        n, per = C.c_size_t(), C.c_uint32()
+        _check(lib().maray_hip_debug_guard_words(self._h, None, 0, C.byref(n), C.byref(per)))
+        out = np.zeros(n.value, np.uint64)
+        _check(lib().maray_hip_debug_guard_words(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(per)))
+        return out.reshape(-1, per.value)
 
     @property
     def launch_counts(self):

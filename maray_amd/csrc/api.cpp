@@ -273,6 +273,28 @@ void validate_program(const maray_program &p)
     check(p.pix_ops, p.n_pix_ops, p.n_pix_slots, true);
 }
 
+// A REFINE section handed in beside a program: the ROW section's checks (no X, no YVAL), no Y either, and every OUT names a
+// guard of the program.
+void validate_refine(const maray_program &p, const maray_refine &r)
+{
+    if (!r.ops || (r.n_consts && !r.consts)) throw Error{MARAY_E_ARG, "null section pointer"};
+    maray_program q = p;
+    q.n_consts = r.n_consts; q.consts = r.consts;
+    q.n_row_ops = r.n_ops; q.row_ops = r.ops; q.n_row_slots = r.n_slots;
+    q.n_pix_ops = 0; q.pix_ops = nullptr;           // (the PIXEL section reads the program's own constant pool)
+    validate_program(q);
+    const uint32_t n_ynum = numeric_yvals(p);
+    for (uint32_t i = 0; i < r.n_ops; i++) {
+        const uint64_t ins = r.ops[i];
+        const uint32_t op = MARAY_INS_OP(ins);
+        if (op == MARAY_OP_NOP || op == MARAY_OP_TEXDIM) continue;
+        if (op == MARAY_OP_OUT && MARAY_INS_AUX(ins) < n_ynum) throw Error{MARAY_E_ARG, "REFINE output " + std::to_string(MARAY_INS_AUX(ins)) + " is not a guard"};
+        const uint32_t refs[2] = {MARAY_INS_A(ins), (op >= MARAY_OP_ADD && op <= MARAY_OP_APP) ? MARAY_INS_B(ins) : 0u};
+        for (uint32_t ref : refs)
+            if (MARAY_REF_KIND(ref) == MARAY_K_SPEC && MARAY_REF_INDEX(ref) == MARAY_SPEC_Y) throw Error{MARAY_E_ARG, "the REFINE section reads Y at op " + std::to_string(i)};
+    }
+}
+
 }   // namespace maray
 
 extern "C" {
@@ -587,6 +609,11 @@ int maray_tape_param_range(const maray_tape *t, uint32_t index, double *lo, doub
     });
 }
 
+int maray_tape_refine(const maray_tape *t, maray_refine *out)
+{
+    return guard([&] { REQUIRE(t && out, "null argument"); *out = t->t.refine(); });
+}
+
 // ---- device ---------------------------------------------------------------------
 int maray_hip_device_count(int *n)
 {
@@ -596,6 +623,12 @@ int maray_hip_device_count(int *n)
 int maray_hip_ctx_create(int device, const maray_program *prog, const maray_texture *tex, uint32_t n_tex,
                          const maray_ctx_opts *opts, maray_ctx **out)
 {
+    return maray_hip_ctx_create_refined(device, prog, nullptr, tex, n_tex, opts, out);
+}
+
+int maray_hip_ctx_create_refined(int device, const maray_program *prog, const maray_refine *refine, const maray_texture *tex, uint32_t n_tex,
+                                 const maray_ctx_opts *opts, maray_ctx **out)
+{
     return guard([&] {
         REQUIRE(prog && out, "null argument");
         REQUIRE(n_tex == 0 || tex, "null texture table");
@@ -603,6 +636,8 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         const maray_program loaded = load_program(prog);
         prog = &loaded;
         validate_program(*prog);
+        if (refine && !refine->n_ops) refine = nullptr;
+        if (refine) validate_refine(*prog, *refine);
         if (prog->n_app > 5u * n_tex)   // reference: rt.functions[id] panics (src/lib.rs:665)
             throw Error{MARAY_E_APP_RANGE, "scene calls App id " + std::to_string(prog->n_app - 1) + " but only " +
                         std::to_string(5u * n_tex) + " texture functions exist"};
@@ -624,7 +659,7 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
         switch (backend) {
         case MARAY_BACKEND_TAPE: b = make_tape_backend(device, *prog, tex, n_tex, true, samples); break;
         case MARAY_BACKEND_TAPE_SMEM: b = make_tape_backend(device, *prog, tex, n_tex, false, samples); break;
-        case MARAY_BACKEND_JIT: b = make_jit_backend(device, *prog, tex, n_tex, samples); break;
+        case MARAY_BACKEND_JIT: b = make_jit_backend(device, *prog, tex, n_tex, samples, refine); break;
         case MARAY_BACKEND_AUTO: {
             // One-shot economics.  The specialised kernels render a frame tens of times faster than the interpreter, but
             // hiprtc needs seconds to build them (chess: 9 k pixel + 17 k row ops -> 1.6 s with the two modules built side
@@ -647,7 +682,7 @@ int maray_hip_ctx_create(int device, const maray_program *prog, const maray_text
             if (force && !strcmp(force, "jit")) want_jit = true;
             if (force && !strcmp(force, "tape")) want_jit = false;
             if (!want_jit) { b = make_tape_backend(device, *prog, tex, n_tex, false, samples); break; }
-            try { b = make_jit_backend(device, *prog, tex, n_tex, samples); }
+            try { b = make_jit_backend(device, *prog, tex, n_tex, samples, refine); }
             catch (const Error &e) {
                 if (e.code == MARAY_E_NO_DEVICE) throw;
                 b = make_tape_backend(device, *prog, tex, n_tex, false, samples);   // still the HIP path, never a CPU fallback
@@ -1187,6 +1222,64 @@ int maray_jit_code_key(const maray_program *prog, char *out33)
 int maray_jit_code_cached(const maray_program *prog, int *cached)
 {
     return guard([&] { REQUIRE(prog && cached, "null argument"); *cached = jit_code_is_cached(load_program(prog)) ? 1 : 0; });
+}
+
+int maray_jit_source_refine(const maray_program *prog, const maray_refine *refine, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        std::string s;
+        if (refine && refine->n_ops) { validate_refine(loaded, *refine); s = jit_source_refine(loaded, *refine); }
+        *src_out = (char *)malloc(s.size() + 1);
+        REQUIRE(*src_out, "out of memory");
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
+int maray_jit_build_refine(const maray_program *prog, const maray_refine *refine, void **code_out, size_t *len_out)
+{
+    return guard([&] {
+        REQUIRE(prog && refine && code_out && len_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        *code_out = nullptr; *len_out = 0;
+        if (!refine->n_ops) return;
+        validate_refine(loaded, *refine);
+        const std::shared_ptr<const JitRefineCode> c = jit_code_refine(loaded, *refine);
+        if (!c) return;
+        *code_out = malloc(c->code.size());
+        REQUIRE(*code_out, "out of memory");
+        memcpy(*code_out, c->code.data(), c->code.size());
+        *len_out = c->code.size();
+    });
+}
+
+int maray_jit_guard_layout(const maray_program *prog, int32_t *pos, uint32_t cap, uint32_t *n_guards, uint32_t *n_words, uint32_t *gw, uint32_t *gh)
+{
+    return guard([&] {
+        REQUIRE(prog && n_guards && n_words && gw && gh && (pos || !cap), "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        std::vector<int32_t> p;
+        jit_guard_layout(loaded, p, n_words, gw, gh);
+        *n_guards = (uint32_t)p.size();
+        for (uint32_t g = 0; g < p.size() && g < cap; g++) pos[g] = p[g];
+    });
+}
+
+int maray_hip_refine_count(const maray_ctx *c, uint64_t *refine_passes)
+{
+    return guard([&] { REQUIRE(c && c->backend && refine_passes, "null argument"); *refine_passes = c->backend->refine_count(); });
+}
+
+int maray_hip_debug_guard_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend && n_words && words_per_rect && (words || !cap), "null argument");
+        *n_words = c->backend->debug_guard_words(words, cap, words_per_rect);
+    });
 }
 
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }

@@ -38,6 +38,10 @@ struct Backend {
     // How many ROW passes (maray_jit_rows) and launch-order kernels (maray_jit_order) the context has enqueued so far: what
     // the tests of the ROW tables' reuse (row_reuse.hpp) count.  The interpreters run their ROW stage per launch and count nothing.
     virtual void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const { *row_passes = *order_kernels = 0; }
+    // maray_jit_refine passes enqueued so far, and (test access) the guard words of the set the last launch used, after a
+    // wait for the context's work: returns the words in the set, copies at most `cap` (maray_hip_debug_guard_words)
+    virtual uint64_t refine_count() const { return 0; }
+    virtual size_t debug_guard_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
@@ -72,9 +76,19 @@ int png_decode(const std::vector<uint8_t> &b, uint8_t **rgb8_out, uint32_t *w_ou
 int hip_device_count();
 // samples = k > 1: a supersampling context (maray_ctx_opts.samples): renders RGB8 only, geometry in output pixels
 Backend *make_tape_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, bool lds_variant, uint32_t samples = 1);
-Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples = 1);
+// refine: the program's REFINE section (null or empty: none), evaluated behind every ROW pass (maray_jit_refine)
+Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples = 1, const maray_refine *refine = nullptr);
 std::string jit_source(const maray_program &prog, int min_waves = 0);   // PIXEL kernel source (__launch_bounds__(256, min_waves); 0 = the layout's default); throws Error
 std::string jit_source_rows(const maray_program &prog, uint32_t *n_chunks_out = nullptr, uint32_t *n_gjobs_out = nullptr);   // ROW kernel source (blockIdx.y = chunk)
+// How the specialised kernels keep a program's guards (test access, maray_jit_guard_layout): pos[g] = the bit of guard g (y value
+// numeric_yvals + g) in a rectangle's words, -1 for a guard derived from others' bits; words per rectangle (0: guards not kept as
+// bits) and the rectangle, in pixels x rows
+void jit_guard_layout(const maray_program &prog, std::vector<int32_t> &pos, uint32_t *n_words, uint32_t *gw, uint32_t *gh);
+// maray_jit_refine: the REFINE section on the rectangles whose guard bits are set; "" when there is nothing to launch.  *n_jobs_out: blockIdx.y of its launch
+std::string jit_source_refine(const maray_program &prog, const maray_refine &refine, uint32_t *n_jobs_out = nullptr);
+// its code object (null when the source is empty): built once, kept like jit_code_samples', under a key of its own made of its text
+struct JitRefineCode { std::vector<char> code; uint32_t n_jobs = 0; };
+std::shared_ptr<const JitRefineCode> jit_code_refine(const maray_program &prog, const maray_refine &refine);
 std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
 std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error

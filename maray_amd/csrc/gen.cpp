@@ -337,6 +337,8 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
     } else if (!png) pin.pin(rgb8, (size_t)w * h * 3);
     maray_program prog;
     maray_tape_program(entry->tape, &prog);
+    maray_refine refine;            // the program's REFINE section travels beside it (maray_hip_ctx_create_refined)
+    maray_tape_refine(entry->tape, &refine);
     // The scene's current parameter values: the program was found by its name (declarations in, values out), so a frame
     // with other values is the same entry, the same contexts and the same code objects; each context is given the values
     // in front of its tiles.  (A program none of whose ops reads a parameter has none: nothing is set.)
@@ -387,7 +389,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
         const int dev = device_of(d);
         const IdleCtx kept = gen_cache_take(*entry, dev, co.backend == MARAY_BACKEND_AUTO, co.hint_mpixels);
         maray_ctx *ctx = kept.ctx;
-        int r = ctx ? MARAY_OK : maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx);
+        int r = ctx ? MARAY_OK : maray_hip_ctx_create_refined(dev, &prog, &refine, tex, n_tex, &co, &ctx);
         if (!r && !param_values.empty()) r = maray_hip_ctx_set_params(ctx, param_values.data(), (uint32_t)param_values.size());
         std::string thrown;
         if (!r && !share[d].empty() && png) {
@@ -562,6 +564,8 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
     }
     maray_program prog;
     maray_tape_program(entry->tape, &prog);
+    maray_refine refine;            // the program's REFINE section travels beside it (maray_hip_ctx_create_refined)
+    maray_tape_refine(entry->tape, &refine);
     const uint32_t P = prog.version == MARAY_TAPE_VERSION_PARAMS ? prog.n_params : 0u;      // the scene's count, or 0: no op reads one
     if (P && P != n_par) return fail_with(MARAY_E_INTERNAL, "the program's parameter count is not the scene's");
 
@@ -605,7 +609,7 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
     const IdleCtx kept = gen_cache_take(*entry, dev, co.backend == MARAY_BACKEND_AUTO, co.hint_mpixels);
     maray_ctx *ctx = kept.ctx;
     if (!ctx)
-        if (const int rc = maray_hip_ctx_create(dev, &prog, tex, n_tex, &co, &ctx)) return rc;
+        if (const int rc = maray_hip_ctx_create_refined(dev, &prog, &refine, tex, n_tex, &co, &ctx)) return rc;
     uint8_t *bytes = nullptr;
     size_t n_bytes = 0;
     const int rc = maray_hip_render_apng(ctx, w, h, P ? rows.data() : nullptr, n_images, n_sub, delay_num, delay_den, n_plays, &bytes, &n_bytes);

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <future>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -57,6 +58,12 @@ struct JitBackend final : Backend {
     std::shared_ptr<const JitCode> code;
     hipModule_t mod = nullptr, mod_rows = nullptr;
     hipFunction_t f_rows = nullptr, f_pix = nullptr, f_order = nullptr;
+    // maray_jit_refine (the program's REFINE section, jit_source_refine): behind every ROW pass, into the same guard words
+    std::shared_ptr<const JitRefineCode> code_refine;
+    hipModule_t mod_refine = nullptr;
+    hipFunction_t f_refine = nullptr;
+    bool refine_on = true;              // MARAY_JIT_GUARD_REFINE=0: no such launch (read once, when the context is created)
+    uint64_t n_refine_passes = 0;
     uint32_t ss = 1;                    // samples per output pixel and axis: > 1 launches maray_jit_pixels_ss (launch_ss)
     std::shared_ptr<const std::vector<char>> code_ss;
     hipModule_t mod_ss = nullptr;
@@ -70,6 +77,8 @@ struct JitBackend final : Backend {
     RowTables tabs[RowReuse::N_SETS];
     RowReuse reuse;
     int cur_set = -1;                   // the set the most recent launch used
+    size_t set_gbits_n[RowReuse::N_SETS] = {};      // guard words each set's last ROW pass wrote
+    size_t last_gbits_n = 0;            // ... and the most recent launch's
     uint64_t row_params = 0;            // bit p: a ROW op reads PARAM p (row_param_mask)
     uint64_t n_row_passes = 0, n_order_kernels = 0;         // maray_jit_rows / maray_jit_order launches enqueued so far (launch_counts)
     unsigned char *d_rgb8 = nullptr; size_t rgb8_cap = 0;      // time_rows without a caller's buffer
@@ -95,6 +104,7 @@ struct JitBackend final : Backend {
         delete slow;
         if (mod) (void)hipModuleUnload(mod);
         if (mod_rows) (void)hipModuleUnload(mod_rows);
+        if (mod_refine) (void)hipModuleUnload(mod_refine);
         if (mod_ss) (void)hipModuleUnload(mod_ss);
         (void)hipFree(d_flags);
         (void)hipFree(d_tex);
@@ -107,7 +117,7 @@ struct JitBackend final : Backend {
         if (pipe) { (void)hipStreamSynchronize(pipe->compute_stream()); host_pipe_release(std::move(pipe)); }
     }
 
-    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples) {
+    void init(int dev, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples, const maray_refine *refine) {
         device = dev;
         ss = samples;
         // MARAY_TRACE_INIT=1: where the time of a context's creation goes (stderr)
@@ -144,7 +154,14 @@ struct JitBackend final : Backend {
         if (const char *e_ = getenv("MARAY_JIT_ROW_REUSE")) if (e_[0] == '0') reuse.enabled = false;
         row_params = row_param_mask(prog);
         lap("device");
-        code = jit_code_for(prog);                       // built by the first context of the process, or read from the cache
+        if (const char *e_ = getenv("MARAY_JIT_GUARD_REFINE")) if (e_[0] == '0') refine_on = false;
+        // the third module is asked for first, on a thread of its own: a cold start builds the three side by side
+        std::future<std::shared_ptr<const JitRefineCode>> refine_code;
+        if (refine_on && refine && refine->n_ops && prog.n_row_ops)
+            refine_code = std::async(std::launch::async, [&prog, refine] { return jit_code_refine(prog, *refine); });
+        try { code = jit_code_for(prog); }               // built by the first context of the process, or read from the cache
+        catch (...) { if (refine_code.valid()) refine_code.wait(); throw; }
+        if (refine_code.valid()) code_refine = refine_code.get();
         lap("code objects");
         HIP_TRY(hipModuleLoadData(&mod, code->pix.data()));
         HIP_TRY(hipModuleGetFunction(&f_pix, mod, "maray_jit_pixels"));
@@ -167,11 +184,15 @@ struct JitBackend final : Backend {
             guard_rows = code->guard_h;
             guard_sub = 256u / code->guard_w;
             lap("load ROW module");
-
+            if (code_refine && n_gwords) {
+                HIP_TRY(hipModuleLoadData(&mod_refine, code_refine->code.data()));
+                HIP_TRY(hipModuleGetFunction(&f_refine, mod_refine, "maray_jit_refine"));
+                lap("load REFINE module");
+            }
         }
         if (prog.n_params) {
             param_values.assign(prog.n_params, NAN);
-            for (hipModule_t m : {mod, mod_rows, mod_ss}) {
+            for (hipModule_t m : {mod, mod_rows, mod_ss, mod_refine}) {
                 if (!m) continue;
                 hipDeviceptr_t p = nullptr;
                 size_t bytes = 0;
@@ -258,6 +279,7 @@ struct JitBackend final : Backend {
         *matched = true;
         if (s >= 0 && (reuse.enabled || !rows_pass)) {
             reuse.touch(s);
+            last_gbits_n = set_gbits_n[s];
             return cur_set = s;
         }
         if (!rows_pass) {
@@ -294,8 +316,17 @@ struct JitBackend final : Backend {
             unsigned gy = n_row_chunks + n_gjobs;
             HIP_TRY(hipModuleLaunchKernel(f_rows, (unsigned)((items + bs - 1) / bs), gy, 1, bs, 1, 1, 0, st, args, nullptr));
             n_row_passes++;
+            // the second bounds, into the words the ROW pass has just written: in front of the launch order, which counts
+            // the bits that are left, and of every reader (one stream)
+            if (f_refine && n_gwords) {
+                void *rargs[] = {&t.gbits, &d_tex, &y0, &rr, &ww, &n_tx_, &blk_rows, &blk_stride, &yrows};
+                const uint64_t rects = (uint64_t)n_groups * n_tx_;
+                HIP_TRY(hipModuleLaunchKernel(f_refine, (unsigned)((rects + bs - 1) / bs), code_refine->n_jobs, 1, bs, 1, 1, 0, st, rargs, nullptr));
+                n_refine_passes++;
+            }
         }
         if (refill) reuse.touch(s); else reuse.filled(s);      // the set carries its key only now: the kernel that fills it is enqueued
+        last_gbits_n = set_gbits_n[s] = gb_n;
         return cur_set = s;
     }
 
@@ -491,16 +522,26 @@ struct JitBackend final : Backend {
 
     const char *kernel_name() const override { return ss > 1 ? "maray_jit_pixels_ss" : "maray_jit_pixels"; }
     void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { *row_passes = n_row_passes; *order_kernels = n_order_kernels; }
+    uint64_t refine_count() const override { return n_refine_passes; }
+    size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override {
+        if (!n_gwords || cur_set < 0 || !tabs[cur_set].gbits) throw Error{MARAY_E_ARG, "no guard words: a program without guards, or no launch yet"};
+        HIP_TRY(hipSetDevice(device));
+        if (have_last) HIP_TRY(hipStreamSynchronize(last_stream));
+        const size_t n = last_gbits_n;
+        if (words && cap) HIP_TRY(hipMemcpy(words, tabs[cur_set].gbits, std::min(n, cap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        *per_rect = n_gwords;
+        return n;
+    }
 };
 
 }   // namespace
 
-Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples)
+Backend *make_jit_backend(int device, const maray_program &prog, const maray_texture *tex, uint32_t n_tex, uint32_t samples, const maray_refine *refine)
 {
     if (hip_device_count() <= 0) throw Error{MARAY_E_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)"};
     auto *b = new JitBackend();
     try {
-        b->init(device, prog, tex, n_tex, samples);
+        b->init(device, prog, tex, n_tex, samples, refine);
     } catch (...) {
         delete b;
         throw;

@@ -389,6 +389,47 @@ HelperEnd helper_finish(HelperJob &j, std::vector<char> &code, std::string &log)
     return end;
 }
 
+// A cache file of one module: its bytes and a checksum of them (<key>.mrss, <key>.mrrf).  A damaged or missing file is a miss.
+bool blob_read(const std::string &path, std::vector<char> &bytes)
+{
+    std::vector<char> b;
+    uint64_t sum = 0;
+    if (!read_file(path, b) || b.size() <= 8) return false;
+    memcpy(&sum, b.data() + b.size() - 8, 8);
+    b.resize(b.size() - 8);
+    if (sum != fnv1a(b.data(), b.size(), 0xcbf29ce484222325ull)) return false;
+    bytes.swap(b);
+    return true;
+}
+
+void blob_write(const std::string &dir, const std::string &path, const std::vector<char> &bytes)
+{
+    mkdirs(dir);
+    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return;                                       // a read-only or missing cache directory is not an error
+    const uint64_t sum = fnv1a(bytes.data(), bytes.size(), 0xcbf29ce484222325ull);
+    const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size() && fwrite(&sum, 8, 1, f) == 1;
+    if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
+}
+
+// One source in a helper process of its own (what build_code does for a program's two modules side by side); in-process when
+// there is no helper or MARAY_JIT_HELPER=0.  `what`: the kernel's name in the error message.
+void compile_aside(const std::string &src, const char *tag, const char *what, std::vector<char> &code)
+{
+    std::string log;
+    const char *e = getenv("MARAY_JIT_HELPER");
+    const std::string helper = self_dir() + "/maray_jitc", rtc = hiprtc_path();
+    if (!(e && e[0] == '0') && !rtc.empty() && access(helper.c_str(), X_OK) == 0) {
+        HelperJob job = helper_start(helper, rtc, src, tag);
+        const HelperEnd end = helper_finish(job, code, log);
+        if (end == HELPER_REJECTED) throw Error{MARAY_E_HIP, std::string("hiprtcCompileProgram (maray_jitc): the ") + what + " kernel does not compile\n" + log};
+        if (end == HELPER_DIED) throw Error{MARAY_E_HIP, std::string("the compiler aborted on the ") + what + " kernel (maray_jitc: " + log + ")"};
+        if (end == HELPER_OK) return;
+    }
+    jit_compile(src, code, log);
+}
+
 std::shared_ptr<const JitCode> build_code(const maray_program &prog, CodeKey &k)
 {
     auto c = std::make_shared<JitCode>();
@@ -494,20 +535,7 @@ std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &p
     if (it != built.end()) return it->second;
     auto code = std::make_shared<std::vector<char>>();
     const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrss";
-    bool have = false;
-    if (!path.empty())
-        if (FILE *f = fopen(path.c_str(), "rb")) {
-            std::vector<char> b;
-            char buf[65536];
-            for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) b.insert(b.end(), buf, buf + n);
-            fclose(f);
-            uint64_t sum = 0;
-            if (b.size() > 8) {
-                memcpy(&sum, b.data() + b.size() - 8, 8);
-                b.resize(b.size() - 8);
-                if (sum == fnv1a(b.data(), b.size(), 0xcbf29ce484222325ull)) { code->swap(b); have = true; }
-            }
-        }
+    const bool have = !path.empty() && blob_read(path, *code);
     if (!have) {
         std::string log;
         const int ladder[] = {0, 6, 4, 2};
@@ -515,19 +543,78 @@ std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &p
             jit_compile(i == 0 ? src : jit_source_samples(prog, k, ladder[i]), *code, log);
             if (code_meta_uint(*code, ".private_segment_fixed_size") <= 0) break;
         }
-        if (!path.empty()) {
-            mkdirs(dir);
-            const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-            if (FILE *f = fopen(tmp.c_str(), "wb")) {
-                const uint64_t sum = fnv1a(code->data(), code->size(), 0xcbf29ce484222325ull);
-                const bool ok = fwrite(code->data(), 1, code->size(), f) == code->size() && fwrite(&sum, 8, 1, f) == 1;
-                if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
-            }
-        }
+        if (!path.empty()) blob_write(dir, path, *code);
     }
     if (built.size() > 32) built.clear();
     built[key] = code;
     return code;
+}
+
+// maray_jit_refine of a program with a REFINE section (jit_source_refine): a third module with a cache entry of its own, so
+// that the other two modules' key and entry are what they are without it.  Its key is the program's name (program_name: the
+// program, the generator's build id, every MARAY_JIT_* knob, the compiler -- all that decides the text) hashed with the
+// section, so a context whose module is in the process or on disk (<key>.mrrf: the code object, the launch's job count and
+// a checksum) generates no source at all.  A consequence: the `code_key` that bench.py stamps into a profile names the PIXEL
+// and ROW modules only; which refine kernel ran follows from the program and the build id in that key's salt, not from the key.
+// Built by a helper process like the other two (JitBackend::init asks for it on a thread of its own, beside jit_code_for: the
+// three compiles run side by side); MARAY_JIT_HELPER=0 or no helper: in-process.  Contexts that ask for a key that is being
+// built wait for that build, not for a lock around the compiler.
+std::shared_ptr<const JitRefineCode> jit_code_refine(const maray_program &prog, const maray_refine &refine)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_future<std::shared_ptr<const JitRefineCode>>> built;
+    if (!refine.n_ops) return nullptr;
+    std::string key;
+    {
+        const std::string name = program_name(prog) + "|refine";
+        const uint32_t counts[3] = {refine.n_consts, refine.n_ops, refine.n_slots};
+        uint64_t h[2] = {0xcbf29ce484222325ull, 0x84222325cbf29ce4ull};
+        for (uint64_t &x : h) {
+            x = fnv1a(name.data(), name.size(), x);
+            x = fnv1a(counts, sizeof counts, x);
+            x = fnv1a(refine.consts, (size_t)refine.n_consts * sizeof(double), x);
+            x = fnv1a(refine.ops, (size_t)refine.n_ops * sizeof(uint64_t), x);
+        }
+        key = hex128(h[0], h[1]);
+    }
+    std::promise<std::shared_ptr<const JitRefineCode>> mine;
+    std::shared_future<std::shared_ptr<const JitRefineCode>> fut;
+    bool build = false;
+    {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = built.find(key);
+        if (it != built.end()) fut = it->second;
+        else {
+            if (built.size() > 32) built.clear();
+            fut = mine.get_future().share(); built.emplace(key, fut); build = true;
+        }
+    }
+    if (!build) return fut.get();
+    try {
+        auto out = std::make_shared<JitRefineCode>();
+        const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrrf";
+        std::vector<char> blob;
+        if (!path.empty() && blob_read(path, blob) && blob.size() > 4) {      // code object + job count
+            memcpy(&out->n_jobs, blob.data() + blob.size() - 4, 4);
+            blob.resize(blob.size() - 4);
+            out->code.swap(blob);
+        } else {
+            const std::string src = jit_source_refine(prog, refine, &out->n_jobs);
+            if (!src.empty()) {
+                compile_aside(src, "refine", "REFINE", out->code);
+                blob = out->code;
+                blob.insert(blob.end(), (const char *)&out->n_jobs, (const char *)&out->n_jobs + 4);
+                if (!path.empty()) blob_write(dir, path, blob);
+            }
+        }
+        if (out->code.empty() || !out->n_jobs || out->n_jobs > 65535) out.reset();       // nothing to launch (no guard words, no bit with a second bound)
+        mine.set_value(out);
+    } catch (...) {
+        mine.set_exception(std::current_exception());
+        std::lock_guard<std::mutex> lk(m);
+        built.erase(key);                               // a failed build is not remembered (the waiters still see its error)
+    }
+    return fut.get();
 }
 
 }   // namespace maray

@@ -119,6 +119,14 @@ GuardPlan jit_guard_plan(const maray_program &P)
     return gp;
 }
 
+void jit_guard_layout(const maray_program &P, std::vector<int32_t> &pos, uint32_t *n_words, uint32_t *gw, uint32_t *gh)
+{
+    const JitKnobs K = jit_knobs();
+    const GuardGeom geom = jit_guard_geom(P, K);
+    *n_words = jit_guard_words(P, K); *gw = geom.gw; *gh = geom.gh;
+    pos = jit_guard_plan(P).pos;
+}
+
 // The parameter table of a program with parameters (include/maray_tape.h, SPEC PARAM): a global of every module of the
 // program, written by the host alone (JitBackend::send_params finds it by name) and read by scalar loads.  Only sources
 // of programs that have parameters contain it; nothing in a source depends on a parameter's VALUE.
@@ -240,6 +248,20 @@ static std::string row_order_kernel(uint32_t n_gwords)
          "}\n";
 }
 
+// The rectangle of work-item `item` of a guard job, as text: its group of rows and run of pixels, clamped at the ragged
+// edges, and the section's XMIN / XMAX / YMIN / YMAX.  Shared by maray_jit_rows' guard jobs and maray_jit_refine: the two
+// fill the same table, so they must agree on what a rectangle is.
+static std::string guard_rectangle(const GuardGeom &geom)
+{
+    return   "    const unsigned grp = item / n_tx, tile = item - grp * n_tx;\n"
+             "    const unsigned r = grp * yrows, r_last = r + yrows - 1u < rows - 1u ? r + yrows - 1u : rows - 1u;      // launch rows of the group\n"
+             "    // (n_tx counts rectangles here; the last 256-pixel tile of a ragged row may own rectangles past the edge: they bound the last pixel)\n"
+             "    const unsigned xlo_ = tile * " + std::to_string(geom.gw) + "u, xlo = xlo_ < w - 1u ? xlo_ : w - 1u, xhi = xlo_ + " + std::to_string(geom.gw - 1) + "u < w - 1u ? xlo_ + " + std::to_string(geom.gw - 1) + "u : w - 1u;\n"
+             "    // a group never straddles two row blocks (the host picks yrows | blk_rows), so its image rows are consecutive\n"
+             "    const double Y = (double)(blk_stride == 0u ? y0 + r : y0 + (r / blk_rows) * blk_stride + r % blk_rows), XMIN = (double)xlo, XMAX = (double)xhi;\n"
+             "    const double YMIN = Y, YMAX = Y + (double)(r_last - r);\n";
+}
+
 // Source of the ROW kernel, maray_jit_rows: one wavefront per block, blockIdx.y picks the job.
 //  y < n_chunks: chunk y of the ROW section, one work-item per row; writes the y values the pixel
 //    kernel reads as operands (and, for a program that may defer tiles to the interpreter, the
@@ -329,13 +351,7 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
         s += "    // guards: (row group, tile), the tiles of a group adjacent\n"
              "    const unsigned n_groups = (rows + yrows - 1u) / yrows;\n"
              "    if (item >= n_groups * n_tx) return;\n"
-             "    const unsigned grp = item / n_tx, tile = item - grp * n_tx;\n"
-             "    const unsigned r = grp * yrows, r_last = r + yrows - 1u < rows - 1u ? r + yrows - 1u : rows - 1u;      // launch rows of the group\n"
-             "    // (n_tx counts rectangles here; the last 256-pixel tile of a ragged row may own rectangles past the edge: they bound the last pixel)\n"
-             "    const unsigned xlo_ = tile * " + std::to_string(geom.gw) + "u, xlo = xlo_ < w - 1u ? xlo_ : w - 1u, xhi = xlo_ + " + std::to_string(geom.gw - 1) + "u < w - 1u ? xlo_ + " + std::to_string(geom.gw - 1) + "u : w - 1u;\n"
-             "    // a group never straddles two row blocks (the host picks yrows | blk_rows), so its image rows are consecutive\n"
-             "    const double Y = (double)(blk_stride == 0u ? y0 + r : y0 + (r / blk_rows) * blk_stride + r % blk_rows), XMIN = (double)xlo, XMAX = (double)xhi;\n"
-             "    const double YMIN = Y, YMAX = Y + (double)(r_last - r);\n"
+             + guard_rectangle(geom) +
              "    unsigned long long gacc = 0ull;\n"
              "    double *yout = nullptr;\n"
              "    (void)Y; (void)XMIN; (void)XMAX; (void)YMIN; (void)YMAX; (void)yout;\n"
@@ -361,6 +377,85 @@ std::string jit_source_rows(const maray_program &P, uint32_t *n_chunks_out, uint
     }
     s += "}\n";
     if (n_gwords) s += row_order_kernel(n_gwords);
+    return s;
+}
+
+// Source of maray_jit_refine: the guard half of maray_jit_rows over the program's REFINE section (include/maray_tape.h,
+// maray_refine), launched behind it on the same stream.  One work-item per rectangle; blockIdx.y picks a job = one byte
+// of the guard words, only the bytes that have a bit with a second bound.  A work-item loads its rectangle's byte; a
+// wavefront in which no lane has one of the job's bits set returns at once (chess @4096^2: 93 % of them), the others
+// evaluate the job's cones -- a few libm bodies per Step(Sin) factor, which is why this is not part of the ROW section,
+// evaluated on every rectangle -- and store byte & (second bounds | bits that have none).  The rectangles, ragged edges
+// included, are maray_jit_rows' (guard_rectangle).
+std::string jit_source_refine(const maray_program &P, const maray_refine &R, uint32_t *n_jobs_out)
+{
+    if (n_jobs_out) *n_jobs_out = 0;
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    const uint32_t n_gwords = jit_guard_words(P, K);
+    if (!R.n_ops || !n_gwords) return "";
+    const uint32_t n_ynum = numeric_yvals(P);
+    const GuardPlan plan = jit_guard_plan(P);
+    const GuardGeom geom = jit_guard_geom(P, K);
+    // the section as the ROW section of a program of its own: what the emitter and the cone analysis take
+    maray_program Q = P;
+    Q.n_consts = R.n_consts; Q.consts = R.consts;
+    Q.n_row_ops = R.n_ops; Q.row_ops = R.ops; Q.n_row_slots = R.n_slots;
+    const RowTapeDeps deps = row_tape_deps(Q);
+    struct Job { uint32_t byte, mask; std::vector<uint32_t> outs; };
+    std::vector<Job> jobs;
+    for (uint32_t j = 0; j < (plan.n_pos + 7) / 8; j++) {
+        Job job{j, 0u, {}};
+        for (uint32_t o : deps.outs) {
+            const uint32_t aux = MARAY_INS_AUX(R.ops[o]);
+            if (aux < n_ynum || aux - n_ynum >= plan.pos.size()) continue;
+            const int32_t k = plan.pos[aux - n_ynum];                // (a derived guard has no bit of its own)
+            if (k >= (int32_t)(8 * j) && k < (int32_t)(8 * (j + 1))) { job.outs.push_back(o); job.mask |= 1u << (k % 8); }
+        }
+        if (!job.outs.empty()) jobs.push_back(job);
+    }
+    if (jobs.empty()) return "";
+    if (n_jobs_out) *n_jobs_out = (uint32_t)jobs.size();
+    Emitter E(Q);
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp): REFINE section, " + std::to_string(R.n_ops) + " ops, " + std::to_string(R.n_outs) + " second bounds in " +
+         std::to_string(jobs.size()) + " jobs; guards in " + std::to_string(n_gwords) + " words,\n"
+         "// each bounded over rectangles of " + std::to_string(geom.gw) + " pixels x " + std::to_string(geom.gh) + " rows\n";
+    s += "#include \"device_math.h\"\n\n";
+    if (P.n_params) s += jit_param_table(P) + "typedef const __attribute__((address_space(4))) double *mr_kptr;\n";
+    s += "extern \"C\" __global__ void __launch_bounds__(" + std::to_string(ROW_BLOCK) + ") maray_jit_refine(unsigned long long *__restrict__ gbits, const MarayTex *__restrict__ tex,\n"
+         "                                                                   unsigned y0, unsigned rows, unsigned w, unsigned n_tx,\n"
+         "                                                                   unsigned blk_rows, unsigned blk_stride, unsigned yrows)\n{\n"
+         "    const unsigned item = blockIdx.x * blockDim.x + threadIdx.x;         // (the host keeps the items of a launch below 2^32)\n"
+         "    (void)tex;\n" + std::string(P.n_params ? "    unsigned long long mr_pbase = (unsigned long long)mr_par_tab;\n" + std::string(PARAM_POINTER) : "") +
+         "    const unsigned n_groups = (rows + yrows - 1u) / yrows;\n"
+         "    const bool mr_in = item < n_groups * n_tx;\n"
+         "    // the byte of the rectangle's guard words this job refines, and its bits that have a second bound\n"
+         "    unsigned mr_at = 0u, mr_has = 0u;\n"
+         "    switch (blockIdx.y) {\n";
+    for (size_t j = 0; j < jobs.size(); j++)
+        s += "    case " + std::to_string(j) + ": mr_at = " + std::to_string(jobs[j].byte) + "u; mr_has = " + std::to_string(jobs[j].mask) + "u; break;\n";
+    s += "    }\n"
+         "    unsigned char *mr_p = (unsigned char *)gbits + ((size_t)item * " + std::to_string(8 * n_gwords) + "u + mr_at);\n"
+         "    const unsigned mr_b = mr_in ? (unsigned)*mr_p : 0u;\n"
+         "    if (mr_ballot((mr_b & mr_has) != 0u) == 0ull) return;                 // no lane of the wavefront has a bit to refine\n"
+         + guard_rectangle(geom) +
+         "    unsigned long long gacc = 0ull;\n"
+         "    (void)Y; (void)XMIN; (void)XMAX; (void)YMIN; (void)YMAX;\n"
+         "    switch (blockIdx.y) {\n";
+    E.out_guard_bits = true;
+    E.guard_first = n_ynum;
+    E.plan = &plan;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const std::vector<uint64_t> tape = row_tape_cone(Q, deps, jobs[j].outs, nullptr);
+        s += "    case " + std::to_string(j) + ": {\n";
+        E.section(tape.data(), R.n_ops, R.n_slots, false, "r");
+        s += "    } break;\n";
+    }
+    s += "    }\n"
+         "    // a bit stays set unless its second bound is 0; bits without one keep their value\n"
+         "    if (mr_in && (mr_b & mr_has) != 0u) *mr_p = (unsigned char)(mr_b & ((unsigned)gacc | ~mr_has));\n"
+         "}\n";
     return s;
 }
 

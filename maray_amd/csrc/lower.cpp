@@ -465,9 +465,19 @@ template <class T> struct IdMap {
     void reserve(size_t n) { if (n > has.size()) { v.resize(n); has.resize(n, 0); } }
 };
 
-struct RowBounds {
-    struct B { int32_t ub, lb; bool lossy; };       // lossy: somewhere below, a sub-expression could only be bounded by "anything"
+// Boolean algebra on DAG nodes whose values are +0.0 or 1.0, as every pass that builds bounds writes it: NOT b = 1 + -(b),
+// AND = min, OR = max (what bool_typing recognises).  Shared by the row bounds and the REFINE section's second bounds.
+struct BoolAlg {
     Dag &g;
+    int32_t c_true, c_false;
+    explicit BoolAlg(Dag &g_) : g(g_) { c_true = g.konst(1.0); c_false = g.konst(0.0); }
+    int32_t b_not(int32_t a) { return g.binary(MARAY_OP_ADD, c_true, g.unary(MARAY_OP_NEG, a)); }
+    int32_t b_and(int32_t a, int32_t b) { return g.binary(MARAY_OP_MIN, a, b); }
+    int32_t b_or(int32_t a, int32_t b) { return g.binary(MARAY_OP_MAX, a, b); }
+};
+
+struct RowBounds : BoolAlg {
+    struct B { int32_t ub, lb; bool lossy; };       // lossy: somewhere below, a sub-expression could only be bounded by "anything"
     const std::vector<uint8_t> &isbool;
     const std::vector<Mono> &mono;
     const std::vector<Ival> &range;                 // static interval of every node over the whole domain
@@ -476,13 +486,13 @@ struct RowBounds {
     IdMap<B> memo;
     struct IV { int32_t lo, hi; bool ok() const { return lo >= 0; } };
     IdMap<IV> iv_memo;
-    int32_t c_true, c_false, x0, xmax;
+    int32_t x0, xmax;
 
     RowBounds(Dag &g_, const std::vector<uint8_t> &b, const std::vector<Mono> &m, const std::vector<Ival> &rg, uint8_t dep_bit_, uint8_t var_leaf_,
               uint8_t lo_leaf, uint8_t hi_leaf)
-        : g(g_), isbool(b), mono(m), range(rg), dep_bit(dep_bit_), var_leaf(var_leaf_) {
+        : BoolAlg(g_), isbool(b), mono(m), range(rg), dep_bit(dep_bit_), var_leaf(var_leaf_) {
         sub_lo.reserve(2 * g.n.size()); sub_hi.reserve(2 * g.n.size()); memo.reserve(2 * g.n.size()); iv_memo.reserve(2 * g.n.size());
-        c_true = g.konst(1.0); c_false = g.konst(0.0); x0 = g.leaf(lo_leaf); xmax = g.leaf(hi_leaf);
+        x0 = g.leaf(lo_leaf); xmax = g.leaf(hi_leaf);
     }
     int32_t subst(int32_t i, int32_t xr) {          // i with the coordinate replaced by node xr
         const DNode d = g.n[i];
@@ -499,7 +509,6 @@ struct RowBounds {
         sub_memo.put(i, r);
         return r;
     }
-    int32_t b_not(int32_t a) { return g.binary(MARAY_OP_ADD, c_true, g.unary(MARAY_OP_NEG, a)); }
 
     // Interval of an arithmetic value over the span, as two expressions free of the coordinate: lo <= v <= hi for every
     // value of the coordinate in [x0, xmax].  Every op here is correctly rounded, hence monotone in each operand, so
@@ -1203,6 +1212,367 @@ struct Lowerer {
     }
 };
 
+// ---- REFINE section ------------------------------------------------------------------------------
+// A second upper bound of a guarded conjunction over a rectangle of pixels, from the factors the row bounds above treat as
+// unknown: Step(Sin(a)) (include/maray_tape.h, "REFINE section").  With [lo, hi] the interval
+// of a over the rectangle -- RowBounds::ival over x, then over y, of an argument the static analysis proves NaN-free and
+// inside the bounded-Sin range -- the factor is 0 everywhere when fl(hi - lo) < 3 and sin(lo) < 0 and sin(hi) < 0 (a real
+// interval shorter than pi whose ends have negative sine holds no point of non-negative sine), 1 everywhere when both sines
+// are positive, unknown otherwise.  An end at +-0 proves nothing: sin(+-0) is neither.  The [lb, ub] pairs are carried
+// through the boolean and arithmetic ops above the factors; everything else is unknown ([0, 1] for a boolean), so the
+// result bounds the conjunction from its patterns alone and an evaluator ANDs it into the geometric guard's bit.
+struct Refiner : BoolAlg {
+    struct IVR { int32_t lo, hi; bool boolish; bool ok() const { return lo >= 0; } };
+    const std::vector<uint8_t> &isb;        // typing of the nodes the scene's sections are made of
+    std::vector<uint8_t> clean;             // per such node: the static analysis proves it NaN-free
+    IdMap<IVR> memo;
+    IdMap<IVR> sin_arg;                     // Step(Sin) node -> [lo, hi] of its argument over the rectangle (free of X and Y)
+    uint32_t n_rule = 0;                    // Step(Sin) factors the rule was built for
+
+    Refiner(Dag &g_, const std::vector<uint8_t> &b) : BoolAlg(g_), isb(b) {}
+
+    bool is_b(int32_t i) const { return i >= 0 && (size_t)i < isb.size() && isb[i]; }
+    bool is_clean(int32_t i) const { return i >= 0 && (size_t)i < clean.size() && clean[i]; }
+    IVR unknown_bool() const { return {c_false, c_true, true}; }
+
+    IVR step_sin(const IVR &a) {
+        // 1 when fl(hi - lo) >= 3: the sign of fl(d - 3) is the sign of d - 3 (a difference is never rounded across zero)
+        const int32_t far = g.unary(MARAY_OP_STEP, g.binary(MARAY_OP_ADD, g.binary(MARAY_OP_ADD, a.hi, g.unary(MARAY_OP_NEG, a.lo)), g.konst(-3.0)));
+        const int32_t sl = g.unary(MARAY_OP_STEPSIN, a.lo), sh = g.unary(MARAY_OP_STEPSIN, a.hi);
+        // t != +-0: Step(t) and Step(-t) are both 1 for a zero only
+        auto nz = [&](int32_t t) { return b_not(b_and(g.unary(MARAY_OP_STEP, t), g.unary(MARAY_OP_STEP, g.unary(MARAY_OP_NEG, t)))); };
+        const int32_t ub = b_or(far, b_or(sl, sh));
+        const int32_t lb = b_and(b_not(far), b_and(b_and(sl, nz(a.lo)), b_and(sh, nz(a.hi))));
+        n_rule++;
+        return {lb, ub, true};
+    }
+
+    IVR refine(int32_t i) {
+        const DNode d = g.n[i];
+        if (d.op == D_CONST) return d.cval == d.cval ? IVR{i, i, is_b(i)} : IVR{-1, -1, false};
+        if (d.op == D_PARAM || (d.op < D_CONST && !d.dep))                // uniform: itself
+            return is_b(i) ? IVR{i, i, true} : is_clean(i) ? IVR{i, i, false} : IVR{-1, -1, false};
+        if (d.op > D_CONST) return {-1, -1, false};                       // a coordinate read outside a pattern's argument
+        if (const IVR *hit = memo.find(i)) return *hit;
+        IVR r = is_b(i) ? unknown_bool() : IVR{-1, -1, false};
+        if (d.op == MARAY_OP_STEPSIN) {
+            if (const IVR *a = sin_arg.find(i)) r = step_sin(*a);
+        } else if (is_b(i)) {
+            if ((d.op == MARAY_OP_MUL || d.op == MARAY_OP_MIN || d.op == MARAY_OP_MAX) && is_b(d.a) && is_b(d.b)) {
+                const IVR a = refine(d.a), b = refine(d.b);
+                r = d.op == MARAY_OP_MAX ? IVR{b_or(a.lo, b.lo), b_or(a.hi, b.hi), true} : IVR{b_and(a.lo, b.lo), b_and(a.hi, b.hi), true};
+            } else if (d.op == MARAY_OP_ADD) {                            // 1 + -(b) = NOT b
+                const int32_t nb = g.n[d.a].op == MARAY_OP_NEG ? d.a : d.b;
+                const IVR a = refine(g.n[nb].a);
+                r = {b_not(a.hi), b_not(a.lo), true};
+            } else if (d.op == MARAY_OP_STEP) {
+                const IVR a = refine(d.a);
+                if (a.ok()) r = {g.unary(MARAY_OP_STEP, a.lo), g.unary(MARAY_OP_STEP, a.hi), true};
+            }
+        } else if (is_clean(i)) {
+            // arithmetic on [lb, ub] pairs: every op is correctly rounded, hence monotone in each operand, so interval
+            // arithmetic in the same arithmetic bounds the rounded results (RowBounds::ival); NaN-free values only
+            const IVR a = d.a >= 0 ? refine(d.a) : IVR{-1, -1, false};
+            const IVR b = d.b >= 0 ? refine(d.b) : IVR{-1, -1, false};
+            switch (d.op) {
+            case MARAY_OP_MOV: r = a; break;
+            case MARAY_OP_NEG: if (a.ok()) r = {g.unary(MARAY_OP_NEG, a.hi), g.unary(MARAY_OP_NEG, a.lo), false}; break;
+            case MARAY_OP_ADD: case MARAY_OP_MIN: case MARAY_OP_MAX:
+                if (a.ok() && b.ok()) r = {g.binary(d.op, a.lo, b.lo), g.binary(d.op, a.hi, b.hi), false};
+                break;
+            case MARAY_OP_MUL:
+                if (a.ok() && b.ok()) {
+                    auto mul = [&](int32_t p, int32_t q) { return g.binary(MARAY_OP_MUL, p, q); };
+                    const int32_t p0 = mul(a.lo, b.lo), p1 = mul(a.lo, b.hi), p2 = mul(a.hi, b.lo), p3 = mul(a.hi, b.hi);
+                    r = {b_and(b_and(p0, p1), b_and(p2, p3)), b_or(b_or(p0, p1), b_or(p2, p3)), false};
+                }
+                break;
+            default: break;
+            }
+        }
+        memo.put(i, r);
+        return r;
+    }
+};
+
+// Arguments that are affine in x and y with constant coefficients -- a texture coordinate of a flat shape is -- get their
+// interval from the end points, not from interval arithmetic: a sum of barycentric terms that each vary with x has the
+// width of all its terms added up there, several times the true one, and a pattern's cell is then never decided.
+//   In real arithmetic the value is f(x, y) = A x + B y + C.  A and B are enclosed here in intervals rounded outwards; when
+//   neither straddles zero, f is monotone in x and in y, so f(xl, yl) <= f(x, y) <= f(xh, yh) over the rectangle with the
+//   ends picked by the signs.  What the kernels compute is fl f, the same expression in f64, op by op; `err` bounds
+//   |fl f - f| over the whole domain (a running bound: an op adds its own rounding, 2^-53 of the largest magnitude its
+//   result can have, to what its operands carry), so  fl f(xl, yl) - 2 err <= fl f(x, y) <= fl f(xh, yh) + 2 err.
+//   The ends are evaluated on the device by the expression itself with X and Y replaced; the margin is a constant.
+struct Affine {
+    bool ok = false;
+    double alo = 0, ahi = 0, blo = 0, bhi = 0;      // enclosures of A and B
+    double err = 0;                                 // |fl f - f| <=
+};
+
+std::vector<Affine> affine_forms(const Dag &g, const std::vector<Ival> &iv, size_t n)
+{
+    std::vector<Affine> v(n);
+    const double u = 0x1p-53, tiny = 0x1p-1000;
+    for (size_t i = 0; i < n; i++) {
+        const DNode &d = g.n[i];
+        Affine r;
+        const double mag = std::max(std::fabs(iv[i].lo), std::fabs(iv[i].hi));
+        const bool bounded = !iv[i].nan && std::isfinite(mag);
+        // a value that depends on no coordinate (a parameter, arithmetic on parameters): the same double in every
+        // evaluation, a constant of f whatever it is -- as long as it is one (finite, no NaN)
+        if (!d.dep && (d.op == D_PARAM || d.op < D_CONST)) { r.ok = bounded; v[i] = r; continue; }
+        switch (d.op) {
+        case D_CONST: r.ok = std::isfinite(d.cval); break;
+        case D_X: r.ok = true; r.alo = r.ahi = 1.0; break;
+        case D_Y: r.ok = true; r.blo = r.bhi = 1.0; break;
+        case MARAY_OP_MOV: r = v[d.a]; break;
+        case MARAY_OP_NEG: { const Affine &a = v[d.a]; r = a; r.alo = -a.ahi; r.ahi = -a.alo; r.blo = -a.bhi; r.bhi = -a.blo; break; }
+        case MARAY_OP_ADD: {
+            const Affine &a = v[d.a], &b = v[d.b];
+            if (!a.ok || !b.ok || !bounded) break;
+            r.ok = true;
+            r.alo = down(a.alo + b.alo); r.ahi = up(a.ahi + b.ahi); r.blo = down(a.blo + b.blo); r.bhi = up(a.bhi + b.bhi);
+            if (a.alo == 0 && a.ahi == 0) { r.alo = b.alo; r.ahi = b.ahi; } else if (b.alo == 0 && b.ahi == 0) { r.alo = a.alo; r.ahi = a.ahi; }
+            if (a.blo == 0 && a.bhi == 0) { r.blo = b.blo; r.bhi = b.bhi; } else if (b.blo == 0 && b.bhi == 0) { r.blo = a.blo; r.bhi = a.bhi; }
+            r.err = up(up(a.err + b.err) + up(u * mag + tiny));
+            break;
+        }
+        case MARAY_OP_MUL: {
+            const int32_t ci = g.n[d.a].op == D_CONST ? d.a : g.n[d.b].op == D_CONST ? d.b : -1;
+            if (ci < 0 || !bounded) break;
+            const Affine &a = v[ci == d.a ? d.b : d.a];
+            const double k = g.n[ci].cval;
+            if (!a.ok || !std::isfinite(k)) break;
+            r.ok = true;
+            auto scale = [&](double lo, double hi, double &rlo, double &rhi) {
+                if (lo == 0 && hi == 0) { rlo = rhi = 0; return; }
+                const double p = k * lo, q = k * hi;
+                rlo = down(std::min(p, q)); rhi = up(std::max(p, q));
+            };
+            scale(a.alo, a.ahi, r.alo, r.ahi); scale(a.blo, a.bhi, r.blo, r.bhi);
+            r.err = up(up(std::fabs(k) * a.err) + up(u * mag + tiny));
+            break;
+        }
+        default: break;
+        }
+        if (r.ok && !(std::isfinite(r.alo) && std::isfinite(r.ahi) && std::isfinite(r.blo) && std::isfinite(r.bhi) && std::isfinite(r.err))) r.ok = false;
+        v[i] = r;
+    }
+    return v;
+}
+
+// node i with X and Y replaced by the nodes xr and yr
+int32_t subst_xy(Dag &g, int32_t i, int32_t xr, int32_t yr, std::unordered_map<int32_t, int32_t> &memo)
+{
+    const DNode d = g.n[i];
+    if (d.op == D_X) return xr;
+    if (d.op == D_Y) return yr;
+    if (!d.dep || d.op >= D_CONST) return i;
+    auto hit = memo.find(i);
+    if (hit != memo.end()) return hit->second;
+    int32_t r;
+    if (d.b >= 0) {
+        const int32_t a = subst_xy(g, d.a, xr, yr, memo), b = subst_xy(g, d.b, xr, yr, memo);
+        r = g.binary(d.op, a, b);
+    } else r = g.unary(d.op, subst_xy(g, d.a, xr, yr, memo));
+    memo.emplace(i, r);
+    return r;
+}
+
+// Builds the REFINE section of a lowered scene into t (nothing when no guarded conjunction has a Step(Sin) factor the rule
+// applies to).  Runs after the ROW and PIXEL sections are encoded: it grows the DAG, and nothing of theirs may move.
+//   yval_of, rowub: the scheduler's (per node: its y value, the row bound that guards it); sched: the PIXEL schedule, whose
+//   row-level SKIP items say which guards are in use and what each one guards; row_params: row_param_mask of the program.
+void build_refine(Dag &g, const std::vector<int32_t> &yval_of, const std::vector<int32_t> &rowub, const std::vector<SItem> &sched, uint64_t row_params,
+                  const std::function<std::vector<uint8_t>()> &bool_typing, bool trace, Tape &t)
+{
+    const size_t N = yval_of.size();
+    std::vector<std::pair<int32_t, int32_t>> guarded;      // (the bound, what it guards): every row-level SKIP of the schedule, groups of shapes too
+    for (const SItem &it : sched) {
+        if (it.target < 0 || it.node < 0 || (size_t)it.node >= N || yval_of[it.node] < 0) continue;
+        if ((size_t)it.target >= rowub.size() || rowub[it.target] != it.node) continue;      // a wave-level SKIP
+        guarded.push_back({it.node, it.target});
+    }
+    if (guarded.empty()) return;
+    std::vector<int32_t> sins;
+    {
+        std::vector<uint8_t> seen(g.n.size(), 0);
+        std::vector<int32_t> st;
+        for (auto &gt : guarded) st.push_back(gt.second);
+        while (!st.empty()) {
+            const int32_t v = st.back(); st.pop_back();
+            if (v < 0 || seen[v] || g.n[v].op >= D_CONST) continue;
+            seen[v] = 1;
+            if (g.n[v].op == MARAY_OP_STEPSIN) { sins.push_back(v); continue; }     // (a pattern inside a pattern's argument is not bounded)
+            st.push_back(g.n[v].a); st.push_back(g.n[v].b);
+        }
+        std::sort(sins.begin(), sins.end());
+    }
+    if (sins.empty()) return;
+    const std::vector<uint8_t> isb0 = bool_typing();
+    Refiner R(g, isb0);
+    {
+        // the arguments' intervals over x ...
+        const std::vector<Ival> iv0 = intervals(g);
+        const std::vector<Mono> mono0 = monotonicity(g, iv0);
+        R.clean.resize(iv0.size());
+        for (size_t i = 0; i < iv0.size(); i++) R.clean[i] = !iv0[i].nan;
+        RowBounds rbx(g, isb0, mono0, iv0, DEP_X, D_X, D_XMIN, D_XMAX);
+        std::vector<std::pair<int32_t, RowBounds::IV>> over_x;
+        std::vector<std::pair<int32_t, Refiner::IVR>> over_xy;
+        const std::vector<Affine> aff = affine_forms(g, iv0, iv0.size());
+        const int32_t ends_x[2] = {g.leaf(D_XMIN), g.leaf(D_XMAX)}, ends_y[2] = {g.leaf(D_YMIN), g.leaf(D_YMAX)};
+        std::unordered_map<int32_t, int32_t> sub_memo[4];
+        for (int32_t s : sins) {
+            const int32_t arg = g.n[s].a;
+            const Ival &a = iv0[arg];
+            if (a.nan || !(std::max(std::fabs(a.lo), std::fabs(a.hi)) < 105414350.0)) continue;
+            const Affine &f = aff[arg];
+            // a coefficient whose enclosure straddles zero (the terms in x of an axis-aligned shape's y coordinate cancel, up to
+            // rounding): whichever end is taken, f moves by at most |coefficient| x the domain's width along that axis -- part of the margin
+            auto definite = [](double lo, double hi) { return lo > 0 || hi < 0 || (lo == 0 && hi == 0); };
+            const double dmax = (double)MARAY_DOMAIN_MAX;
+            const double slack = f.ok ? up((definite(f.alo, f.ahi) ? 0.0 : up(std::max(-f.alo, f.ahi) * dmax)) + (definite(f.blo, f.bhi) ? 0.0 : up(std::max(-f.blo, f.bhi) * dmax))) : INFINITY;
+            if (f.ok && slack < 0x1p-20) {
+                // the ends by the coefficients' signs; the margin covers both evaluations' errors and the rounding of its own addition
+                const int xl = f.ahi < 0 ? 1 : 0, yl = f.bhi < 0 ? 1 : 0;
+                const double mag = std::max(std::fabs(a.lo), std::fabs(a.hi));
+                const double margin = up(up(up(up(2.0 * f.err) + slack) + up(4.0 * 0x1p-53 * mag + 0x1p-1000)) * (1.0 + 0x1p-50));
+                const int32_t lo = subst_xy(g, arg, ends_x[xl], ends_y[yl], sub_memo[2 * xl + yl]);
+                const int32_t hi = subst_xy(g, arg, ends_x[1 - xl], ends_y[1 - yl], sub_memo[2 * (1 - xl) + (1 - yl)]);
+                over_xy.push_back({s, Refiner::IVR{g.binary(MARAY_OP_ADD, lo, g.konst(-margin)), g.binary(MARAY_OP_ADD, hi, g.konst(margin)), false}});
+                continue;
+            }
+            if (trace) fprintf(stderr, "maray lower: Step(Sin) %d: argument not affine with coefficients of clear sign (ok %d, A [%g, %g], B [%g, %g], err %g)\n", s, (int)f.ok, f.alo, f.ahi, f.blo, f.bhi, f.err);
+            const RowBounds::IV x = rbx.ival(arg);
+            if (x.ok()) over_x.push_back({s, x});
+        }
+        if (over_x.empty() && over_xy.empty()) return;
+        // ... and the ends' over y: the y-lift of the guards, on a typing of the DAG as it has grown
+        const std::vector<uint8_t> isb1 = bool_typing();
+        const std::vector<Ival> iv1 = intervals(g, &iv0);
+        const std::vector<Mono> mono_y = monotonicity(g, iv1, DEP_Y, D_Y);
+        RowBounds rby(g, isb1, mono_y, iv1, DEP_Y, D_Y, D_YMIN, D_YMAX);
+        for (auto &sx : over_x) {
+            const RowBounds::IV lo = rby.ival(sx.second.lo), hi = rby.ival(sx.second.hi);
+            if (lo.ok() && hi.ok()) over_xy.push_back({sx.first, Refiner::IVR{lo.lo, hi.hi, false}});
+        }
+        // the ends must be finite whatever the rectangle: fl(hi - lo) is then no NaN
+        const std::vector<Ival> iv2 = intervals(g, &iv1);
+        for (auto &s : over_xy) {
+            const Ival &lo = iv2[s.second.lo], &hi = iv2[s.second.hi];
+            if (lo.nan || hi.nan || std::isinf(lo.lo) || std::isinf(lo.hi) || std::isinf(hi.lo) || std::isinf(hi.hi)) continue;
+            R.sin_arg.put(s.first, s.second);
+        }
+    }
+    if (R.sin_arg.keys.empty()) return;
+    // A guard's output must cover EVERYTHING that is skipped when its bit is clear, not only the conjunction that has a SKIP
+    // on it.  The evaluators skip the region of a SKIP (w, t) when the bit of w is clear -- or, where w is a MAX tree over
+    // other guards' bounds, when all of their bits are (jit_guard_plan derives such a guard: it has no bit of its own); a
+    // tile none of whose bits is set skips every region.  So, for every row-level SKIP of the schedule, with t taken apart
+    // over MAX into its operands m (a conjunction is its own only operand):
+    //   - w's own output has to be >= the OR of the operands' second bounds;
+    //   - every guard u that w's MAX tree reaches has to cover the operands it bounds: an operand m with rowub[m] == u
+    //     adds its second bound to u's output (u's geometric 0 proves m 0, u's second 0 now does too, so all of the tree's
+    //     bits clear still proves t 0); an operand that no reached guard bounds, or that has no second bound, leaves none
+    //     of the reached guards an output.
+    // A shape that shares its geometric bound with a neighbour and has no SKIP of its own (too small a cone) is thus part of
+    // the bound's output through the group that skips it.  No output is always sound: the bit stays geometric.
+    std::function<int32_t(int32_t)> bound_of = [&](int32_t m) -> int32_t {            // second upper bound of m (+0.0 where it is 0), or -1
+        if (m < 0) return -1;
+        const DNode d = g.n[m];
+        if (R.is_b(m)) return R.refine(m).hi;
+        if (d.op == MARAY_OP_MUL)                           // a shape times a finite colour of clear sign: +0 where the shape is
+            for (int o = 0; o < 2; o++) {
+                const int32_t c = o ? d.a : d.b, sh = o ? d.b : d.a;
+                if (g.n[c].op == D_CONST && std::isfinite(g.n[c].cval) && !std::signbit(g.n[c].cval) && g.n[c].cval != 0.0) return bound_of(sh);
+            }
+        return -1;
+    };
+    std::unordered_map<int32_t, int32_t> out_of;            // bound node -> OR of what it has to cover
+    std::unordered_set<int32_t> none;                       // bound nodes that get no output
+    auto cover = [&](int32_t u, int32_t m) {                // u's output has to cover operand m
+        const int32_t ub = bound_of(m);
+        if (ub < 0 || g.n[ub].op >= D_CONST) { none.insert(u); return; }
+        auto at = out_of.find(u);
+        if (at == out_of.end()) out_of.emplace(u, ub);
+        else at->second = g.binary(MARAY_OP_MAX, at->second, ub);
+    };
+    for (auto &gt : guarded) {
+        const int32_t w = gt.first;
+        std::vector<int32_t> operands, st{gt.second};       // t over MAX
+        while (!st.empty()) {
+            const int32_t v = st.back(); st.pop_back();
+            if (g.n[v].op == MARAY_OP_MAX) { st.push_back(g.n[v].a); st.push_back(g.n[v].b); }
+            else operands.push_back(v);
+        }
+        std::vector<int32_t> reached;                       // guards below w's MAX tree
+        st.assign(1, w);
+        while (!st.empty()) {
+            const int32_t v = st.back(); st.pop_back();
+            if (v != w && (size_t)v < N && yval_of[v] >= 0) reached.push_back(v);
+            if (g.n[v].op == MARAY_OP_MAX) { st.push_back(g.n[v].a); st.push_back(g.n[v].b); }
+        }
+        for (int32_t m : operands) cover(w, m);
+        bool all = true;
+        for (int32_t m : operands) {
+            const int32_t u = (size_t)m < rowub.size() ? rowub[m] : -1;
+            if (u >= 0 && std::find(reached.begin(), reached.end(), u) != reached.end()) cover(u, m);
+            else all = false;
+        }
+        if (!all) for (int32_t u : reached) none.insert(u);
+    }
+    std::vector<std::pair<int32_t, int32_t>> outs;         // (y value, node)
+    for (auto &o : out_of) if (!none.count(o.first)) outs.push_back({yval_of[o.first], o.second});
+    std::sort(outs.begin(), outs.end());
+    Section sec;
+    std::vector<uint8_t> in(g.n.size(), 0);
+    for (auto &o : outs) {
+        if (g.n[o.second].op >= D_CONST || (uint32_t)o.first > 0x1FFFu) continue;
+        // the cone; a parameter the ROW section does not read is not part of the ROW tables' key: no output then
+        std::vector<int32_t> cone, st{o.second};
+        bool keyed = true;
+        std::vector<uint8_t> seen(g.n.size(), 0);
+        while (!st.empty() && keyed) {
+            const int32_t v = st.back(); st.pop_back();
+            if (v < 0 || seen[v]) continue;
+            seen[v] = 1;
+            if (g.n[v].op == D_PARAM) keyed = g.n[v].aux < 64 && ((row_params >> g.n[v].aux) & 1);
+            if (g.n[v].op == D_X || g.n[v].op == D_Y) keyed = false;      // (cannot happen: the bounds are free of both)
+            if (g.n[v].op >= D_CONST) continue;
+            cone.push_back(v);
+            st.push_back(g.n[v].a); st.push_back(g.n[v].b);
+        }
+        if (!keyed) continue;
+        for (int32_t v : cone) in[v] = 1;
+        sec.outs.push_back({o.second, (uint32_t)o.first});
+    }
+    if (sec.outs.empty()) return;
+    std::sort(sec.outs.begin(), sec.outs.end(), [](const std::pair<int32_t, uint32_t> &a, const std::pair<int32_t, uint32_t> &b) { return a.second < b.second; });
+    Lowerer L(g);
+    L.regions = false;                      // straight-line cones: a job evaluates a handful of them
+    L.isbool = bool_typing();
+    L.sin_bounded.assign(g.n.size(), 0);
+    {
+        const std::vector<Ival> iv = intervals(g);
+        for (size_t i = 0; i < g.n.size(); i++) {
+            if (!in[i] || (g.n[i].op != MARAY_OP_SIN && g.n[i].op != MARAY_OP_STEPSIN)) continue;
+            const Ival &a = iv[g.n[i].a];
+            if (!a.nan && std::max(std::fabs(a.lo), std::fabs(a.hi)) < 105414350.0) L.sin_bounded[i] = 1;
+        }
+    }
+    L.in_section = in;
+    L.build(sec, false);
+    t.refine_consts = std::move(L.consts);
+    if (t.refine_consts.empty()) t.refine_consts.push_back(0.0);
+    t.refine_ops = std::move(sec.ops);
+    t.refine_slots = sec.n_slots;
+    t.refine_outs = (uint32_t)sec.outs.size();
+    if (trace) fprintf(stderr, "maray lower: REFINE section: %zu Step(Sin) factors bounded, %u outputs for %zu guarded conjunctions, %zu ops\n",
+                       R.sin_arg.keys.size(), t.refine_outs, guarded.size(), t.refine_ops.size());
+}
+
 }   // namespace
 
 void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
@@ -1558,6 +1928,12 @@ void lower_scene(const Scene &scene_in, const maray_lower_opts &opts, Tape &t)
     for (uint64_t ins : t.pix_ops) info.op_histogram[MARAY_INS_OP(ins)]++;
     const uint64_t row_params = row_param_mask(t.program());
     info.row_params[0] = (uint32_t)row_params; info.row_params[1] = (uint32_t)(row_params >> 32);
+    // The REFINE section, last: it grows the DAG, and the two sections above are what they were without it.
+    t.refine_consts.clear(); t.refine_ops.clear(); t.refine_slots = t.refine_outs = 0;
+    if (row_guards && opts.no_y_spans == 0) {
+        build_refine(g, L.yval_of, L.rowub, pix.sched, row_params, bool_typing, trace, t);
+        lap("REFINE section");
+    }
 }
 
 }   // namespace maray
