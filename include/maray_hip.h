@@ -471,6 +471,9 @@ typedef struct maray_gen_opts {
     uint32_t transfer;       /* MARAY_TRANSFER_* (offset 28; "transfer"): programs and contexts are kept per (k, filter, transfer) */
 } maray_gen_opts;
 enum { MARAY_ENCODER_HOST = 0, MARAY_ENCODER_DEVICE = 1 };
+/* A flag on `encoder`: the device encoder with dynamic-Huffman codes ("device PNG encoder": MARAY_PNG_CODES_DYNAMIC).  The
+ * valid words are 0, 1 and MARAY_ENCODER_DEVICE | MARAY_ENCODER_DYNAMIC; the flag alone is MARAY_E_ARG like every other word. */
+#define MARAY_ENCODER_DYNAMIC 0x100
 
 /* gen_to_image: fills the caller's w*h*3 RGB8 buffer. */
 int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
@@ -491,7 +494,8 @@ int maray_gen_cache_info(char *out, size_t cap);
  * call, maray_hip_render_rows_shutter_device) into its encoder's band buffer, encodes them on its own device and hands over
  * only the compressed segments; the calling thread puts the file together in row order (the same bytes for any n_devices and
  * tile_rows).  With a report the percentage is still printed, but the partial file is NOT re-saved: there is no host raster.
- * A scene of size 0 in x or y is MARAY_E_ARG with this encoder. */
+ * A scene of size 0 in x or y is MARAY_E_ARG with this encoder.  With MARAY_ENCODER_DEVICE | MARAY_ENCODER_DYNAMIC every worker's
+ * encoder writes dynamic codes: the same pixels in a smaller file, whose bytes depend on n_devices and tile_rows. */
 int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
               const maray_gen_opts *opts, maray_report report, const char *png_path);
 
@@ -544,6 +548,51 @@ int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *val
  * of its gathered stream; and the bytes the process' encoders have copied to the host so far (payloads and totals). */
 int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32_t h, int reps, float *ms_avg, uint64_t *stream_bytes);
 uint64_t maray_hip_png_bytes_to_host(void);
+/* Dynamic-Huffman codes: a second way of coding the SAME tokens, opt-in everywhere; MARAY_PNG_CODES_FIXED is everything
+ * above, byte for byte.  Any other value of a `codes` argument: MARAY_E_ARG, reported before a device is looked for.
+ *   - tokens: exactly the fixed coder's.  Each row is one filter byte 0 plus 3 w bytes, cut into segments of SEG = 256
+ *     pixels; a segment's first pixel is literal; a run of pixels equal to the pixel before them is one match of distance 3
+ *     whose length is a multiple of 3 and at most 192 (a run is closed at every 64-pixel step).  The token sequence is a
+ *     function of the raster alone; only the codes differ;
+ *   - a band's piece: per band of rows the device counts the tokens, the host fits a code to the counts, and the device
+ *     writes the band as ONE dynamic block: BFINAL = 0, BTYPE = 10; HLIT, HDIST, HCLEN, the code-length code and the
+ *     lengths (the run symbols 16 .. 18 may be used or not: today they are not); every segment's tokens in row-major order
+ *     with nothing between segments; symbol 256; then the empty stored block that ends on a byte boundary (three zero bits,
+ *     zeros to the byte, 00 00 FF FF).  Pieces concatenate at byte granularity, and the stream around them is unchanged:
+ *     78 01, the pieces, 01 00 00 FF FF, the Adler-32;
+ *   - codes: any prefix code with lengths of at most 15 in which length 0 is given to exactly the unused symbols and the
+ *     literal/length code is complete (symbols 0 and 256 always occur: it has at least two symbols).  The distance code set
+ *     is the symbols 0, 1, 2 with lengths 0 0 1 when the band holds a match, and one symbol of length 0 when it holds none.
+ *     Where the unrestricted Huffman tree of the band's counts is at most 15 deep the code costs what that tree costs (an
+ *     optimal code; the cost is unique though the tree is not); deeper, it is an optimal code among those of at most 15 bits;
+ *   - what the bytes depend on: the raster AND how its rows were cut into bands and encode calls (MARAY_PNG_BAND_ROWS,
+ *     tile_rows, the device split) -- unlike the fixed coder's "function of the raster alone".  The decoded raster does not
+ *     depend on the cut; the same raster and the same cuts give the same bytes on every stream and in every run;
+ *   - band size: a dynamic band holds at most 2^28 filtered bytes (MARAY_PNG_BAND_ROWS is clipped to that), so every bit
+ *     offset inside a band is below 15 x 2^28 < 2^32; everything past a band is 64-bit, as above;
+ *   - slot: a segment of n bytes takes at most ceil(15 n / 8) bytes of scratch;
+ *   - errors, limits and the Adler-32: unchanged.
+ * How it runs, per band: maray_png_histogram (the compress kernel's tokeniser feeding 286 counts in LDS; a capped grid that
+ * strides over the segments; every block stores its partial counts) and maray_png_histogram_sum; 1,152 bytes of counts to the
+ * host, which fits the code (maray_png_dynamic_codes) and sends back 1,144 bytes of codes; maray_png_compress_dyn (a
+ * segment's bits into its slot, its length in bits), maray_png_scan (bit offsets), maray_png_zero and maray_png_gather_bits
+ * (every segment's bits shifted to its place behind the header's); then the totals and exactly the piece's bytes. */
+enum { MARAY_PNG_CODES_FIXED = 0, MARAY_PNG_CODES_DYNAMIC = 1 };
+/* The three entry points above with a `codes` argument; with MARAY_PNG_CODES_FIXED each is exactly the call it extends. */
+int maray_hip_png_encode_device_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, void *stream, uint8_t **png_out,
+                                   size_t *n_out);
+int maray_hip_render_png_ex(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint32_t codes, uint8_t **png_out,
+                            size_t *n_out);
+/* (DYNAMIC: ONE band is (3 w + 1) h <= 2^28; the band's code is fitted once, before the timed loop; the kernels timed are the
+ * six above, and *stream_bytes the bytes of the band's piece) */
+int maray_hip_time_png_encode_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, int reps, float *ms_avg,
+                                 uint64_t *stream_bytes);
+/* The host's part on its own; needs no device.  From a band's counts -- lit_counts[256] >= 1 and at least one more symbol;
+ * of the distance counts only dist_counts[2] may be above 0 (else MARAY_E_ARG) -- the code lengths, and in `header` the
+ * block's bits LSB-first from BFINAL up to but not including the first token (*header_bits of them, at most 2,286; the rest
+ * of the last byte is zero).  cap < ceil(*header_bits / 8): MARAY_E_ARG. */
+int maray_png_dynamic_codes(const uint32_t lit_counts[286], const uint32_t dist_counts[30], uint8_t lit_lens[286], uint8_t dist_lens[30],
+                            uint8_t *header, size_t cap, size_t *header_bits);
 
 /* ---- animation (one APNG, encoded on the device frame by frame) ----------------------------------------------------
  * An animation is written as ONE file: an APNG, i.e. a PNG whose IDAT image is frame 0 (any PNG reader shows it) followed
@@ -594,7 +643,8 @@ int maray_hip_time_frame_delta_copy(int device, uint32_t w, uint32_t h, int reps
  * parameter count), written to `path` as one APNG.  With opts->shutter = n > 1 each image's sub-frames are the scene's
  * maray_scene_shutter_values around that row.  The tape and the context come from what maray_gen_to_image keeps, exactly as
  * it finds them: a second animation of a scene pays no lowering.  One device: opts->n_devices > 1 is MARAY_E_ARG;
- * opts->encoder is ignored (an animation is always encoded on the device); there are no progress reports.  The scene's
+ * opts->encoder is ignored (an animation is always encoded on the device) but for the flag MARAY_ENCODER_DYNAMIC: dynamic
+ * codes for every frame; there are no progress reports.  The scene's
  * current parameter values are as they were when the call returns, however it ends. */
 int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
                         uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path);

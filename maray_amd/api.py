@@ -14,6 +14,8 @@ BACKEND_TAPE, BACKEND_TAPE_SMEM, BACKEND_JIT, BACKEND_AUTO = 0, 1, 2, 3
 REPORT_NONE, REPORT_ROW, REPORT_DURATION_MS = 0, 1, 2
 FILTER_BOX, FILTER_TENT = 0, 1
 ENCODER_HOST, ENCODER_DEVICE = 0, 1
+ENCODER_DYNAMIC = 0x100                 # a flag on ENCODER_DEVICE: dynamic-Huffman codes (MARAY_ENCODER_DYNAMIC)
+CODES_FIXED, CODES_DYNAMIC = 0, 1       # MARAY_PNG_CODES_*
 TRANSFER_NONE, TRANSFER_SRGB = 0, 1
 
 
@@ -166,6 +168,10 @@ def lib():
         'maray_hip_png_encode_device': (C.c_int, [C.c_int, vp, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_render_png': (C.c_int, [vp, u32, u32, vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_time_png_encode': (C.c_int, [C.c_int, vp, u32, u32, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_hip_png_encode_device_ex': (C.c_int, [C.c_int, vp, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_png_ex': (C.c_int, [vp, u32, u32, vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_png_encode_ex': (C.c_int, [C.c_int, vp, u32, u32, u32, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_png_dynamic_codes': (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         'maray_hip_png_bytes_to_host': (C.c_uint64, []),
         'maray_hip_frame_delta': (C.c_int, [C.c_int, vp, vp, u32, u32, vp, C.POINTER(u32)]),
         'maray_hip_apng_encode_device': (C.c_int, [C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -582,12 +588,12 @@ class Context:
         cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
         _check(lib().maray_hip_render_tiles_shutter(self._h, w, h, flat, len(tiles), vp_, n, image.ctypes.data, cb, None))
 
-    def render_png(self, w, h, frames=None):
-        """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png); frames: as
-        for render_rows_shutter (None: the plain render)."""
+    def render_png(self, w, h, frames=None, codes=CODES_FIXED):
+        """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png_ex); frames: as
+        for render_rows_shutter (None: the plain render); codes=CODES_DYNAMIC: a Huffman code fitted to every band."""
         n, vp_, keep = (0, None, None) if frames is None else self._frames(frames)
         p, sz = C.c_void_p(), C.c_size_t()
-        _check(lib().maray_hip_render_png(self._h, w, h, vp_, n, C.byref(p), C.byref(sz)))
+        _check(lib().maray_hip_render_png_ex(self._h, w, h, vp_, n, codes, C.byref(p), C.byref(sz)))
         return _take_bytes(p, sz)
 
     def render_apng(self, w, h, frames, sub=1, fps=(25, 1), loops=0):
@@ -688,7 +694,8 @@ def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_ki
     """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
     parameter spans; filter=FILTER_TENT: the tent reconstruction filter; transfer=TRANSFER_SRGB: averaged in linear light; as
     gen_to_image).  encoder=ENCODER_DEVICE: the PNG's
-    zlib stream is built on the devices and no raster crosses to the host (include/maray_hip.h, "device PNG encoder")."""
+    zlib stream is built on the devices and no raster crosses to the host (include/maray_hip.h, "device PNG encoder");
+    ENCODER_DEVICE | ENCODER_DYNAMIC: with dynamic-Huffman codes, the same pixels in a smaller file."""
     arr, n, keep = _textures(textures)
     go = GenOpts()
     go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.encoder = backend, n_devices, samples, shutter, filter, encoder
@@ -703,11 +710,12 @@ def _delay(fps):
 
 
 def gen_animation(scene, path, frames, fps=(25, 1), loops=0, textures=None, backend=BACKEND_AUTO, n_devices=0, samples=0, shutter=0, spans=None,
-                  filter=FILTER_BOX, transfer=TRANSFER_NONE):
+                  filter=FILTER_BOX, transfer=TRANSFER_NONE, codes=CODES_FIXED):
     """An animation of the scene as one APNG at `path`, rendered and encoded on one device (maray_gen_animation).  frames: an
     (n, P) matrix, one row of values per image and one column per declared parameter, or a dict {name_or_id: sequence} -- the
     parameters it does not name keep their current value.  fps, loops: as Context.render_apng; the other options as gen's
-    (shutter=n with spans: every image the mean of n sub-frames around its values).  The scene's values are as they were
+    (shutter=n with spans: every image the mean of n sub-frames around its values); codes=CODES_DYNAMIC: dynamic-Huffman
+    codes for every frame (the flag ENCODER_DYNAMIC on the options' encoder word).  The scene's values are as they were
     afterwards."""
     for k, v in (spans or {}).items():
         scene.set_param_span(scene.param_index(k), v)
@@ -728,6 +736,9 @@ def gen_animation(scene, path, frames, fps=(25, 1), loops=0, textures=None, back
     arr, n, keep = _textures(textures)
     go = GenOpts()
     go.backend, go.n_devices, go.samples, go.shutter, go.filter, go.transfer = backend, n_devices, samples, shutter, filter, transfer
+    if codes not in (CODES_FIXED, CODES_DYNAMIC):
+        raise MarayError(-1, 'gen_animation: unknown PNG codes')
+    go.encoder = ENCODER_DYNAMIC if codes == CODES_DYNAMIC else 0
     num, den = _delay(fps)
     _check(lib().maray_gen_animation(scene._h, arr, n, C.byref(go), a.ctypes.data if a.size else None, a.shape[0], num, den, loops, os.fsencode(path)))
 
@@ -767,19 +778,33 @@ def _take_bytes(p, sz):
         lib().maray_free(p)
 
 
-def png_encode_device(d_ptr, w, h, device=0, stream=0):
+def png_encode_device(d_ptr, w, h, device=0, stream=0, codes=CODES_FIXED):
     """A packed (h, w, 3) uint8 raster in device memory (any alignment) -> the bytes of a PNG, encoded on the device
-    (maray_hip_png_encode_device); enqueued on `stream` and waited for."""
+    (maray_hip_png_encode_device_ex); enqueued on `stream` and waited for.  codes=CODES_DYNAMIC: a Huffman code fitted to
+    every band of rows instead of the fixed codes."""
     p, sz = C.c_void_p(), C.c_size_t()
-    _check(lib().maray_hip_png_encode_device(device, d_ptr or None, w, h, stream or None, C.byref(p), C.byref(sz)))
+    _check(lib().maray_hip_png_encode_device_ex(device, d_ptr or None, w, h, codes, stream or None, C.byref(p), C.byref(sz)))
     return _take_bytes(p, sz)
 
 
-def time_png_encode(d_ptr, w, h, device=0, reps=10):
-    """(average ms of the encoder's three kernels over the raster as one band, bytes of the stream they make)."""
+def time_png_encode(d_ptr, w, h, device=0, reps=10, codes=CODES_FIXED):
+    """(average ms of the encoder's kernels over the raster as one band, bytes of the stream they make)."""
     ms, nb = C.c_float(), C.c_uint64()
-    _check(lib().maray_hip_time_png_encode(device, d_ptr or None, w, h, reps, C.byref(ms), C.byref(nb)))
+    _check(lib().maray_hip_time_png_encode_ex(device, d_ptr or None, w, h, codes, reps, C.byref(ms), C.byref(nb)))
     return ms.value, nb.value
+
+
+def png_dynamic_codes(lit_counts, dist_counts):
+    """The host's part of the dynamic coder (maray_png_dynamic_codes; no device): 286 literal/length counts and 30 distance
+    counts -> (lit_lens uint8[286], dist_lens uint8[30], the block header's bytes, its bits)."""
+    lit = np.ascontiguousarray(lit_counts, np.uint32)
+    dist = np.ascontiguousarray(dist_counts, np.uint32)
+    if lit.shape != (286,) or dist.shape != (30,):
+        raise MarayError(-1, 'png_dynamic_codes: 286 literal/length counts and 30 distance counts')
+    lit_lens, dist_lens, header, bits = np.zeros(286, np.uint8), np.zeros(30, np.uint8), np.zeros(512, np.uint8), C.c_size_t()
+    _check(lib().maray_png_dynamic_codes(lit.ctypes.data, dist.ctypes.data, lit_lens.ctypes.data, dist_lens.ctypes.data, header.ctypes.data,
+                                         header.size, C.byref(bits)))
+    return lit_lens, dist_lens, header[:(bits.value + 7) // 8].tobytes(), bits.value
 
 
 def png_bytes_to_host():

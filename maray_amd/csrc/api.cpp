@@ -908,25 +908,39 @@ static void png_hand_over(const std::vector<uint8_t> &file, uint8_t **png_out, s
 
 int maray_hip_png_encode_device(int device, const void *d_rgb8, uint32_t w, uint32_t h, void *stream, uint8_t **png_out, size_t *n_out)
 {
+    return maray_hip_png_encode_device_ex(device, d_rgb8, w, h, MARAY_PNG_CODES_FIXED, stream, png_out, n_out);
+}
+
+int maray_hip_png_encode_device_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, void *stream, uint8_t **png_out,
+                                   size_t *n_out)
+{
     return guard([&] {
         REQUIRE(png_out && n_out, "null argument");
         *png_out = nullptr; *n_out = 0;
+        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
         REQUIRE(d_rgb8, "null argument");
         REQUIRE(w && h, "empty image");
         png_check_size(w, h);
         PngEncoderLease E(device);
         PngPiece piece;
         piece.y0 = 0; piece.y1 = h;
-        E->encode_rows((const unsigned char *)d_rgb8, w, h, (hipStream_t)stream, piece);
+        E->encode_rows((const unsigned char *)d_rgb8, w, h, (hipStream_t)stream, piece, codes);
         png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
     });
 }
 
 int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint8_t **png_out, size_t *n_out)
 {
+    return maray_hip_render_png_ex(c, w, h, values, n_frames, MARAY_PNG_CODES_FIXED, png_out, n_out);
+}
+
+int maray_hip_render_png_ex(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint32_t codes, uint8_t **png_out,
+                            size_t *n_out)
+{
     return guard([&] {
         REQUIRE(png_out && n_out, "null argument");
         *png_out = nullptr; *n_out = 0;
+        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
         REQUIRE(c && c->backend, "null context");
         REQUIRE(w && h, "empty image");
         check_rows(w, h, 0, h);
@@ -946,16 +960,23 @@ int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *val
         E->encode_rendered(w, 0, h, E->own_stream, [&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
             if (values) c->backend->render_device_shutter(w, h, RowBlocks::range(b0, b1), values, n_frames, d8, st);
             else c->backend->render_device(w, h, RowBlocks::range(b0, b1), d8, nullptr, st);
-        }, piece);
+        }, piece, codes);
         png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
     });
 }
 
 int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32_t h, int reps, float *ms_avg, uint64_t *stream_bytes)
 {
+    return maray_hip_time_png_encode_ex(device, d_rgb8, w, h, MARAY_PNG_CODES_FIXED, reps, ms_avg, stream_bytes);
+}
+
+int maray_hip_time_png_encode_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, int reps, float *ms_avg,
+                                 uint64_t *stream_bytes)
+{
     return guard([&] {
         REQUIRE(ms_avg, "null argument");
-        *ms_avg = png_time_kernels(device, (const unsigned char *)d_rgb8, w, h, reps, stream_bytes);
+        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
+        *ms_avg = png_time_kernels(device, (const unsigned char *)d_rgb8, w, h, reps, stream_bytes, codes);
     });
 }
 
@@ -999,7 +1020,15 @@ int maray_hip_apng_encode_device(int device, const void *d_frames, uint32_t n_fr
 int maray_hip_render_apng(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
                           uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, uint8_t **out, size_t *n_out)
 {
+    return maray::render_apng_codes(c, w, h, values, n_images, n_sub, delay_num, delay_den, n_plays, MARAY_PNG_CODES_FIXED, out, n_out);
+}
+
+// maray_hip_render_apng with the frames' codes (apng_device.hpp): maray_gen_animation's way in
+extern "C++" int maray::render_apng_codes(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                             uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, uint32_t codes, uint8_t **out, size_t *n_out)
+{
     return guard([&] {
+        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
         REQUIRE(out && n_out, "null argument");
         *out = nullptr; *n_out = 0;
         REQUIRE(c && c->backend, "null context");
@@ -1019,7 +1048,7 @@ int maray_hip_render_apng(maray_ctx *c, uint32_t w, uint32_t h, const double *va
             device = it->second;
         }
         PngEncoderLease E(device);
-        ApngWriter W(*E.e, w, h, n_images, delay_num, delay_den, n_plays);
+        ApngWriter W(*E.e, w, h, n_images, delay_num, delay_den, n_plays, codes);
         for (uint32_t i = 0; i < n_images; i++) {
             const double *rows = values ? values + (size_t)i * n_sub * P : nullptr;
             W.add_frame([&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {

@@ -36,9 +36,11 @@ void apng_check_timing(uint32_t n_frames, uint32_t delay_num, uint32_t delay_den
     if (delay_num > 65535 || delay_den > 65535) throw Error{MARAY_E_ARG, "delay_num and delay_den must fit 16 bits"};
 }
 
-ApngWriter::ApngWriter(PngEncoder &enc, uint32_t w_, uint32_t h_, uint32_t n_frames_, uint32_t delay_num_, uint32_t delay_den_, uint32_t n_plays)
-    : E(enc), w(w_), h(h_), n_frames(n_frames_), delay_num(delay_num_), delay_den(delay_den_)
+ApngWriter::ApngWriter(PngEncoder &enc, uint32_t w_, uint32_t h_, uint32_t n_frames_, uint32_t delay_num_, uint32_t delay_den_, uint32_t n_plays,
+                       uint32_t codes_)
+    : E(enc), w(w_), h(h_), n_frames(n_frames_), delay_num(delay_num_), delay_den(delay_den_), codes(codes_)
 {
+    if (codes != MARAY_PNG_CODES_FIXED && codes != MARAY_PNG_CODES_DYNAMIC) throw Error{MARAY_E_ARG, "unknown PNG codes"};
     apng_check_timing(n_frames, delay_num, delay_den);
     if (!w || !h) throw Error{MARAY_E_ARG, "empty image"};
     apng_check_frame(w, h);
@@ -91,16 +93,16 @@ void ApngWriter::add_frame(const Render &render, hipStream_t st)
     }
     piece.y0 = 0; piece.y1 = r.h;
     if (r.w == w)
-        E.encode_rows(cur + (size_t)r.y * w * 3, w, r.h, st, piece);      // whole rows are packed already
+        E.encode_rows(cur + (size_t)r.y * w * 3, w, r.h, st, piece, codes);      // whole rows are packed already
     else {
         // the box's rows, cropped band by band: encode_rows wants packed rows of the box's width
-        const uint32_t bstep = E.band_rows(r.w);
+        const uint32_t bstep = E.band_rows(r.w, codes);
         unsigned char *band = E.band_buffer((size_t)std::min(bstep, r.h) * r.w * 3);
         for (uint32_t y = 0; y < r.h; y += std::min(bstep, r.h - y)) {
             const uint32_t rows = std::min(bstep, r.h - y);
             HIP_TRY(hipMemcpy2DAsync(band, (size_t)r.w * 3, cur + ((size_t)(r.y + y) * w + r.x) * 3, (size_t)w * 3, (size_t)r.w * 3, rows,
                                      hipMemcpyDeviceToDevice, st));
-            E.encode_rows(band, r.w, rows, st, piece);
+            E.encode_rows(band, r.w, rows, st, piece, codes);
         }
     }
     const std::vector<uint8_t> z = png_close_stream(r.h, {&piece});

@@ -62,6 +62,7 @@ struct ApngWriter {
     using Render = std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)>;
     PngEncoder &E;
     const uint32_t w, h, n_frames, delay_num, delay_den;
+    const uint32_t codes;                                // MARAY_PNG_CODES_*: how every frame's rows are coded (encode_rows)
     unsigned char *raster[2] = {nullptr, nullptr};      // prev and cur, swapped between frames
     uint32_t *d_partials = nullptr, *d_box = nullptr;    // one allocation
     uint32_t *h_box = nullptr;                           // pinned host
@@ -69,12 +70,17 @@ struct ApngWriter {
     std::vector<uint8_t> file;
     std::vector<ApngRect> rects;                         // per frame (measurements)
 
-    ApngWriter(PngEncoder &enc, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays);
+    ApngWriter(PngEncoder &enc, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays,
+               uint32_t codes = MARAY_PNG_CODES_FIXED);
     ~ApngWriter();
     ApngWriter(const ApngWriter &) = delete;
     void add_frame(const Render &render, hipStream_t st);
     std::vector<uint8_t> finish();
     void release();                                      // the device and pinned memory (the destructor's work)
 };
+
+// maray_hip_render_apng with the codes of every frame (api.cpp); with MARAY_PNG_CODES_FIXED exactly that call
+int render_apng_codes(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub, uint32_t delay_num,
+                      uint32_t delay_den, uint32_t n_plays, uint32_t codes, uint8_t **out, size_t *n_out);
 
 }   // namespace maray

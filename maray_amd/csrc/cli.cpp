@@ -46,7 +46,9 @@ static void usage()
             "      --linear                 Average samples (-s) and shutter frames in linear light: bytes are decoded as sRGB,\n"
             "                               averaged and encoded again; alone it changes nothing\n"
             "      --encoder <e>            host | device (default: host); device builds the PNG's compressed stream on the GPU,\n"
-            "                               so that no raster crosses to the host (same pixels, other file bytes)\n");
+            "                               so that no raster crosses to the host (same pixels, other file bytes)\n"
+            "      --png-codes <c>          fixed | dynamic (default: fixed); needs --encoder device or --apng.  dynamic fits a Huffman\n"
+            "                               code to every band of rows: the same pixels in a several times smaller file\n");
 }
 
 namespace {
@@ -97,6 +99,7 @@ int main(int argc, char **argv)
     uint32_t shutter_samples = 0;
     bool linear = false;                // --linear
     bool apng = false;                  // --apng
+    bool png_codes_given = false, dynamic_codes = false;      // --png-codes
     uint32_t fps_num = 25, fps_den = 1, loops = 0;
     maray_gen_opts go;
     memset(&go, 0, sizeof go);
@@ -154,6 +157,13 @@ int main(int argc, char **argv)
             else if (e == "device") go.encoder = MARAY_ENCODER_DEVICE;
             else { fprintf(stderr, "Error: --encoder takes host or device, not `%s`\n", e.c_str()); usage(); return 2; }
         }
+        else if (a == "--png-codes") {
+            const std::string e = val();
+            png_codes_given = true;
+            if (e == "fixed") dynamic_codes = false;
+            else if (e == "dynamic") dynamic_codes = true;
+            else { fprintf(stderr, "Error: --png-codes takes fixed or dynamic, not `%s`\n", e.c_str()); usage(); return 2; }
+        }
         else if (a == "-p" || a == "--param") {
             Param p; std::vector<double> n;
             if (!split_name(val(), p.name, n) || (n.size() != 1 && n.size() != 3)) { fprintf(stderr, "Error: -p takes NAME=VALUE or NAME=VALUE:LO:HI\n"); usage(); return 2; }
@@ -196,6 +206,12 @@ int main(int argc, char **argv)
     }
     if (input.empty() || output.empty()) { usage(); return 2; }
     if (go.filter == MARAY_FILTER_TENT && go.samples < 2) { fprintf(stderr, "Error: --filter tent needs -s 2, 4 or 8\n"); usage(); return 2; }
+    if (png_codes_given && go.encoder != MARAY_ENCODER_DEVICE && !apng) {
+        fprintf(stderr, "Error: --png-codes chooses the device encoder's codes: it needs --encoder device or --apng\n");
+        usage();
+        return 2;
+    }
+    if (dynamic_codes) go.encoder |= MARAY_ENCODER_DYNAMIC;
     if (apng && !frames) { fprintf(stderr, "Error: --apng writes an animation: it needs --animate NAME=FROM:TO:FRAMES\n"); return 2; }
     if (apng && output.find('%') != std::string::npos) { fprintf(stderr, "Error: --apng writes one file: --output must not contain a `%%d` conversion\n"); return 2; }
     if (apng && go.n_devices > 1) { fprintf(stderr, "Error: --apng renders and encodes on one device: --gpus must be 1\n"); return 2; }

@@ -257,7 +257,9 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
 {
     if (!s || (!rgb8 && !png)) return fail_with(MARAY_E_ARG, "null argument");
     return gen_guard([&]() -> int {
-    if (opts && opts->encoder != MARAY_ENCODER_HOST && opts->encoder != MARAY_ENCODER_DEVICE) return fail_with(MARAY_E_ARG, "unknown encoder");
+    if (opts && opts->encoder != MARAY_ENCODER_HOST && opts->encoder != MARAY_ENCODER_DEVICE &&
+        opts->encoder != (MARAY_ENCODER_DEVICE | MARAY_ENCODER_DYNAMIC)) return fail_with(MARAY_E_ARG, "unknown encoder");
+    const uint32_t png_codes = opts && (opts->encoder & MARAY_ENCODER_DYNAMIC) ? MARAY_PNG_CODES_DYNAMIC : MARAY_PNG_CODES_FIXED;
     const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
     if (transfer != MARAY_TRANSFER_NONE && transfer != MARAY_TRANSFER_SRGB) return fail_with(MARAY_E_ARG, "unknown transfer");
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
@@ -403,7 +405,7 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
                         const int rr = shutter_values.empty() ? maray_hip_render_rows_device(ctx, w, h, b0, b1, d8, nullptr, st)
                                                               : maray_hip_render_rows_shutter_device(ctx, w, h, b0, b1, shutter_values.data(), shutter, d8, st);
                         if (rr) throw Error{rr, maray_last_error()};
-                    }, *piece);
+                    }, *piece, png_codes);
                     const uint32_t y0 = piece->y0, y1 = piece->y1;
                     { std::lock_guard<std::mutex> lk(png->m); png->pieces.push_back(std::move(piece)); }
                     on_tile(&tu, y0, y1);
@@ -480,12 +482,13 @@ extern "C" int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_
     uint32_t w = 0, h = 0;
     maray_scene_size(s, &w, &h);
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
-    if (opts && opts->encoder == MARAY_ENCODER_DEVICE) {
+    if (opts && (opts->encoder == MARAY_ENCODER_DEVICE || opts->encoder == (MARAY_ENCODER_DEVICE | MARAY_ENCODER_DYNAMIC))) {
         if (!w || !h) return fail_with(MARAY_E_ARG, "empty image");
         png_check_size(w, h);
         PngCollect col;
         if (const int rc = gen_run(s, tex, n_tex, opts, report, gen_report_device, nullptr, nullptr, w, h, &col)) return rc;
         // the calling thread assembles the file in row order: segments are independent, so it is the single-device file
+        // (with dynamic codes: pieces are, each band a block of its own -- the same pixels, bytes that depend on the cut)
         std::sort(col.pieces.begin(), col.pieces.end(), [](const std::unique_ptr<PngPiece> &a, const std::unique_ptr<PngPiece> &b) { return a->y0 < b->y0; });
         std::vector<const PngPiece *> order;
         for (auto &p : col.pieces) order.push_back(p.get());
@@ -612,7 +615,9 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
         if (const int rc = maray_hip_ctx_create_refined(dev, &prog, &refine, tex, n_tex, &co, &ctx)) return rc;
     uint8_t *bytes = nullptr;
     size_t n_bytes = 0;
-    const int rc = maray_hip_render_apng(ctx, w, h, P ? rows.data() : nullptr, n_images, n_sub, delay_num, delay_den, n_plays, &bytes, &n_bytes);
+    // the encoder word is ignored but for the flag: dynamic codes for every frame
+    const uint32_t png_codes = opts && (opts->encoder & MARAY_ENCODER_DYNAMIC) ? MARAY_PNG_CODES_DYNAMIC : MARAY_PNG_CODES_FIXED;
+    const int rc = render_apng_codes(ctx, w, h, P ? rows.data() : nullptr, n_images, n_sub, delay_num, delay_den, n_plays, png_codes, &bytes, &n_bytes);
     if (rc) { const std::string msg = maray_last_error(); maray_hip_ctx_free(ctx); return fail_with(rc, msg); }      // (a context that failed is not kept)
     gen_cache_give(*entry, dev, ctx, kept.ctx ? kept.hint_mpixels : co.hint_mpixels);
     std::unique_ptr<uint8_t, void (*)(void *)> own(bytes, maray_free);

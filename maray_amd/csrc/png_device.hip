@@ -18,6 +18,7 @@
 // No device-wide counter, no inline assembly, no scratch memory.  LDS: 4 x 896 bytes per block of maray_png_compress.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "png_device.hpp"
@@ -286,12 +287,251 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_gather(const PngBandArgs a
     if (lane < len - t0) dst[t0 + lane] = src[t0 + lane];
 }
 
+// ---- dynamic-Huffman codes: the same tokens, counted, then written with the band's own code ----------------------------------
+//   maray_png_histogram      maray_png_compress's tokeniser (load, __shfl_up, __ballot, run length) feeding the 286 counts of
+//                            the literal/length alphabet in LDS (ds_add_u32); a capped grid whose wavefronts stride over the
+//                            segments; every block STORES its counts, and
+//   maray_png_histogram_sum  one block adds the blocks' counts up (maray_frame_delta's two launches: no device-wide counter).
+//                            A band's distance count is the sum of its length symbols' counts: every match is at distance 3.
+//   maray_png_compress_dyn   maray_png_compress with the band's code from a table in LDS (reversed code | length << 16, filled
+//                            once per block): a literal pixel is up to 45 bits, a match its length code, the extra bits and
+//                            one zero bit (the only distance code, of length 1); no header, no end-of-block, no sync; the
+//                            segment's length is kept in BITS, so that maray_png_scan yields bit offsets.
+//   maray_png_zero           zeroes the span of the stream the band's bits will take (the total is on the device by then), and
+//   maray_png_gather_bits    one wavefront per segment shifts its slot's bits to their bit offset behind the header's bits (a
+//                            64-bit funnel shift per destination dword): dwords wholly inside the segment are plain stores,
+//                            the first and the last are atomicOr -- short segments share a dword with their neighbours, and
+//                            OR does not care for the order.
+// LDS: 1,152 bytes per block of maray_png_histogram; 1,144 + 4 x 1,456 bytes per block of maray_png_compress_dyn.
+constexpr int STAGE_DW_DYN = PNG_SLOT_MAX_DYN / 4;
+constexpr int HIST_BLOCK = 64 * PNG_HIST_WAVES, HIST_SUM_BLOCK = 320, ZERO_BLOCK = 256, ZERO_MAX_BLOCKS = 2048;
+static_assert(HIST_SUM_BLOCK >= (int)PNG_HIST_STRIDE && PNG_HIST_STRIDE >= PNG_LIT_SYMS, "one lane per count");
+
+// the pixel at p (any alignment) from the aligned dwords that hold its three bytes
+__device__ __forceinline__ uint32_t load_pixel(const unsigned char *p)
+{
+    const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t *q = (const uint32_t *)(p - mis);
+    const uint32_t d0 = q[0], d1 = mis >= 2u ? q[1] : 0u;
+    return __builtin_amdgcn_alignbyte(d1, d0, mis) & 0xFFFFFFu;
+}
+
+// One step of 64 pixels of a segment exactly as maray_png_compress cuts it into tokens.  Returns 0: this lane starts no
+// token; 1: its pixel is three literals; 2: it starts a match of *run pixels.  `last` carries the step's last pixel on.
+__device__ __forceinline__ uint32_t step_token(const unsigned char *src, uint32_t p0, uint32_t npix, uint32_t lane, uint32_t *last,
+                                               uint32_t *pix_out, uint32_t *run)
+{
+    const uint32_t px = p0 + lane;
+    const bool valid = px < npix;
+    const uint32_t pix = valid ? load_pixel(src + (size_t)px * 3) : 0u;
+    uint32_t prev = (uint32_t)__shfl_up((int)pix, 1);
+    if (lane == 0u) prev = *last;
+    const bool eq = valid && px != 0u && pix == prev;
+    const uint64_t m = __ballot(eq);
+    *last = (uint32_t)__shfl((int)pix, 63);
+    *pix_out = pix;
+    *run = 0u;
+    if (valid && !eq) return 1u;
+    if (eq && (lane == 0u || !((m >> (lane - 1u)) & 1ull))) {
+        const uint64_t rest = ~(m >> lane);
+        *run = rest ? (uint32_t)__ffsll((long long)rest) - 1u : 64u;
+        return 2u;
+    }
+    return 0u;
+}
+
+// the length symbol of a match of len bytes (3 .. 258), its number of extra bits and their value (match3's first half)
+__device__ __forceinline__ uint32_t length_symbol(uint32_t len, uint32_t *eb, uint32_t *extra)
+{
+    const uint32_t l = len - 3u;
+    *eb = 0u; *extra = 0u;
+    if (len == 258u) return 285u;
+    if (l < 8u) return 257u + l;
+    const uint32_t e = 29u - (uint32_t)__clz((int)l);
+    *eb = e;
+    *extra = l & ((1u << e) - 1u);
+    return 261u + 4u * e + ((l >> e) & 3u);
+}
+
+__global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram(const PngBandArgs a)
+{
+    __shared__ uint32_t hist[PNG_HIST_STRIDE];
+    for (uint32_t i = threadIdx.x; i < PNG_HIST_STRIDE; i += HIST_BLOCK) hist[i] = 0u;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // (wave-uniform trip counts, no barrier inside; seg + the stride stays below 2^32: n_segs < 2^31)
+    for (uint32_t seg = blockIdx.x * PNG_HIST_WAVES + wave; seg < a.n_segs; seg += gridDim.x * PNG_HIST_WAVES) {
+        const uint32_t row = seg / a.nseg, s = seg - row * a.nseg;
+        const uint32_t npix = seg_pixels(a.w, s);
+        const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
+        if (s == 0u && lane == 0u) atomicAdd(&hist[0], 1u);         // the row's filter byte
+        uint32_t last = 0u;
+        for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
+            uint32_t pix, run;
+            const uint32_t kind = step_token(src, p0, npix, lane, &last, &pix, &run);
+            if (kind == 1u) {
+                atomicAdd(&hist[pix & 255u], 1u);
+                atomicAdd(&hist[(pix >> 8) & 255u], 1u);
+                atomicAdd(&hist[pix >> 16], 1u);
+            } else if (kind == 2u) {
+                uint32_t eb, extra;
+                atomicAdd(&hist[length_symbol(3u * run, &eb, &extra)], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < PNG_HIST_STRIDE; i += HIST_BLOCK) a.hist[(size_t)blockIdx.x * PNG_HIST_STRIDE + i] = hist[i];
+}
+
+// count i of the band = the sum of the blocks' counts i (a band has at most 2^28 bytes: no count overflows)
+__global__ __launch_bounds__(HIST_SUM_BLOCK) void maray_png_histogram_sum(uint32_t *hist, uint32_t n_blocks)
+{
+    const uint32_t i = threadIdx.x;
+    if (i >= PNG_HIST_STRIDE) return;
+    uint32_t sum = 0u;
+    for (uint32_t b = 0; b < n_blocks; b++) sum += hist[(size_t)b * PNG_HIST_STRIDE + i];
+    hist[(size_t)n_blocks * PNG_HIST_STRIDE + i] = sum;
+}
+
+// value (up to 45 bits) at bit `bit` of the staging buffer: up to three dwords
+__device__ __forceinline__ void or_bits64(uint32_t *stage, uint32_t bit, uint64_t value)
+{
+    const uint32_t d = bit >> 5, sh = bit & 31u;
+    const uint64_t v = value << sh;
+    const uint32_t w0 = (uint32_t)v, w1 = (uint32_t)(v >> 32), w2 = sh ? (uint32_t)(value >> (64u - sh)) : 0u;
+    if (w0 && d < (uint32_t)STAGE_DW_DYN) atomicOr(&stage[d], w0);
+    if (w1 && d + 1u < (uint32_t)STAGE_DW_DYN) atomicOr(&stage[d + 1u], w1);
+    if (w2 && d + 2u < (uint32_t)STAGE_DW_DYN) atomicOr(&stage[d + 2u], w2);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn(const PngBandArgs a)
+{
+    __shared__ uint32_t table[PNG_LIT_SYMS];
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW_DYN];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t *stage = stage_all + wave * STAGE_DW_DYN;
+    for (uint32_t i = threadIdx.x; i < PNG_LIT_SYMS; i += PC_BLOCK) table[i] = a.table[i];
+    for (uint32_t i = lane; i < (uint32_t)STAGE_DW_DYN; i += 64u) stage[i] = 0u;
+    __syncthreads();
+    const uint32_t seg = blockIdx.x * PC_WAVES + wave;
+    const bool active = seg < a.n_segs;                     // (wave-uniform; nobody leaves before the second barrier)
+    uint32_t seg_bits = 0u;
+    if (active) {
+        const uint32_t row = seg / a.nseg, s = seg - row * a.nseg;
+        const uint32_t npix = seg_pixels(a.w, s), first = s == 0u ? 1u : 0u;
+        const uint32_t n = 3u * npix + first;
+        const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
+        uint32_t bitpos = 0u;
+        if (first) {                                        // the filter byte 0 as a literal
+            const uint32_t e = table[0];
+            if (lane == 0u) or_bits64(stage, 0u, e & 0xFFFFu);
+            bitpos = e >> 16;
+        }
+        uint32_t sum_a = 0u, sum_b = 0u, last = 0u;
+        for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
+            uint32_t pix, run;
+            const uint32_t kind = step_token(src, p0, npix, lane, &last, &pix, &run);
+            const uint32_t px = p0 + lane;
+            uint64_t tok = 0u;
+            uint32_t nb = 0u;
+            if (kind == 1u) {
+                const uint32_t e0 = table[pix & 255u], e1 = table[(pix >> 8) & 255u], e2 = table[pix >> 16];
+                const uint32_t n0 = e0 >> 16, n1 = e1 >> 16, n2 = e2 >> 16;
+                tok = (uint64_t)(e0 & 0xFFFFu) | ((uint64_t)(e1 & 0xFFFFu) << n0) | ((uint64_t)(e2 & 0xFFFFu) << (n0 + n1));
+                nb = n0 + n1 + n2;
+            } else if (kind == 2u) {
+                uint32_t eb, extra;
+                const uint32_t e = table[length_symbol(3u * run, &eb, &extra)];
+                const uint32_t n0 = e >> 16;
+                tok = (uint64_t)(e & 0xFFFFu) | ((uint64_t)extra << n0);
+                nb = n0 + eb + 1u;                          // and the distance code: one zero bit
+            }
+            if (px < npix) {
+                const uint32_t wgt = n - (first + 3u * px);
+                const uint32_t r = pix & 255u, g = (pix >> 8) & 255u, b = pix >> 16;
+                sum_a += r + g + b;
+                sum_b += wgt * r + (wgt - 1u) * g + (wgt - 2u) * b;
+            }
+            uint32_t inc = nb;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t t = (uint32_t)__shfl_up((int)inc, d);
+                if (lane >= (uint32_t)d) inc += t;
+            }
+            if (nb) or_bits64(stage, bitpos + inc - nb, tok);
+            bitpos += (uint32_t)__shfl((int)inc, 63);
+        }
+        seg_bits = bitpos;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            sum_a += (uint32_t)__shfl_xor((int)sum_a, d);
+            sum_b += (uint32_t)__shfl_xor((int)sum_b, d);
+        }
+        if (lane == 0u) {                                   // the Adler shares: exactly maray_png_compress's
+            const uint32_t row_bytes = 3u * a.w + 1u;
+            const uint32_t after = (a.rows - 1u - row) * row_bytes + (row_bytes - (1u + 3u * (s * PNG_SEG + npix)));
+            const uint32_t ra = sum_a % PNG_ADLER_MOD;
+            a.lens[seg] = seg_bits;
+            a.adler[2 * (size_t)seg] = ra;
+            a.adler[2 * (size_t)seg + 1] = (sum_b % PNG_ADLER_MOD + ra * (after % PNG_ADLER_MOD)) % PNG_ADLER_MOD;
+        }
+    }
+    __syncthreads();
+    if (active) {
+        uint32_t *slot = (uint32_t *)(a.slots + (size_t)seg * a.slot_bytes);
+        const uint32_t ndw = min((seg_bits + 31u) >> 5, min(a.slot_bytes >> 2, (uint32_t)STAGE_DW_DYN));
+        for (uint32_t i = lane; i < ndw; i += 64u) slot[i] = stage[i];
+    }
+}
+
+// bytes of the stream a dynamic band may take: the slots' bytes, the header's and a dword's slack, in whole 16 bytes
+__host__ __device__ inline uint64_t dyn_stream_cap(uint32_t n_segs, uint32_t slot_bytes) { return (uint64_t)n_segs * slot_bytes + 512u; }
+
+__global__ __launch_bounds__(ZERO_BLOCK) void maray_png_zero(const PngBandArgs a)
+{
+    const uint64_t bits = (uint64_t)a.header_bits + a.totals[0];
+    const uint64_t cap16 = dyn_stream_cap(a.n_segs, a.slot_bytes) / 16u;
+    const uint64_t n16 = min(((bits + 7u) / 8u + 15u) / 16u + 1u, cap16);
+    uint4 *dst = (uint4 *)a.stream;
+    for (uint64_t i = (uint64_t)blockIdx.x * ZERO_BLOCK + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * ZERO_BLOCK)
+        dst[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_gather_bits(const PngBandArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t seg = blockIdx.x * PC_WAVES + (threadIdx.x >> 6);
+    if (seg >= a.n_segs) return;
+    const uint32_t G = scan_group(a.n_segs), g = seg / G;
+    uint32_t before = 0;                                    // (a band's bits fit 32 bits)
+    for (uint64_t j = (uint64_t)g * G + lane; j < seg; j += 64) before += a.lens[j];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += (uint32_t)__shfl_xor((int)before, d);
+    const uint32_t nbits = min(a.lens[seg], 8u * a.slot_bytes);
+    const uint64_t at = (uint64_t)a.header_bits + a.offsets[g] + before;      // the segment's first bit in the stream
+    if (!nbits || at + nbits > 8u * (dyn_stream_cap(a.n_segs, a.slot_bytes) - 16u)) return;      // (never: the scan's sums are the slots' bits)
+    const uint32_t sh = (uint32_t)at & 31u;
+    const uint32_t *src = (const uint32_t *)(a.slots + (size_t)seg * a.slot_bytes);
+    uint32_t *dst = (uint32_t *)a.stream + (at >> 5);
+    const uint32_t nsrc = (nbits + 31u) >> 5, nd = (sh + nbits + 31u) >> 5;
+    for (uint32_t k = lane; k < nd; k += 64u) {
+        // destination dword k holds the source's bits 32 k - sh .. 32 k - sh + 31: the top of dword k - 1, the bottom of dword k
+        const uint32_t lo = k >= 1u && k - 1u < nsrc ? src[k - 1u] : 0u, hi = k < nsrc ? src[k] : 0u;
+        const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> (32u - sh));
+        if (k == 0u || k == nd - 1u) { if (v) atomicOr(&dst[k], v); }
+        else dst[k] = v;
+    }
+}
+
 void check_band(const PngBandArgs &a)
 {
+    const bool dyn = a.codes == MARAY_PNG_CODES_DYNAMIC;
     if (!a.src || !a.slots || !a.lens || !a.adler || !a.offsets || !a.stream || !a.totals || !a.w || !a.rows ||
-        a.nseg != png_row_segments(a.w) || a.slot_bytes != png_slot_bytes(a.w) || a.slot_bytes > PNG_SLOT_MAX ||
+        (a.codes != MARAY_PNG_CODES_FIXED && !dyn) || (dyn && (!a.hist || a.header_bits > PNG_DYN_HEADER_MAX_BITS || ((uintptr_t)a.stream & 15))) ||
+        a.nseg != png_row_segments(a.w) || a.slot_bytes != (dyn ? png_slot_bytes_dyn(a.w) : png_slot_bytes(a.w)) ||
+        a.slot_bytes > (dyn ? PNG_SLOT_MAX_DYN : PNG_SLOT_MAX) ||
         (uint64_t)a.rows * a.nseg != a.n_segs || ((uintptr_t)a.slots & 15) ||
-        (uint64_t)a.rows * (3ull * a.w + 1ull) > (1ull << 30))
+        (uint64_t)a.rows * (3ull * a.w + 1ull) > (dyn ? PNG_DYN_BAND_MAX_BYTES : 1ull << 30))
         throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad band arguments"};
 }
 
@@ -301,7 +541,15 @@ void png_band_compress(const PngBandArgs &a, hipStream_t st)
 {
     check_band(a);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(maray_png_compress, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    if (a.codes == MARAY_PNG_CODES_DYNAMIC && !a.table) {
+        const uint32_t blocks = png_hist_blocks(a.n_segs);
+        hipLaunchKernelGGL(maray_png_histogram, dim3(blocks), dim3(HIST_BLOCK), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(maray_png_histogram_sum, dim3(1), dim3(HIST_SUM_BLOCK), 0, st, a.hist, blocks);
+    } else if (a.codes == MARAY_PNG_CODES_DYNAMIC)
+        hipLaunchKernelGGL(maray_png_compress_dyn, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    else
+        hipLaunchKernelGGL(maray_png_compress, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
 }
 
@@ -317,7 +565,15 @@ void png_band_gather(const PngBandArgs &a, hipStream_t st)
 {
     check_band(a);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(maray_png_gather, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    if (a.codes == MARAY_PNG_CODES_DYNAMIC) {
+        if (!a.table) throw Error{MARAY_E_INTERNAL, "device PNG encoder: a dynamic band is gathered after its code is set"};
+        const uint64_t n16 = dyn_stream_cap(a.n_segs, a.slot_bytes) / 16;
+        const uint32_t zb = (uint32_t)std::min<uint64_t>((n16 + ZERO_BLOCK - 1) / ZERO_BLOCK, ZERO_MAX_BLOCKS);
+        hipLaunchKernelGGL(maray_png_zero, dim3(zb), dim3(ZERO_BLOCK), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(maray_png_gather_bits, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    } else
+        hipLaunchKernelGGL(maray_png_gather, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
 }
 

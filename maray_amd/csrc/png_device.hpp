@@ -28,6 +28,26 @@ inline uint32_t png_slot_bytes(uint32_t w)
 constexpr uint32_t PNG_SLOT_MAX = ((9 * (3 * PNG_SEG + 1) + 7) / 8 + 16 + 15) / 16 * 16;
 inline uint32_t png_row_segments(uint32_t w) { return (w + PNG_SEG - 1) / PNG_SEG; }
 
+// ---- dynamic-Huffman codes (MARAY_PNG_CODES_DYNAMIC): the same tokens, one dynamic block per band --------------------------
+// A segment of n filtered bytes is at most 15 n bits: ceil(15 n / 8) bytes, rounded up to 16 like the fixed coder's slot.
+inline uint32_t png_slot_bytes_dyn(uint32_t w)
+{
+    const uint32_t n = 3 * (w < PNG_SEG ? w : PNG_SEG) + 1;
+    return ((15 * n + 7) / 8 + 15) / 16 * 16;
+}
+constexpr uint32_t PNG_SLOT_MAX_DYN = ((15 * (3 * PNG_SEG + 1) + 7) / 8 + 15) / 16 * 16;
+constexpr uint64_t PNG_DYN_BAND_MAX_BYTES = (uint64_t)1 << 28;    // filtered bytes of a dynamic band: every bit offset fits 32 bits
+constexpr uint32_t PNG_LIT_SYMS = 286, PNG_DIST_SYMS = 30;
+constexpr uint32_t PNG_DYN_HEADER_MAX_BITS = 17 + 19 * 3 + (PNG_LIT_SYMS + PNG_DIST_SYMS) * 7;    // no run symbols: 2286
+// maray_png_histogram: blocks of PNG_HIST_WAVES wavefronts, one segment per wavefront and pass; the grid is capped at
+// PNG_HIST_MAX_BLOCKS and strides over the band's segments.  Every block stores PNG_HIST_STRIDE words of partial counts.
+constexpr uint32_t PNG_HIST_WAVES = 4, PNG_HIST_MAX_BLOCKS = 512, PNG_HIST_STRIDE = 288;
+inline uint32_t png_hist_blocks(uint32_t n_segs)
+{
+    const uint32_t b = (n_segs + PNG_HIST_WAVES - 1) / PNG_HIST_WAVES;
+    return b < 1 ? 1 : b > PNG_HIST_MAX_BLOCKS ? PNG_HIST_MAX_BLOCKS : b;
+}
+
 // What a run of segments contributes to the Adler-32, as an element of a monoid: n bytes with A = sum b_i and
 // B = sum (n - i) b_i, all three modulo 65521.  (s1, s2) after the run = (s1 + A, s2 + n s1 + B).
 struct AdlerPart {
@@ -53,10 +73,26 @@ struct PngBandArgs {
     uint64_t *totals;               // [0] = bytes of the stream, [1] = n | a << 32, [2] = b: the band's AdlerPart
     uint32_t w, rows, nseg, slot_bytes;
     uint32_t n_segs;                // rows * nseg
+    // MARAY_PNG_CODES_DYNAMIC (else all zero): lens and offsets count BITS, totals[0] is the band's bits, slots are
+    // png_slot_bytes_dyn wide and the stream starts with header_bits zero bits for the host's block header
+    uint32_t codes;                 // MARAY_PNG_CODES_*
+    uint32_t header_bits;           // bits of the block header in front of the first token; 0 while the band is being counted
+    uint32_t *hist;                 // png_hist_blocks(n_segs) x PNG_HIST_STRIDE partial counts, then PNG_HIST_STRIDE words: their sums
+    const uint32_t *table;          // PNG_LIT_SYMS words: reversed code | length << 16; null while the band is being counted
 };
-void png_band_compress(const PngBandArgs &a, hipStream_t st);       // maray_png_compress
-void png_band_scan(const PngBandArgs &a, hipStream_t st);           // maray_png_scan
-void png_band_gather(const PngBandArgs &a, hipStream_t st);         // maray_png_gather
+// The launchers dispatch on a.codes.  FIXED: maray_png_compress, maray_png_scan, maray_png_gather.  DYNAMIC: compress is
+// maray_png_histogram + maray_png_histogram_sum while a.table is null and maray_png_compress_dyn once it is set; scan is
+// maray_png_scan; gather is maray_png_zero + maray_png_gather_bits.
+void png_band_compress(const PngBandArgs &a, hipStream_t st);
+void png_band_scan(const PngBandArgs &a, hipStream_t st);
+void png_band_gather(const PngBandArgs &a, hipStream_t st);
+
+// The host's part of a dynamic band (png_device.cpp; maray_png_dynamic_codes is the public form of the first).
+// table[s] = the canonical code of literal/length symbol s, bit-reversed for the LSB-first stream, | length << 16
+void png_dynamic_table(const uint8_t lit_lens[PNG_LIT_SYMS], uint32_t table[PNG_LIT_SYMS]);
+// z holds, from byte `base` on, `bits` bits of a band (header and tokens) and nothing behind them: appends symbol 256
+// (table[256]) and the empty stored block that ends on a byte boundary (three zero bits, zeros to the byte, 00 00 FF FF)
+void png_dynamic_close(std::vector<uint8_t> &z, uint64_t bits, uint32_t code256, size_t base = 0);
 
 // The compressed segments of rows [y0, y1) of an image, on the host, with their Adler part
 struct PngPiece {
@@ -82,13 +118,15 @@ struct PngEncoder {
     explicit PngEncoder(int dev);
     ~PngEncoder();
     PngEncoder(const PngEncoder &) = delete;
-    uint32_t band_rows(uint32_t w) const;
+    uint32_t *h_counts = nullptr;                                // pinned host: PNG_HIST_STRIDE counts down, PNG_LIT_SYMS table words up
+    uint32_t band_rows(uint32_t w, uint32_t codes = MARAY_PNG_CODES_FIXED) const;
     unsigned char *band_buffer(size_t bytes);                    // `raster`, grown to hold `bytes` (the animation writer's crops)
     // rows x w pixels at d_rgb8 (device memory, any alignment), enqueued on st and waited for; appends to `out`
-    void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out);
+    void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out, uint32_t codes = MARAY_PNG_CODES_FIXED);
     // rows [y0, y1) band by band: render(b0, b1, d8, st) enqueues the rows' RGB8 into d8 on st
     void encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,
-                         const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out);
+                         const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out,
+                         uint32_t codes = MARAY_PNG_CODES_FIXED);
 };
 
 // An encoder of `device`: one an earlier call left, or a new one (MARAY_PNG_BAND_ROWS is read here: a kept encoder made
@@ -116,6 +154,9 @@ std::vector<uint8_t> png_close_stream(uint32_t h_end, const std::vector<const Pn
 std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces);
 // Average ms of compress + scan + gather over the caller's w x rows raster in device memory, as one band (measurements);
 // *stream_bytes = the bytes of the gathered stream.
-float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes);
+// With DYNAMIC codes the six kernels of a band whose code is fitted once, before the timed loop (the host's round trip is
+// not a kernel); *stream_bytes = the bytes of the band's piece.
+float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes,
+                       uint32_t codes = MARAY_PNG_CODES_FIXED);
 
 }   // namespace maray
