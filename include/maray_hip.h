@@ -432,6 +432,21 @@ int maray_jit_build_refine(const maray_program *prog, const maray_refine *refine
  * in a rectangle's words, -1 for a guard derived from other guards' bits (at most `cap` entries are written); *n_words =
  * 64-bit words per rectangle (0: the guards are not kept as bits), *gw x *gh = the rectangle in pixels x rows.  Needs no GPU. */
 int maray_jit_guard_layout(const maray_program *prog, int32_t *pos, uint32_t cap, uint32_t *n_guards, uint32_t *n_words, uint32_t *gw, uint32_t *gh);
+/* The census of guard bits (MARAY_BACKEND_JIT, plain contexts that reuse their ROW outputs).  The first launch that finds a
+ * set of ROW outputs filled runs maray_jit_census over the set's geometry -- the PIXEL kernel's own text without its stores,
+ * recording per rectangle which guarded shapes are != 0 on some pixel -- and maray_jit_census_apply, which writes the set's
+ * words without the eligible guard bits of the others into a second table of the set, which that launch and the later ones of
+ * the set read (the ROW pass's words stay what they are); then the launch order, then the pixels.  Once per filling of a set;
+ * a launch of more than 65,534 rows takes none.  MARAY_JIT_GUARD_CENSUS=0 in the environment when the context is created: no
+ * such launch (rasters are identical either way; not part of a code key).
+ * maray_hip_census_count: how many the context has enqueued (0 for an interpreter's context).
+ * maray_jit_census_eligible: per guard word of a rectangle (see maray_jit_guard_layout), the bits a census may clear: bits of
+ * leaves of a guarded reduction of the PIXEL section that gate nothing else, read no parameter the ROW section does not read
+ * and hold no Sin that may send its tile to the interpreter; at most `cap` words are written, *n_words = words per rectangle.
+ * maray_jit_source_census: the kernels' source ("" when no bit is eligible; free with maray_free).  Neither needs a GPU. */
+int maray_hip_census_count(const maray_ctx *c, uint64_t *census_launches);
+int maray_jit_census_eligible(const maray_program *prog, uint64_t *mask, uint32_t cap, uint32_t *n_words);
+int maray_jit_source_census(const maray_program *prog, char **src_out);
 /* How many maray_jit_refine passes the context has enqueued since it was created (0 for an interpreter's context). */
 int maray_hip_refine_count(const maray_ctx *c, uint64_t *refine_passes);
 /* Test access: the guard words of the set of ROW outputs the most recent launch used, copied to the host after everything
@@ -439,6 +454,9 @@ int maray_hip_refine_count(const maray_ctx *c, uint64_t *refine_passes);
  * rectangles of a group of rows adjacent), *words_per_rect = words per rectangle; at most `cap` words are copied.
  * MARAY_E_ARG for a context without guard words or before its first launch. */
 int maray_hip_debug_guard_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
+/* The same for the words the most recent launch READ: those of maray_hip_debug_guard_words, which the ROW pass and the second
+ * bounds wrote, until the set has been through its census; from then on what maray_jit_census_apply left of them. */
+int maray_hip_debug_census_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

@@ -144,7 +144,11 @@ def lib():
         'maray_jit_build_refine': (C.c_int, [C.POINTER(Program), C.POINTER(Refine), C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_jit_guard_layout': (C.c_int, [C.POINTER(Program), vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         'maray_hip_refine_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_hip_census_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_jit_census_eligible': (C.c_int, [C.POINTER(Program), vp, u32, C.POINTER(u32)]),
+        'maray_jit_source_census': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
         'maray_hip_debug_guard_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
+        'maray_hip_debug_census_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
         'maray_hip_ctx_free': (None, [vp]),
         'maray_hip_render_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
         'maray_hip_render_tiles': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, TILE_FN, vp]),
@@ -442,6 +446,24 @@ class Tape:
         _check(lib().maray_jit_guard_layout(C.byref(self.program), pos.ctypes.data, n.value, C.byref(n), C.byref(nw), C.byref(gw), C.byref(gh)))
         return pos, nw.value, gw.value, gh.value
 
+    def census_eligible(self):
+        """maray_jit_census_eligible: per guard word of a rectangle (guard_layout), the bits a census may clear, as uint64."""
+        n = C.c_uint32()
+        _check(lib().maray_jit_census_eligible(C.byref(self.program), None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint64)
+        _check(lib().maray_jit_census_eligible(C.byref(self.program), out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    @property
+    def jit_source_census(self):
+        """Source of maray_jit_census and maray_jit_census_apply; '' when no guard bit is eligible (maray_jit_source_census)."""
+        p = C.c_void_p()
+        _check(lib().maray_jit_source_census(C.byref(self.program), C.byref(p)))
+        try:
+            return C.string_at(p).decode()
+        finally:
+            lib().maray_free(p)
+
     def refine_arrays(self):
         """(consts, ops, n_slots) of the REFINE section as numpy copies; None when the program has none."""
         r = self.refine
@@ -640,6 +662,13 @@ class Context:
         _check(lib().maray_hip_refine_count(self._h, C.byref(n)))
         return n.value
 
+    @property
+    def census_count(self):
+        """maray_jit_census launches this context has enqueued so far (maray_hip_census_count)."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_census_count(self._h, C.byref(n)))
+        return n.value
+
     def debug_guard_words(self):
         """Test access (maray_hip_debug_guard_words): the guard words of the set the last launch used, (rectangles, words per
         rectangle) uint64, the rectangles of a group of rows adjacent."""
@@ -647,6 +676,15 @@ class Context:
         _check(lib().maray_hip_debug_guard_words(self._h, None, 0, C.byref(n), C.byref(per)))
         out = np.zeros(n.value, np.uint64)
         _check(lib().maray_hip_debug_guard_words(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(per)))
+        return out.reshape(-1, per.value)
+
+    def debug_census_words(self):
+        """Test access (maray_hip_debug_census_words): the guard words the last launch read, shaped like debug_guard_words():
+        those, until the set has been through its census; then what the census left of them."""
+        n, per = C.c_size_t(), C.c_uint32()
+        _check(lib().maray_hip_debug_census_words(self._h, None, 0, C.byref(n), C.byref(per)))
+        out = np.zeros(n.value, np.uint64)
+        _check(lib().maray_hip_debug_census_words(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(per)))
         return out.reshape(-1, per.value)
 
     @property

@@ -1303,11 +1303,54 @@ int maray_hip_refine_count(const maray_ctx *c, uint64_t *refine_passes)
     return guard([&] { REQUIRE(c && c->backend && refine_passes, "null argument"); *refine_passes = c->backend->refine_count(); });
 }
 
+int maray_hip_census_count(const maray_ctx *c, uint64_t *census_launches)
+{
+    return guard([&] { REQUIRE(c && c->backend && census_launches, "null argument"); *census_launches = c->backend->census_count(); });
+}
+
+int maray_jit_census_eligible(const maray_program *prog, uint64_t *mask, uint32_t cap, uint32_t *n_words)
+{
+    return guard([&] {
+        REQUIRE(prog && n_words && (mask || !cap), "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        std::vector<uint64_t> el;
+        (void)jit_source_census(loaded, &el);
+        std::vector<int32_t> pos;
+        uint32_t nw = 0, gw = 0, gh = 0;
+        jit_guard_layout(loaded, pos, &nw, &gw, &gh);
+        el.resize(nw, 0);                               // no kernel: no bit is eligible
+        *n_words = (uint32_t)el.size();
+        for (uint32_t j = 0; j < el.size() && j < cap; j++) mask[j] = el[j];
+    });
+}
+
+int maray_jit_source_census(const maray_program *prog, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        const std::string s = jit_source_census(loaded);
+        *src_out = (char *)malloc(s.size() + 1);
+        REQUIRE(*src_out, "out of memory");
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
 int maray_hip_debug_guard_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect)
 {
     return guard([&] {
         REQUIRE(c && c->backend && n_words && words_per_rect && (words || !cap), "null argument");
         *n_words = c->backend->debug_guard_words(words, cap, words_per_rect);
+    });
+}
+
+int maray_hip_debug_census_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend && n_words && words_per_rect && (words || !cap), "null argument");
+        *n_words = c->backend->debug_census_words(words, cap, words_per_rect);
     });
 }
 

@@ -41,7 +41,10 @@ struct Backend {
     // maray_jit_refine passes enqueued so far, and (test access) the guard words of the set the last launch used, after a
     // wait for the context's work: returns the words in the set, copies at most `cap` (maray_hip_debug_guard_words)
     virtual uint64_t refine_count() const { return 0; }
+    virtual uint64_t census_count() const { return 0; }     // maray_jit_census launches enqueued so far (maray_hip_census_count)
     virtual size_t debug_guard_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
+    // ... and the words the last launch read: those with the bits its set's census cleared, where it has been through one (maray_hip_debug_census_words)
+    virtual size_t debug_census_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
@@ -89,6 +92,13 @@ std::string jit_source_refine(const maray_program &prog, const maray_refine &ref
 // its code object (null when the source is empty): built once, kept like jit_code_samples', under a key of its own made of its text
 struct JitRefineCode { std::vector<char> code; uint32_t n_jobs = 0; };
 std::shared_ptr<const JitRefineCode> jit_code_refine(const maray_program &prog, const maray_refine &refine);
+// maray_jit_census + maray_jit_census_apply: the census form of the PIXEL kernel (which guarded leaves are != 0 on some pixel of
+// a rectangle) and the kernel that clears the guard bits of the others; "" when no bit is eligible.  *eligible: per guard word, the
+// bits a census decides (maray_jit_census_eligible)
+std::string jit_source_census(const maray_program &prog, std::vector<uint64_t> *eligible = nullptr, int min_waves = 0);
+// its code object (null when the source is empty): a module and a cache entry of its own, like jit_code_refine's
+struct JitCensusCode { std::vector<char> code; std::vector<uint64_t> eligible; };
+std::shared_ptr<const JitCensusCode> jit_code_census(const maray_program &prog);
 std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
 std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error

@@ -194,7 +194,9 @@ struct FilterBackend final : Backend {
     const char *kernel_name() const override { return name.c_str(); }
     void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { inner->launch_counts(row_passes, order_kernels); }
     uint64_t refine_count() const override { return inner->refine_count(); }
+    uint64_t census_count() const override { return inner->census_count(); }
     size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_guard_words(words, cap, per_rect); }
+    size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_census_words(words, cap, per_rect); }
 };
 
 }   // namespace

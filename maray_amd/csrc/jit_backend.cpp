@@ -46,8 +46,10 @@ struct RowTables {
     double *yvals = nullptr; size_t yvals_cap = 0;
     unsigned long long *gbits = nullptr; size_t gbits_cap = 0;
     unsigned *order = nullptr; size_t order_cap = 0;          // the launch order computed from gbits (maray_jit_order)
+    unsigned char *hits = nullptr; size_t hits_cap = 0;       // the census's flags, 64 per guard word (maray_jit_census)
+    unsigned long long *cbits = nullptr; size_t cbits_cap = 0;      // gbits with the bits the census cleared: what the launches of a set read once it is through (maray_jit_census_apply)
     void release() {
-        (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order);
+        (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order); (void)hipFree(hits); (void)hipFree(cbits);
         *this = RowTables{};
     }
 };
@@ -64,6 +66,15 @@ struct JitBackend final : Backend {
     hipFunction_t f_refine = nullptr;
     bool refine_on = true;              // MARAY_JIT_GUARD_REFINE=0: no such launch (read once, when the context is created)
     uint64_t n_refine_passes = 0;
+    // maray_jit_census + maray_jit_census_apply (jit_source_census): once per kept filling of a set, in front of its launch order
+    std::shared_ptr<const JitCensusCode> code_census;
+    hipModule_t mod_census = nullptr;
+    hipFunction_t f_census = nullptr, f_census_apply = nullptr;
+    bool census_on = true;              // MARAY_JIT_GUARD_CENSUS=0: no such launch (read once, when the context is created)
+    uint64_t n_census = 0;
+    // the census module's parameter table is not among d_par: it is written by the launch that takes a census, not by every
+    // frame of an animation (a copy per module and frame is what a host-bound shutter waits for)
+    hipDeviceptr_t d_par_census = nullptr;
     uint32_t ss = 1;                    // samples per output pixel and axis: > 1 launches maray_jit_pixels_ss (launch_ss)
     std::shared_ptr<const std::vector<char>> code_ss;
     hipModule_t mod_ss = nullptr;
@@ -105,6 +116,7 @@ struct JitBackend final : Backend {
         if (mod) (void)hipModuleUnload(mod);
         if (mod_rows) (void)hipModuleUnload(mod_rows);
         if (mod_refine) (void)hipModuleUnload(mod_refine);
+        if (mod_census) (void)hipModuleUnload(mod_census);
         if (mod_ss) (void)hipModuleUnload(mod_ss);
         (void)hipFree(d_flags);
         (void)hipFree(d_tex);
@@ -159,9 +171,16 @@ struct JitBackend final : Backend {
         std::future<std::shared_ptr<const JitRefineCode>> refine_code;
         if (refine_on && refine && refine->n_ops && prog.n_row_ops)
             refine_code = std::async(std::launch::async, [&prog, refine] { return jit_code_refine(prog, *refine); });
+        // ... and the fourth: a plain context that reuses its sets (a supersampling context takes no census)
+        if (const char *e_ = getenv("MARAY_JIT_GUARD_CENSUS")) if (e_[0] == '0') census_on = false;
+        std::future<std::shared_ptr<const JitCensusCode>> census_code;
+        if (census_on && reuse.enabled && ss == 1 && prog.n_row_ops)
+            census_code = std::async(std::launch::async, [&prog] { return jit_code_census(prog); });
         try { code = jit_code_for(prog); }               // built by the first context of the process, or read from the cache
-        catch (...) { if (refine_code.valid()) refine_code.wait(); throw; }
-        if (refine_code.valid()) code_refine = refine_code.get();
+        catch (...) { if (refine_code.valid()) refine_code.wait(); if (census_code.valid()) census_code.wait(); throw; }
+        try { if (refine_code.valid()) code_refine = refine_code.get(); }
+        catch (...) { if (census_code.valid()) census_code.wait(); throw; }
+        if (census_code.valid()) code_census = census_code.get();
         lap("code objects");
         HIP_TRY(hipModuleLoadData(&mod, code->pix.data()));
         HIP_TRY(hipModuleGetFunction(&f_pix, mod, "maray_jit_pixels"));
@@ -189,17 +208,23 @@ struct JitBackend final : Backend {
                 HIP_TRY(hipModuleGetFunction(&f_refine, mod_refine, "maray_jit_refine"));
                 lap("load REFINE module");
             }
+            if (code_census && n_gwords && code_census->eligible.size() == n_gwords) {
+                HIP_TRY(hipModuleLoadData(&mod_census, code_census->code.data()));
+                HIP_TRY(hipModuleGetFunction(&f_census, mod_census, "maray_jit_census"));
+                HIP_TRY(hipModuleGetFunction(&f_census_apply, mod_census, "maray_jit_census_apply"));
+                lap("load CENSUS module");
+            }
         }
         if (prog.n_params) {
             param_values.assign(prog.n_params, NAN);
-            for (hipModule_t m : {mod, mod_rows, mod_ss, mod_refine}) {
+            for (hipModule_t m : {mod, mod_rows, mod_ss, mod_refine, mod_census}) {
                 if (!m) continue;
                 hipDeviceptr_t p = nullptr;
                 size_t bytes = 0;
                 HIP_TRY(hipModuleGetGlobal(&p, &bytes, m, "mr_par_tab"));
                 if (bytes != (size_t)prog.n_params * sizeof(double)) throw Error{MARAY_E_INTERNAL, "parameter table of a module has another size than the program"};
                 HIP_TRY(hipMemcpyHtoD(p, param_values.data(), bytes));          // NaN until set
-                d_par.push_back(p);
+                if (m == mod_census) d_par_census = p; else d_par.push_back(p);
             }
             ring.init(prog.n_params);
             P.param_ranges = nullptr;
@@ -271,7 +296,7 @@ struct JitBackend final : Backend {
     // Called after the stream hand-over and send_params: every launch of the context is ordered behind the previous one,
     // whichever streams they are on, so a set filled on one stream is complete for a reader on another.
     int row_set(uint32_t w, uint32_t rows_total, unsigned y0, unsigned blk_rows, unsigned blk_stride, unsigned yrows, uint32_t n_groups,
-                bool want_order, hipStream_t st, bool rows_pass, bool *matched) {
+                bool want_order, hipStream_t st, bool rows_pass, bool *matched, bool want_census = false) {
         RowKey key;
         key.geometry(w, rows_total, y0, blk_rows, blk_stride, yrows);
         key.params(param_values.data(), (uint32_t)param_values.size(), reuse.enabled ? row_params : ~0ull);
@@ -290,10 +315,12 @@ struct JitBackend final : Backend {
         const size_t yv_n = (size_t)rows_total * std::max<uint32_t>(P.n_yvals, 1);
         const size_t gb_n = (size_t)n_groups * ((w + 255) / 256) * guard_sub * std::max<uint32_t>(n_gwords, 1);
         const size_t od_n = want_order ? rows_total : 0;
+        const size_t hb_n = want_census ? gb_n * 64 : 0;           // a flag per guard bit
+        const size_t cb_n = want_census ? gb_n : 0;                // ... and the words the census leaves
         const bool refill = s >= 0;             // reuse is off: the scratch holds this key and is written again
         if (!refill)
-            s = reuse.place(key, yv_n * sizeof(double) + gb_n * sizeof(unsigned long long) + od_n * sizeof(unsigned),
-                            [&](int v) { return tabs[v].yvals_cap >= yv_n && tabs[v].gbits_cap >= gb_n && tabs[v].order_cap >= od_n; },
+            s = reuse.place(key, yv_n * sizeof(double) + gb_n * sizeof(unsigned long long) + od_n * sizeof(unsigned) + hb_n + cb_n * sizeof(unsigned long long),
+                            [&](int v) { return tabs[v].yvals_cap >= yv_n && tabs[v].gbits_cap >= gb_n && tabs[v].order_cap >= od_n && tabs[v].hits_cap >= hb_n && tabs[v].cbits_cap >= cb_n; },
                             [&](int v) { tabs[v].release(); });      // (hipFree waits for the device: at a promotion or an eviction only)
         RowTables &t = tabs[s];
         ensure(t.yvals, t.yvals_cap, yv_n);
@@ -302,7 +329,7 @@ struct JitBackend final : Backend {
         // A kept set gets its order table with the other two, whether or not an order is ever computed in it: fits() asks for
         // all three, so a set whose keys rotate away before their second launch can still be taken over as it is (the
         // scratch's grows in launch(), when an order is due)
-        if (s) ensure(t.order, t.order_cap, od_n);
+        if (s) { ensure(t.order, t.order_cap, od_n); ensure(t.hits, t.hits_cap, hb_n); ensure(t.cbits, t.cbits_cap, cb_n); }      // (the census's flags likewise)
         // bits past the last guard belong to no job and are never written: zero them once per table (the pixel kernel tests whole words)
         if (t.gbits_cap != had) HIP_TRY(hipMemsetAsync(t.gbits, 0, t.gbits_cap * sizeof(unsigned long long), st));
         if (P.n_row_ops) {
@@ -395,29 +422,12 @@ struct JitBackend final : Backend {
         // more than one grid takes none
         const bool want_order = f_order && n_gwords && rows_total <= rows_per_grid && n_groups <= 4096 && n_groups > 1;
         bool matched;
-        const int set = row_set(w, rows_total, y0, blk_rows, blk_stride, yrows, n_groups, want_order, st, rows_pass, &matched);
+        // the census is a launch of the pixel kernel's shape over the set's geometry: a launch of more than one grid takes none
+        const bool want_census = f_census && rows_total <= rows_per_grid;
+        const int set = row_set(w, rows_total, y0, blk_rows, blk_stride, yrows, n_groups, want_order, st, rows_pass, &matched, want_census);
         RowTables &T = tabs[set];
         if (!T.yvals || !T.gbits) throw Error{MARAY_E_INTERNAL, "launch without a ROW pass before any ROW pass"};
         unsigned n_yvals = P.n_yvals;
-        // launch order of the PIXEL kernel (maray_jit_order): once per key, from the set's guard bits, whether this launch
-        // ran the ROW kernel or found them there; used by every later launch of that key (time_rows too)
-        const unsigned *row_order = nullptr;
-        if (want_order && matched) {
-            RowReuse::Set &S = reuse.sets[set];
-            // The order costs one 43 us kernel per key and saves ~2.6 us per launch: it is computed by the first launch that
-            // finds the set holding its key (an animation, a benchmark loop: the second launch; a key that came back into
-            // a kept set: the launch after the one that filled it), never for the tiles of a one-shot render, each of
-            // which is a geometry of its own, nor for keys that rotate through more sets than a context keeps.
-            if (!S.order && S.launches >= 2) {
-                ensure(T.order, T.order_cap, (size_t)rows_total);
-                unsigned rr = rows_total, n_tx_ = (w + 255) / 256 * guard_sub;
-                void *oargs[] = {&T.gbits, &T.order, &rr, &n_tx_, &yrows};
-                HIP_TRY(hipModuleLaunchKernel(f_order, 1, 1, 1, 256, 1, 1, n_groups * 4, st, oargs, nullptr));
-                n_order_kernels++;
-                S.order = true;             // only now: the kernel that computes it is enqueued
-            }
-            if (S.order) row_order = T.order;
-        }
         const unsigned n_tx = (w + 255) / 256;
         const uint64_t n_tiles = (uint64_t)n_tx * rows_total;
         // Tiles per wavefront.  Every tile of a program without guards costs the same: nothing to balance, and a strip as long as
@@ -439,6 +449,60 @@ struct JitBackend final : Backend {
         tiles = std::max(1u, std::min(tiles, n_tx));
         const unsigned gx = (n_tx + 4 * tiles - 1) / (4 * tiles);
         if (n_tiles > 0xFFFFFFFFull) throw Error{MARAY_E_ARG, "too many tiles in one launch; render fewer rows per call"};
+        // The census (maray_jit_census, jit_source_census): the pixel launch without its stores, over exactly the set's geometry,
+        // records which leaves are != 0 on some pixel of each rectangle; maray_jit_census_apply writes the set's guard words without the
+        // eligible bits of the others into the set's second table, cbits, which this launch and the later ones read.  Once per filling of a set, on the first launch that finds it filled (row_reuse.hpp,
+        // census_due) -- its inputs are the program, the geometry and the ROW-read parameters, a set's key -- and in front of the
+        // launch order, which counts the bits that are left.  One stream: flags zeroed, census, apply, order, pixels.
+        if (want_census && reuse.census_due(set, matched)) {
+            const size_t words = set_gbits_n[set];
+            if (words && words <= 0xFFFFFFFFull / 64) {
+                ensure(T.hits, T.hits_cap, words * 64);
+                ensure(T.cbits, T.cbits_cap, words);
+                HIP_TRY(hipMemsetAsync(T.hits, 0, words * 64, st));
+                if (d_par_census) {             // the values this launch renders with (send_params has run)
+                    double *slot = ring.take();
+                    const size_t bytes = param_values.size() * sizeof(double);
+                    memcpy(slot, param_values.data(), bytes);
+                    HIP_TRY(hipMemcpyHtoDAsync(d_par_census, slot, bytes, st));
+                    ring.sent(st);
+                }
+                unsigned char *no8 = nullptr; double *no64 = nullptr; unsigned *fl = nullptr; const unsigned *no_order = nullptr;
+                const double *yv = T.yvals;
+                const unsigned long long *gb = T.gbits;
+                unsigned ww = w, yy0 = y0, tile_base = 0, row_base = 0, ntx = n_tx, rows = rows_total, rpw = 1;
+                unsigned char *hits = T.hits;
+                void *cargs[] = {&no8, &no64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &no_order, &rows, &rpw, &hits};
+                HIP_TRY(hipModuleLaunchKernel(f_census, gx, rows_total, 1, 256, 1, 1, 0, st, cargs, nullptr));
+                unsigned long long *cbw = T.cbits;
+                unsigned nw = (unsigned)words;
+                void *aargs[] = {&gb, &hits, &cbw, &nw};
+                HIP_TRY(hipModuleLaunchKernel(f_census_apply, (nw + 255u) / 256u, 1, 1, 256, 1, 1, 0, st, aargs, nullptr));
+                n_census++;
+                reuse.sets[set].census = true;          // only now: the kernels are enqueued
+            }
+        }
+        // launch order of the PIXEL kernel (maray_jit_order): once per key, from the set's guard bits, whether this launch
+        // ran the ROW kernel or found them there; used by every later launch of that key (time_rows too)
+        // the guard words this launch and its order read: the census's where the set has been through one
+        const unsigned long long *gwords = reuse.sets[set].census ? T.cbits : T.gbits;
+        const unsigned *row_order = nullptr;
+        if (want_order && matched) {
+            RowReuse::Set &S = reuse.sets[set];
+            // The order costs one 43 us kernel per key and saves ~2.6 us per launch: it is computed by the first launch that
+            // finds the set holding its key (an animation, a benchmark loop: the second launch; a key that came back into
+            // a kept set: the launch after the one that filled it), never for the tiles of a one-shot render, each of
+            // which is a geometry of its own, nor for keys that rotate through more sets than a context keeps.
+            if (!S.order && S.launches >= 2) {
+                ensure(T.order, T.order_cap, (size_t)rows_total);
+                unsigned rr = rows_total, n_tx_ = (w + 255) / 256 * guard_sub;
+                void *oargs[] = {&gwords, &T.order, &rr, &n_tx_, &yrows};
+                HIP_TRY(hipModuleLaunchKernel(f_order, 1, 1, 1, 256, 1, 1, n_groups * 4, st, oargs, nullptr));
+                n_order_kernels++;
+                S.order = true;             // only now: the kernel that computes it is enqueued
+            }
+            if (S.order) row_order = T.order;
+        }
         if (has_sin) {
             ensure(d_flags, flags_cap, (size_t)n_tiles + 1);                // work list {count, tile, ...} of deferred tiles
             HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(unsigned), st));
@@ -450,7 +514,7 @@ struct JitBackend final : Backend {
             const double *yv = T.yvals + (size_t)r0 * n_yvals;
             unsigned *fl = d_flags;
             unsigned ww = w, yy0 = y0, tile_base = r0 * n_tx, row_base = r0;
-            const unsigned long long *gb = T.gbits;              // indexed by the row of the whole call
+            const unsigned long long *gb = gwords;               // indexed by the row of the whole call
             unsigned ntx = n_tx;
             unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
             void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw};
@@ -523,12 +587,17 @@ struct JitBackend final : Backend {
     const char *kernel_name() const override { return ss > 1 ? "maray_jit_pixels_ss" : "maray_jit_pixels"; }
     void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { *row_passes = n_row_passes; *order_kernels = n_order_kernels; }
     uint64_t refine_count() const override { return n_refine_passes; }
-    size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override {
+    uint64_t census_count() const override { return n_census; }
+    size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, false); }
+    size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true); }
+    // the ROW pass's and the second bounds' words of the set the last launch used, or (census) the words that launch read
+    size_t debug_words(uint64_t *words, size_t cap, uint32_t *per_rect, bool census) {
         if (!n_gwords || cur_set < 0 || !tabs[cur_set].gbits) throw Error{MARAY_E_ARG, "no guard words: a program without guards, or no launch yet"};
         HIP_TRY(hipSetDevice(device));
         if (have_last) HIP_TRY(hipStreamSynchronize(last_stream));
         const size_t n = last_gbits_n;
-        if (words && cap) HIP_TRY(hipMemcpy(words, tabs[cur_set].gbits, std::min(n, cap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        const unsigned long long *src = census && reuse.sets[cur_set].census ? tabs[cur_set].cbits : tabs[cur_set].gbits;
+        if (words && cap) HIP_TRY(hipMemcpy(words, src, std::min(n, cap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         *per_rect = n_gwords;
         return n;
     }

@@ -617,4 +617,66 @@ std::shared_ptr<const JitRefineCode> jit_code_refine(const maray_program &prog, 
     return fut.get();
 }
 
+// maray_jit_census of a program (jit_source_census): a fourth module, kept like maray_jit_refine's -- in the process and on disk
+// under a key of its own (<key>.mrcs: the code object, the eligible masks, their count and a checksum) made of the program's
+// name, which holds all that decides the text; the other modules' keys and entries do not move.  Built by a helper process
+// beside the others (JitBackend::init asks for it on a thread of its own).  Null when no guard bit is eligible.
+std::shared_ptr<const JitCensusCode> jit_code_census(const maray_program &prog)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_future<std::shared_ptr<const JitCensusCode>>> built;
+    std::string key;
+    {
+        const std::string name = program_name(prog) + "|census";
+        key = hex128(fnv1a(name.data(), name.size(), 0xcbf29ce484222325ull), fnv1a(name.data(), name.size(), 0x84222325cbf29ce4ull));
+    }
+    std::promise<std::shared_ptr<const JitCensusCode>> mine;
+    std::shared_future<std::shared_ptr<const JitCensusCode>> fut;
+    bool build = false;
+    {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = built.find(key);
+        if (it != built.end()) fut = it->second;
+        else {
+            if (built.size() > 32) built.clear();
+            fut = mine.get_future().share(); built.emplace(key, fut); build = true;
+        }
+    }
+    if (!build) return fut.get();
+    try {
+        auto out = std::make_shared<JitCensusCode>();
+        const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrcs";
+        std::vector<char> blob;
+        uint32_t nw = 0;
+        bool have = false;
+        if (!path.empty() && blob_read(path, blob) && blob.size() >= 4) {       // code object + masks + their count (0: nothing eligible)
+            memcpy(&nw, blob.data() + blob.size() - 4, 4);
+            if (nw <= 1024 && blob.size() >= 4 + (size_t)nw * 8) {
+                out->eligible.resize(nw);
+                if (nw) memcpy(out->eligible.data(), blob.data() + blob.size() - 4 - (size_t)nw * 8, (size_t)nw * 8);
+                blob.resize(blob.size() - 4 - (size_t)nw * 8);
+                out->code.swap(blob);
+                have = true;
+            }
+        }
+        if (!have) {
+            const std::string src = jit_source_census(prog, &out->eligible);
+            if (!src.empty()) compile_aside(src, "census", "CENSUS", out->code);
+            else out->eligible.clear();
+            blob = out->code;
+            nw = (uint32_t)out->eligible.size();
+            blob.insert(blob.end(), (const char *)out->eligible.data(), (const char *)out->eligible.data() + (size_t)nw * 8);
+            blob.insert(blob.end(), (const char *)&nw, (const char *)&nw + 4);
+            if (!path.empty()) blob_write(dir, path, blob);
+        }
+        if (out->code.empty() || out->eligible.empty()) out.reset();            // nothing to launch
+        mine.set_value(out);
+    } catch (...) {
+        mine.set_exception(std::current_exception());
+        std::lock_guard<std::mutex> lk(m);
+        built.erase(key);                               // a failed build is not remembered (the waiters still see its error)
+    }
+    return fut.get();
+}
+
 }   // namespace maray

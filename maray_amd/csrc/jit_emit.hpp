@@ -228,6 +228,7 @@ struct Emitter {
         int cmp_kind = 0; std::string cmp_x; double cmp_k = 0.0;
         bool cst = false;       // a known constant (a literal of the tape, MR_NONE / MR_ALL as numbers, or arithmetic on such): cval
         double cval = 0.0;
+        bool taint = false;     // census: its cone reads a parameter the ROW section does not, or holds a Sin that may defer its tile
     };
     const maray_program &P;
     std::string out;
@@ -266,6 +267,15 @@ struct Emitter {
     std::map<std::string, std::pair<std::string, uint32_t>> texels;      // (image, x, y, width) -> its variable and the block it was declared in
     const RedPlan *rplan = nullptr;             // PIXEL: the guarded OR-reductions of the section being emitted (null: walk the tree as written)
     uint32_t red_serial = 0;                    // (names of the labels: a section may be emitted more than once into one kernel)
+    // PIXEL: the census form (jit_source_census).  The section's text is what maray_jit_pixels gets, with two differences, both
+    // at a reduction: a leaf's LEAF_END also records a hit for the leaf's bit -- flag `bit` of the pass's rectangle, mr_chit,
+    // where its value is != 0 (a max reduction: differs bitwise from +0.0) on some pixel inside the picture, mr_cin -- and the
+    // loop over a word's bits does not leave early on "every lane covered".  Out, per guard bit: census_leaf = some
+    // instrumented leaf records it; census_bad = a hit does not say all the PIXEL section skips on that bit (it gates a plain
+    // SKIPZ region too, alone or through a derived guard; a leaf on it is tainted; its reduction sits inside a region).
+    bool census = false;
+    uint64_t census_row_params = ~0ull;         // bit p: the ROW section reads PARAM p (a set's key holds its value); the others taint
+    std::vector<uint8_t> census_leaf, census_bad;
     explicit Emitter(const maray_program &p) : P(p) {}
 
     // word wi of the guard words of the rectangle at hand: an SGPR pair by name (<= 12 words); beyond, lane wi % 64 of a
@@ -325,6 +335,7 @@ struct Emitter {
                     // MR_ALL / MR_NONE typing, never the k of a fused compare (cst stays false): a scalar load from the
                     // module's parameter table, whose address every pass makes opaque like the constant table's (mr_par)
                     t.d = "mr_par[" + std::to_string(idx - MARAY_SPEC_PARAM0) + "]";
+                    t.taint = idx - MARAY_SPEC_PARAM0 >= 64 || !((census_row_params >> (idx - MARAY_SPEC_PARAM0)) & 1);
                     return &t;
                 }
                 static const char *const spec_name[] = {"X", "Y", "", "XMAX", "XMIN", "YMAX", "YMIN"};
@@ -335,7 +346,7 @@ struct Emitter {
         // the double form of a value, materialising it once if needed
         // leaf: the block of a reduction's leaf (no variable, no else).  mask: the lanes on which what the region computes can
         // matter -- a wave-level region of booleans computes q of n = p AND q (p OR q): where p is 0 (1), n does not depend on q
-        struct Open { uint32_t end; bool as_bool; bool nz; uint32_t id; bool leaf; std::string mask; };
+        struct Open { uint32_t end; bool as_bool; bool nz; uint32_t id; bool leaf; std::string mask; bool taint = false; };
         std::vector<Open> open;     // SKIPZ / SKIPNZ regions being emitted, innermost last
         uint32_t next_scope = 1;
         auto dbl = [&](Val *v, const char *hint, uint32_t i, int which) -> std::string {
@@ -362,6 +373,8 @@ struct Emitter {
         if (rp) for (size_t k = 0; k < rp->reds.size(); k++) red_leaf_text[k].resize(rp->reds[k].leaf_end.size());
         std::string out_saved;                  // the section's text while a leaf's is being collected in `out`
         const uint32_t serial = red_serial++;
+        bool leaf_taint = false;                // census: the leaf being collected has a tainted op
+        auto census_mark = [&](std::vector<uint8_t> &v, uint32_t bit) { if (v.size() <= bit) v.resize(bit + 1, 0); v[bit] = 1; };
         for (uint32_t i = 0; i < n; i++) {
             const uint64_t ins = ops[i];
             const uint32_t op = MARAY_INS_OP(ins), aux = MARAY_INS_AUX(ins), dst = MARAY_INS_DST(ins);
@@ -369,6 +382,8 @@ struct Emitter {
             const uint8_t role = rp ? rp->role[i] : (uint8_t)RedPlan::NONE;
             if (role == RedPlan::IGNORED_SKIP) continue;            // legal: an evaluator may ignore any SKIP op
             if (role == RedPlan::LEAF_SKIP) {
+                leaf_taint = false;
+                if (census && !open.empty()) census_mark(census_bad, rp->reds[rp->red[i]].leaf_bit[rp->leaf[i]]);
                 out_saved.swap(out);                                // (out_saved was empty: leaves do not nest)
                 open.push_back(Open{i + aux, true, false, next_scope++, true, std::string()});
                 ktab_block.clear();
@@ -379,6 +394,7 @@ struct Emitter {
                 // if (some lane still needs it) { region } else result = 0 / 1;  -- a scalar branch on the ballot
                 const bool nz = op == MARAY_OP_SKIPNZ;
                 const uint32_t end = i + aux;
+                if (va) leaf_taint |= va->taint;
                 snprintf(name, sizeof name, "%s%u", prefix, end);
                 const uint32_t gref = MARAY_INS_A(ins);
                 const bool row_guard = pixel && MARAY_REF_KIND(gref) == MARAY_K_YVAL;
@@ -422,6 +438,7 @@ struct Emitter {
                         const uint32_t k = plan ? (uint32_t)plan->pos[g] : g;
                         m[k / 64] = 1ull << (k % 64);
                     } else for (uint32_t k : plan->members[g]) m[k / 64] |= 1ull << (k % 64);       // derived: any of its members' bits
+                    if (census) for (uint32_t k = 0; k < 64 * guard_words; k++) if ((m[k / 64] >> (k % 64)) & 1) census_mark(census_bad, k);
                     std::string any;
                     int terms = 0;
                     for (uint32_t wi = 0; wi < guard_words; wi++)
@@ -451,7 +468,7 @@ struct Emitter {
                 // in, and is entered nine times in ten (18 of 20 per pass): likely (board crop 82.3 -> 81.6 us).
                 out += "    if (__builtin_expect(" + cond + (pixel && !row_guard ? ", 1)) {\n" : ", 0)) {\n");
                 open.push_back(Open{end, typed_bool, nz, next_scope++, false,
-                                    (!row_guard && as_bool && va->kind == BOOL) ? (nz ? "~" + va->b : va->b) : std::string()});
+                                    (!row_guard && as_bool && va->kind == BOOL) ? (nz ? "~" + va->b : va->b) : std::string(), va->taint});
                 ktab_block.clear();
                 continue;
             }
@@ -471,6 +488,9 @@ struct Emitter {
             Val *vb = (op >= MARAY_OP_ADD && op <= MARAY_OP_APP && !forced[i]) ? ref(MARAY_INS_B(ins), 1) : nullptr;
             snprintf(name, sizeof name, "%s%u", prefix, i);
             const std::string self = name;
+            bool taint = (va && va->taint) || (vb && vb->taint) ||
+                         ((op == MARAY_OP_SIN || op == MARAY_OP_STEPSIN) && !(aux & MARAY_AUX_SIN_BOUNDED));
+            leaf_taint |= taint;
             Val r;
             std::string e;      // double expression
             std::string be;     // bool expression
@@ -626,6 +646,7 @@ struct Emitter {
                 }
                 if (role == RedPlan::INNER) {
                     r.kind = REDPART;
+                    r.taint = taint;
                     vals[i] = r;
                     is_bool_op[i] = rbool;
                     acc = (int)i;
@@ -636,6 +657,7 @@ struct Emitter {
                 // Per word: the reduction's bits of it, lowest first (s_ff1), each reached through a table of branches that
                 // follows an s_setpc (s_getpc returns the address of the instruction after itself: the table starts 12 bytes on)
                 const RedPlan::Red &red = rp->reds[id];
+                if (census) for (uint32_t b : red.leaf_bit) { census_mark(census_leaf, b); if (!open.empty()) census_mark(census_bad, b); }
                 const std::string rid = std::to_string(serial) + "_" + std::to_string(id);
                 const std::string racc = "mr_racc" + rid;
                 if (rbool) {
@@ -668,7 +690,7 @@ struct Emitter {
                     const std::string w = std::to_string(wi), next = "mr_rn" + rid + "_" + w;
                     const std::string nz = guard_word_nonzero(wi);
                     if (!nz.empty()) out += "    if (" + nz + ")\n";
-                    out += "    for (mr_mask mr_rm = " + guard_word(wi) + " & " + hex + "; mr_rm != 0ull" + (rbool ? " && !mr_covered(" + racc + ")" : std::string()) + "; ) {\n"
+                    out += "    for (mr_mask mr_rm = " + guard_word(wi) + " & " + hex + "; mr_rm != 0ull" + (rbool && !census ? " && !mr_covered(" + racc + ")" : std::string()) + "; ) {\n"
                            "        const unsigned mr_rk = (unsigned)__builtin_ctzll(mr_rm);\n"
                            "        mr_rm &= mr_rm - 1ull;\n"
                            "        asm goto(\"s_getpc_b64 s[20:21]\\n\\ts_add_u32 s20, s20, %0\\n\\ts_addc_u32 s21, s21, 0\\n\\ts_setpc_b64 s[20:21]\"";
@@ -704,6 +726,7 @@ struct Emitter {
                 // the AND / OR that ends a region: assign the variable declared before the `if`
                 const Open o = open.back();
                 open.pop_back();
+                taint |= o.taint;
                 if (o.as_bool && !be.empty()) {
                     out += "    b" + self + " = " + be + ";\n    } else b" + self + (o.nz ? " = MR_ALL;\n" : " = MR_NONE;\n");
                     r.kind = BOOL; r.b = "b" + self;
@@ -719,6 +742,7 @@ struct Emitter {
                 while (!open.empty() && open.back().end == i && !open.back().leaf) {     // enclosing regions that end here too
                     const Open o2 = open.back();
                     open.pop_back();
+                    taint |= o2.taint;
                     out += o.as_bool ? "    } else b" + self + (o2.nz ? " = MR_ALL;\n" : " = MR_NONE;\n")
                                      : "    } else " + self + (o2.nz ? " = 1.0;\n" : " = 0.0;\n");
                 }
@@ -743,6 +767,13 @@ struct Emitter {
                 const std::string ra = "mr_racc" + std::to_string(serial) + "_" + std::to_string(id);
                 if (rp->reds[id].boolean) out += "    " + ra + " |= " + (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")") + ";\n";
                 else out += "    " + ra + " = mr_max(" + ra + ", " + dbl(&r, "m", i, 0) + ");\n";
+                if (census) {
+                    const uint32_t bit = rp->reds[id].leaf_bit[rp->leaf[i]];
+                    const std::string hit = rp->reds[id].boolean ? (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")")
+                                                                 : "mr_ballot(__double_as_longlong(" + dbl(&r, "m", i, 0) + ") != 0ll)";
+                    out += "    if (mr_any(" + hit + " & mr_cin) && mr_lane == 0u) mr_chit[" + std::to_string(bit) + "] = 1;\n";
+                    if (leaf_taint || taint || r.taint) census_mark(census_bad, bit);
+                }
                 red_leaf_text[id][rp->leaf[i]].swap(out);
                 out.swap(out_saved);
                 out_saved.clear();
@@ -755,6 +786,7 @@ struct Emitter {
                 if (dst != MARAY_DST_NONE) slot[dst] = (int)i;
                 continue;
             }
+            r.taint |= taint;
             vals[i] = r;
             is_bool_op[i] = r.kind == BOOL;
             acc = (int)i;

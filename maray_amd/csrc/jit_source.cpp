@@ -893,6 +893,105 @@ std::string jit_source(const maray_program &P, int min_waves)
     return S.splice_constants(MR_STORE_RUN);
 }
 
+// ---- maray_jit_census --------------------------------------------------------------------------------------------------------
+// Folds a rectangle's hit flags into its guard words: out = word & (hits | ~eligible), into the set's second table of words --
+// the ROW pass's and the second bounds' words stay what they are (maray_hip_debug_guard_words reads them; the pixel launches
+// of a set that has been through its census read `out`).  One work-item per word; the eligible masks are literals of the
+// text.  A word without an eligible bit set is copied (and its flags unread).
+static std::string census_apply_kernel(const std::vector<uint64_t> &eligible)
+{
+    std::string s = "extern \"C\" __global__ void __launch_bounds__(256) maray_jit_census_apply(const unsigned long long *__restrict__ gbits, const unsigned char *__restrict__ hits,\n"
+                    "                                                                         unsigned long long *__restrict__ out, unsigned n_words)\n{\n"
+                    "    const unsigned i = blockIdx.x * 256u + threadIdx.x;                  // (the host keeps the words of a launch below 2^32)\n"
+                    "    if (i >= n_words) return;\n"
+                    "    unsigned long long mr_el = 0ull;\n"
+                    "    switch (i % " + std::to_string(eligible.size()) + "u) {\n";
+    for (size_t j = 0; j < eligible.size(); j++) {
+        char hex[32];
+        snprintf(hex, sizeof hex, "0x%llxull", (unsigned long long)eligible[j]);
+        s += "    case " + std::to_string(j) + ": mr_el = " + hex + "; break;\n";
+    }
+    s += "    }\n"
+         "    const unsigned long long word = gbits[i];\n"
+         "    if ((word & mr_el) == 0ull) { out[i] = word; return; }\n"
+         "    const unsigned long long *h = (const unsigned long long *)(hits + (size_t)i * 64u);      // flag of bit b of word i: byte 64 i + b\n"
+         "    unsigned long long m = 0ull;\n"
+         "    for (unsigned k = 0; k < 8u; k++) {\n"
+         "        const unsigned long long v = h[k];\n"
+         "        for (unsigned b = 0; b < 8u; b++) m |= ((v >> (8u * b)) & 1ull) << (8u * k + b);\n"
+         "    }\n"
+         "    out[i] = word & (m | ~mr_el);\n"
+         "}\n";
+    return s;
+}
+
+// Source of maray_jit_census (and maray_jit_census_apply): the narrow form of maray_jit_pixels with the emitter's census flag
+// set (jit_emit.hpp, Emitter::census) -- the prologue, the head, the strip's and the tile's guard words, the pass's tables and
+// the section are the very text jit_source() emits, which is the soundness argument: a leaf is evaluated on a rectangle's
+// pixels by the instructions that render them.  What differs is what stands here: a tile without a guard bit is left at once
+// instead of painted, no pixel is converted or stored, and every leaf a pass enters records, where it is != 0 on a pixel
+// inside the picture, a byte flag for its bit in the pass's rectangle (`hits`: 64 x n_gwords bytes per rectangle, indexed
+// like the guard words; idempotent plain stores of 1 from lane 0).  The launch is the pixel launch's, over the geometry of a
+// kept set.  *eligible: per guard word, the bits a hit decides (see Emitter::census); "" when there are none.
+std::string jit_source_census(const maray_program &P, std::vector<uint64_t> *eligible_out, int min_waves)
+{
+    if (eligible_out) eligible_out->clear();
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    if (!g.n || S.reductions.empty() || jit_wide_general(P, S.n_gwords, K)) return "";
+    if (g.per_lane() && g.sub > 1) E.gw_lane_base = "mr_gsub";
+    E.census = true;
+    E.census_row_params = row_param_mask(P);
+    std::string &s = E.out;
+    std::string head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_census(");
+    const char tail[] = "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw)";
+    head.replace(head.find(tail), sizeof tail - 1, "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw, unsigned char *__restrict__ mr_hits)");
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; census form: which guarded leaves are != 0 on some pixel of a rectangle\n" +
+         PIXELS_PROLOGUE + head + S.texture_loads() + strip_guard_fetch(g) +
+         "    (void)rgb8; (void)rgb64;\n"
+         "    for (unsigned t = 0; t < tiles; t++) {\n"
+         "    const unsigned x0 = (tile0 + t) * 256u;\n"
+         "    if (x0 >= w) break;\n"
+         "/*MR_KBASE*/" + tile_guard_fetch(g) +
+         sky_test(g) + "    continue;\n    }\n"
+         "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + PIXELS_PASS_TABLES + pass_guard_words(g) +
+         "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
+         "    const double X = (double)x;\n"
+         "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
+         "    float mr_defer = 0.0f;\n"
+         "    (void)X; (void)mr_defer;\n"
+         "    const mr_mask mr_cin = mr_ballot(x < w);                                 // the lanes inside the picture\n"
+         "    // the flags of this pass's rectangle: rectangles are numbered like their guard words\n"
+         "    unsigned char *mr_chit = mr_hits + (((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * " + std::to_string(g.sub) + "u + " +
+         (g.sub > 1 ? g.esub : std::string("0u")) + ") * " + std::to_string(64 * g.n) + "u;\n";
+    {   // the variant of a tile without a guard bit is not part of this kernel, but it comes first in maray_jit_pixels and takes
+        // the first entries of the constant table and the first label numbers: emitted and dropped, so that the section below
+        // is that kernel's text entry for entry
+        const size_t keep = s.size();
+        E.td = "mr_d"; E.tm = "mr_m"; E.assume_guards_zero = true; E.rplan = nullptr;
+        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+        s.resize(keep);
+    }
+    E.td = "double"; E.tm = "mr_mask"; E.assume_guards_zero = false; E.rplan = &S.reductions;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    s += "    (void)o0; (void)o1; (void)o2;\n"
+         "    }\n"
+         "    }\n}\n";
+    std::vector<uint64_t> eligible(g.n, 0);
+    bool any = false;
+    for (uint32_t b = 0; b < 64 * g.n && b < E.census_leaf.size(); b++)
+        if (E.census_leaf[b] && !(b < E.census_bad.size() && E.census_bad[b])) { eligible[b / 64] |= 1ull << (b % 64); any = true; }
+    if (!any) return "";
+    s += census_apply_kernel(eligible);
+    if (eligible_out) *eligible_out = eligible;
+    return S.splice_constants("");
+}
+
 
 // ---- maray_jit_pixels_ss ---------------------------------------------------------------------------------------------------------
 static const char SAMPLES_PROLOGUE[] =

@@ -9,6 +9,8 @@
 // memory, never a wrong pixel, because a hit compares whole keys), so the tiles of a one-shot render keep sharing the
 // scratch and allocate nothing.  Kept sets are bounded by count and by bytes and evicted least recently used; a set that
 // could not fit the byte budget is simply not kept.  jit_backend.cpp owns the device memory behind the set numbers.
+// Two things are derived from a set's guard words once it is found filled, and kept with it: the launch order, and before it the
+// census that clears the bits of shapes that are zero on every pixel of a rectangle (census_due).
 #pragma once
 
 #include <cstddef>
@@ -55,6 +57,7 @@ struct RowReuse {
         RowKey key;
         bool keyed = false;         // the tables hold the ROW outputs of `key` (set only once the ROW kernel is enqueued)
         bool order = false;         // ... and the launch order computed from its guard bits
+        bool census = false;        // ... and the second table of guard words the census made of them (maray_jit_census): without the bits of leaves that are zero on every pixel of a rectangle
         uint32_t launches = 0;      // launches that used the set under this key: the second one (the first that found it filled) computes the order
         uint64_t stamp = 0;         // last use (kept sets: least recently used goes first)
         size_t bytes = 0;           // kept sets: device bytes accounted to the set (0 = not in use)
@@ -79,6 +82,13 @@ struct RowReuse {
 
     // A launch uses set s, found by find().
     void touch(int s) { sets[s].stamp = ++clock; sets[s].launches++; }
+
+    // Is the census of set s due on this launch?  Like the launch order it costs about a launch and is paid by the first launch
+    // that finds the set holding its key (launches >= 2: a one-shot render never pays), once per filling -- place() and a
+    // refill withdraw the flag with the order's -- and only while sets are reused at all: with reuse off every launch that asks
+    // for a ROW pass writes the words again.  matched: the set holds this launch's key.  The caller sets Set::census once the
+    // kernels are enqueued, and enqueues them in front of the order kernel, which counts the bits that are left.
+    bool census_due(int s, bool matched) const { return enabled && matched && sets[s].keyed && !sets[s].census && sets[s].launches >= 2; }
 
     bool was_seen(uint64_t h) const {
         for (uint64_t v : seen) if (v == h) return true;
@@ -129,6 +139,7 @@ struct RowReuse {
         }
         sets[s].keyed = false;
         sets[s].order = false;
+        sets[s].census = false;
         sets[s].launches = 0;                           // (touch() by filled() counts this launch)
         sets[s].key = key;
         return s;
