@@ -524,7 +524,7 @@ int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_t n_tex,
  * bytes.  The result is an ordinary PNG -- IHDR (8-bit truecolour, no interlace), IDAT chunks of at most 2^30 bytes, IEND,
  * CRC-32 by zlib's crc32 -- around this stream:
  *   - filtered data: row y is one filter byte followed by the row's 3 w bytes.  The encoder writes filter 0 (None) in every
- *     row; a later one may write any type 0 .. 4 that a decoder accepts;
+ *     row unless a row filter is asked for ("Row filters" below: any type 0 .. 4);
  *   - segments: each row's 3 w + 1 filtered bytes are cut into segments of SEG = 256 pixels (the last of a row may be
  *     shorter; the filter byte belongs to the row's first segment).  Segments are compressed independently: no match
  *     reaches back over a segment's start;
@@ -611,6 +611,49 @@ int maray_hip_time_png_encode_ex(int device, const void *d_rgb8, uint32_t w, uin
  * of the last byte is zero).  cap < ceil(*header_bits / 8): MARAY_E_ARG. */
 int maray_png_dynamic_codes(const uint32_t lit_counts[286], const uint32_t dist_counts[30], uint8_t lit_lens[286], uint8_t dist_lens[30],
                             uint8_t *header, size_t cap, size_t *header_bits);
+/* Row filters: the filter byte of every row, opt-in everywhere; MARAY_PNG_FILTER_NONE is everything above, byte for byte.
+ * A filter turns a vertical repeat or a ramp into a constant, and a constant is what the distance-3 run tokeniser codes well.
+ *   - the option: NONE writes type 0 in every row; SUB .. PAETH force PNG type 1 .. 4 on every row (each filter's arithmetic
+ *     on its own); ADAPTIVE picks a type per row by the rule below.  Any other value: MARAY_E_ARG, reported before a device
+ *     is looked for;
+ *   - arithmetic: PNG's, with bpp = 3, over the WHOLE row -- segments cut the compression, not the filter: the left and
+ *     upper-left neighbours of a segment's first pixel are the previous segment's last pixels; neighbours left of x = 0 are 0,
+ *     and so is the row above row 0; Average is floor((a + b) / 2) on the 9-bit sum; Paeth breaks ties in the order a, b, c;
+ *     everything modulo 256;
+ *   - tokens: the tokeniser above, applied to the FILTERED pixels: a segment's first pixel is literal, a run of filtered
+ *     pixels equal to the filtered pixel before them is one distance-3 match, closed every 64 pixels; the filter byte t is the
+ *     literal in front of the row's first segment.  The slot bounds hold for any bytes: unchanged.  The Adler-32 is over the
+ *     filtered bytes, t included;
+ *   - the rule (ADAPTIVE), exact integer arithmetic and independent of launch order: for row y and type t, bytes_t = the sum
+ *     over the row's segments of the bytes the segment occupies as a fixed-Huffman segment under t, bits_t = the sum of those
+ *     segments' token bits (block header, filter byte and tokens, without the end-of-block); the row takes the smallest
+ *     (bytes_t, bits_t, t).  With dynamic codes the SAME rule with the fixed codes' costs is used: a proxy, not that coder's
+ *     own optimum;
+ *   - size: with fixed codes a row's ADAPTIVE bytes are never more than its type-0 bytes, so an ADAPTIVE file is never larger
+ *     than the NONE file of the same raster.  Forced types promise nothing;
+ *   - the row above a cut: a band's first row is filtered like any other row (later bands of a raster read the row above
+ *     them in the raster; maray_hip_render_png_opts keeps a band's last row in a 3 w-byte carry buffer, copied on the stream
+ *     before the next band is rendered).  With fixed codes the file therefore stays a function of the raster and the filter
+ *     option alone: the same for every MARAY_PNG_BAND_ROWS and stream.  With dynamic codes the bytes depend on the cut as
+ *     above; the filter types and the decoded raster do not;
+ *   - maray_gen and the animations (maray_gen_animation, maray_hip_render_apng, maray_hip_apng_encode_device) do not take the
+ *     option: maray_gen_opts.encoder has no word for it.
+ * How it runs, per band, before the kernels above: ADAPTIVE: maray_png_filter_cost (one wavefront per segment: the tokeniser's
+ * counting for all five types at once, five (bytes, bits) pairs per segment) and maray_png_filter_pick (one wavefront per
+ * row); a forced type: the rows' types are set to the constant.  Then the filtered forms of maray_png_compress,
+ * maray_png_histogram and maray_png_compress_dyn read the row's type. */
+enum { MARAY_PNG_FILTER_NONE = 0, MARAY_PNG_FILTER_ADAPTIVE = 1, MARAY_PNG_FILTER_SUB = 2, MARAY_PNG_FILTER_UP = 3, MARAY_PNG_FILTER_AVERAGE = 4, MARAY_PNG_FILTER_PAETH = 5 };
+/* The encoder's options: `codes` (MARAY_PNG_CODES_*), `filter` (MARAY_PNG_FILTER_*), and six reserved words that must be 0
+ * (else MARAY_E_ARG).  A null pointer stands for all zeros. */
+typedef struct { uint32_t codes, filter, reserved[6]; } maray_png_opts;
+/* The three entry points with the options; with filter = MARAY_PNG_FILTER_NONE each is exactly its `_ex` form. */
+int maray_hip_png_encode_device_opts(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_opts *opts, void *stream,
+                                     uint8_t **png_out, size_t *n_out);
+int maray_hip_render_png_opts(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, const maray_png_opts *opts,
+                              uint8_t **png_out, size_t *n_out);
+/* (with a filter the kernels timed include maray_png_filter_cost and maray_png_filter_pick, or the constant's fill) */
+int maray_hip_time_png_encode_opts(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_opts *opts, int reps, float *ms_avg,
+                                   uint64_t *stream_bytes);
 
 /* ---- animation (one APNG, encoded on the device frame by frame) ----------------------------------------------------
  * An animation is written as ONE file: an APNG, i.e. a PNG whose IDAT image is frame 0 (any PNG reader shows it) followed

@@ -8,11 +8,13 @@ from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, EN
                   gen_cache_clear, gen_cache_info, gen_to_image, image_read, lib, lib_path, png_bytes_to_host, png_encode_device, png_read, png_write, time_filter,
                   time_png_encode, time_shutter_reduce, transfer_table, var_id, version,
                   apng_encode_device, frame_delta, gen_animation, time_frame_delta,
-                  CODES_DYNAMIC, CODES_FIXED, ENCODER_DYNAMIC, png_dynamic_codes)
+                  CODES_DYNAMIC, CODES_FIXED, ENCODER_DYNAMIC, png_dynamic_codes,
+                  PNG_FILTER_ADAPTIVE, PNG_FILTER_AVERAGE, PNG_FILTER_NONE, PNG_FILTER_PAETH, PNG_FILTER_SUB, PNG_FILTER_UP, PngOpts)
 
 __all__ = ['Scene', 'Tape', 'Context', 'PinnedRaster', 'MarayError', 'gen', 'gen_to_image', 'gen_cache_clear', 'gen_cache_info', 'device_count', 'lib', 'lib_path',
            'png_read', 'png_write', 'image_read', 'version', 'var_id', 'Program', 'BACKEND_TAPE', 'BACKEND_TAPE_SMEM', 'BACKEND_JIT', 'BACKEND_AUTO', 'FILTER_BOX', 'FILTER_TENT',
            'time_filter', 'ENCODER_HOST', 'ENCODER_DEVICE', 'GenOpts', 'png_encode_device', 'time_png_encode', 'png_bytes_to_host',
            'TRANSFER_NONE', 'TRANSFER_SRGB', 'CtxOpts', 'transfer_table', 'time_shutter_reduce',
            'frame_delta', 'apng_encode_device', 'gen_animation', 'time_frame_delta',
-           'CODES_FIXED', 'CODES_DYNAMIC', 'ENCODER_DYNAMIC', 'png_dynamic_codes']
+           'CODES_FIXED', 'CODES_DYNAMIC', 'ENCODER_DYNAMIC', 'png_dynamic_codes',
+           'PNG_FILTER_NONE', 'PNG_FILTER_ADAPTIVE', 'PNG_FILTER_SUB', 'PNG_FILTER_UP', 'PNG_FILTER_AVERAGE', 'PNG_FILTER_PAETH', 'PngOpts']

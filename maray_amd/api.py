@@ -16,7 +16,20 @@ FILTER_BOX, FILTER_TENT = 0, 1
 ENCODER_HOST, ENCODER_DEVICE = 0, 1
 ENCODER_DYNAMIC = 0x100                 # a flag on ENCODER_DEVICE: dynamic-Huffman codes (MARAY_ENCODER_DYNAMIC)
 CODES_FIXED, CODES_DYNAMIC = 0, 1       # MARAY_PNG_CODES_*
+# MARAY_PNG_FILTER_*: the device PNG encoder's row filter (png_filter=; `filter` is the reconstruction filter everywhere)
+PNG_FILTER_NONE, PNG_FILTER_ADAPTIVE, PNG_FILTER_SUB, PNG_FILTER_UP, PNG_FILTER_AVERAGE, PNG_FILTER_PAETH = range(6)
 TRANSFER_NONE, TRANSFER_SRGB = 0, 1
+
+
+class PngOpts(C.Structure):
+    """maray_png_opts"""
+    _fields_ = [('codes', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+
+
+def _png_opts(codes, png_filter):
+    o = PngOpts()
+    o.codes, o.filter = codes, png_filter
+    return o
 
 
 class MarayError(RuntimeError):
@@ -175,6 +188,9 @@ def lib():
         'maray_hip_png_encode_device_ex': (C.c_int, [C.c_int, vp, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_render_png_ex': (C.c_int, [vp, u32, u32, vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_time_png_encode_ex': (C.c_int, [C.c_int, vp, u32, u32, u32, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_hip_png_encode_device_opts': (C.c_int, [C.c_int, vp, u32, u32, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_png_opts': (C.c_int, [vp, u32, u32, vp, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_png_encode_opts': (C.c_int, [C.c_int, vp, u32, u32, vp, C.c_int, C.POINTER(C.c_float), u64p]),
         'maray_png_dynamic_codes': (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         'maray_hip_png_bytes_to_host': (C.c_uint64, []),
         'maray_hip_frame_delta': (C.c_int, [C.c_int, vp, vp, u32, u32, vp, C.POINTER(u32)]),
@@ -610,12 +626,13 @@ class Context:
         cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
         _check(lib().maray_hip_render_tiles_shutter(self._h, w, h, flat, len(tiles), vp_, n, image.ctypes.data, cb, None))
 
-    def render_png(self, w, h, frames=None, codes=CODES_FIXED):
-        """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png_ex); frames: as
-        for render_rows_shutter (None: the plain render); codes=CODES_DYNAMIC: a Huffman code fitted to every band."""
+    def render_png(self, w, h, frames=None, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
+        """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png_opts); frames: as
+        for render_rows_shutter (None: the plain render); codes=CODES_DYNAMIC: a Huffman code fitted to every band;
+        png_filter=PNG_FILTER_*: the rows' PNG filter (ADAPTIVE: per row the type that makes the row smallest)."""
         n, vp_, keep = (0, None, None) if frames is None else self._frames(frames)
         p, sz = C.c_void_p(), C.c_size_t()
-        _check(lib().maray_hip_render_png_ex(self._h, w, h, vp_, n, codes, C.byref(p), C.byref(sz)))
+        _check(lib().maray_hip_render_png_opts(self._h, w, h, vp_, n, C.byref(_png_opts(codes, png_filter)), C.byref(p), C.byref(sz)))
         return _take_bytes(p, sz)
 
     def render_apng(self, w, h, frames, sub=1, fps=(25, 1), loops=0):
@@ -816,19 +833,21 @@ def _take_bytes(p, sz):
         lib().maray_free(p)
 
 
-def png_encode_device(d_ptr, w, h, device=0, stream=0, codes=CODES_FIXED):
+def png_encode_device(d_ptr, w, h, device=0, stream=0, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
     """A packed (h, w, 3) uint8 raster in device memory (any alignment) -> the bytes of a PNG, encoded on the device
-    (maray_hip_png_encode_device_ex); enqueued on `stream` and waited for.  codes=CODES_DYNAMIC: a Huffman code fitted to
-    every band of rows instead of the fixed codes."""
+    (maray_hip_png_encode_device_opts); enqueued on `stream` and waited for.  codes=CODES_DYNAMIC: a Huffman code fitted to
+    every band of rows instead of the fixed codes; png_filter=PNG_FILTER_*: the rows' PNG filter."""
     p, sz = C.c_void_p(), C.c_size_t()
-    _check(lib().maray_hip_png_encode_device_ex(device, d_ptr or None, w, h, codes, stream or None, C.byref(p), C.byref(sz)))
+    _check(lib().maray_hip_png_encode_device_opts(device, d_ptr or None, w, h, C.byref(_png_opts(codes, png_filter)), stream or None, C.byref(p),
+                                                  C.byref(sz)))
     return _take_bytes(p, sz)
 
 
-def time_png_encode(d_ptr, w, h, device=0, reps=10, codes=CODES_FIXED):
-    """(average ms of the encoder's kernels over the raster as one band, bytes of the stream they make)."""
+def time_png_encode(d_ptr, w, h, device=0, reps=10, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
+    """(average ms of the encoder's kernels over the raster as one band, bytes of the stream they make); with a png_filter the
+    kernels that choose the rows' types are among them."""
     ms, nb = C.c_float(), C.c_uint64()
-    _check(lib().maray_hip_time_png_encode_ex(device, d_ptr or None, w, h, codes, reps, C.byref(ms), C.byref(nb)))
+    _check(lib().maray_hip_time_png_encode_opts(device, d_ptr or None, w, h, C.byref(_png_opts(codes, png_filter)), reps, C.byref(ms), C.byref(nb)))
     return ms.value, nb.value
 
 

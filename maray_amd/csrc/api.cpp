@@ -911,20 +911,40 @@ int maray_hip_png_encode_device(int device, const void *d_rgb8, uint32_t w, uint
     return maray_hip_png_encode_device_ex(device, d_rgb8, w, h, MARAY_PNG_CODES_FIXED, stream, png_out, n_out);
 }
 
+// the words of a maray_png_opts (null: all zeros), checked before a device is looked for
+static void png_opts_words(const maray_png_opts *opts, uint32_t *codes, uint32_t *filter)
+{
+    *codes = opts ? opts->codes : (uint32_t)MARAY_PNG_CODES_FIXED;
+    *filter = opts ? opts->filter : (uint32_t)MARAY_PNG_FILTER_NONE;
+    REQUIRE(*codes == MARAY_PNG_CODES_FIXED || *codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
+    REQUIRE(png_filter_known(*filter), "unknown PNG filter");
+    for (int i = 0; opts && i < 6; i++) REQUIRE(!opts->reserved[i], "maray_png_opts: a reserved word is not 0");
+}
+
 int maray_hip_png_encode_device_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, void *stream, uint8_t **png_out,
                                    size_t *n_out)
+{
+    maray_png_opts o;
+    memset(&o, 0, sizeof o);
+    o.codes = codes;
+    return maray_hip_png_encode_device_opts(device, d_rgb8, w, h, &o, stream, png_out, n_out);
+}
+
+int maray_hip_png_encode_device_opts(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_opts *opts, void *stream,
+                                     uint8_t **png_out, size_t *n_out)
 {
     return guard([&] {
         REQUIRE(png_out && n_out, "null argument");
         *png_out = nullptr; *n_out = 0;
-        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
+        uint32_t codes, filter;
+        png_opts_words(opts, &codes, &filter);
         REQUIRE(d_rgb8, "null argument");
         REQUIRE(w && h, "empty image");
         png_check_size(w, h);
         PngEncoderLease E(device);
         PngPiece piece;
         piece.y0 = 0; piece.y1 = h;
-        E->encode_rows((const unsigned char *)d_rgb8, w, h, (hipStream_t)stream, piece, codes);
+        E->encode_rows((const unsigned char *)d_rgb8, w, h, (hipStream_t)stream, piece, codes, filter);
         png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
     });
 }
@@ -937,10 +957,20 @@ int maray_hip_render_png(maray_ctx *c, uint32_t w, uint32_t h, const double *val
 int maray_hip_render_png_ex(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, uint32_t codes, uint8_t **png_out,
                             size_t *n_out)
 {
+    maray_png_opts o;
+    memset(&o, 0, sizeof o);
+    o.codes = codes;
+    return maray_hip_render_png_opts(c, w, h, values, n_frames, &o, png_out, n_out);
+}
+
+int maray_hip_render_png_opts(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, const maray_png_opts *opts,
+                              uint8_t **png_out, size_t *n_out)
+{
     return guard([&] {
         REQUIRE(png_out && n_out, "null argument");
         *png_out = nullptr; *n_out = 0;
-        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
+        uint32_t codes, filter;
+        png_opts_words(opts, &codes, &filter);
         REQUIRE(c && c->backend, "null context");
         REQUIRE(w && h, "empty image");
         check_rows(w, h, 0, h);
@@ -960,7 +990,7 @@ int maray_hip_render_png_ex(maray_ctx *c, uint32_t w, uint32_t h, const double *
         E->encode_rendered(w, 0, h, E->own_stream, [&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t st) {
             if (values) c->backend->render_device_shutter(w, h, RowBlocks::range(b0, b1), values, n_frames, d8, st);
             else c->backend->render_device(w, h, RowBlocks::range(b0, b1), d8, nullptr, st);
-        }, piece, codes);
+        }, piece, codes, filter);
         png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
     });
 }
@@ -973,10 +1003,20 @@ int maray_hip_time_png_encode(int device, const void *d_rgb8, uint32_t w, uint32
 int maray_hip_time_png_encode_ex(int device, const void *d_rgb8, uint32_t w, uint32_t h, uint32_t codes, int reps, float *ms_avg,
                                  uint64_t *stream_bytes)
 {
+    maray_png_opts o;
+    memset(&o, 0, sizeof o);
+    o.codes = codes;
+    return maray_hip_time_png_encode_opts(device, d_rgb8, w, h, &o, reps, ms_avg, stream_bytes);
+}
+
+int maray_hip_time_png_encode_opts(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_opts *opts, int reps, float *ms_avg,
+                                   uint64_t *stream_bytes)
+{
     return guard([&] {
         REQUIRE(ms_avg, "null argument");
-        REQUIRE(codes == MARAY_PNG_CODES_FIXED || codes == MARAY_PNG_CODES_DYNAMIC, "unknown PNG codes");
-        *ms_avg = png_time_kernels(device, (const unsigned char *)d_rgb8, w, h, reps, stream_bytes, codes);
+        uint32_t codes, filter;
+        png_opts_words(opts, &codes, &filter);
+        *ms_avg = png_time_kernels(device, (const unsigned char *)d_rgb8, w, h, reps, stream_bytes, codes, filter);
     });
 }
 

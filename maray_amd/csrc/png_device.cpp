@@ -49,7 +49,8 @@ uint32_t band_rows_from_env()
 }
 
 // the scratch of a band of `rows` rows: where everything lies, and the kernels' arguments
-PngBandArgs band_args(PngEncoder &E, const unsigned char *src, uint32_t w, uint32_t rows, uint32_t codes = MARAY_PNG_CODES_FIXED)
+PngBandArgs band_args(PngEncoder &E, const unsigned char *src, uint32_t w, uint32_t rows, uint32_t codes = MARAY_PNG_CODES_FIXED,
+                      uint32_t filter = MARAY_PNG_FILTER_NONE, const unsigned char *above = nullptr)
 {
     const bool dyn = codes == MARAY_PNG_CODES_DYNAMIC;
     PngBandArgs a{};
@@ -72,6 +73,13 @@ PngBandArgs band_args(PngEncoder &E, const unsigned char *src, uint32_t w, uint3
     a.adler = (uint32_t *)(E.meta + o_adler);
     a.offsets = (uint64_t *)(E.meta + o_off);
     a.totals = (uint64_t *)(E.meta + o_tot);
+    if (filter != MARAY_PNG_FILTER_NONE) {                     // the rows' types, then (ADAPTIVE) ten words per segment
+        const size_t o_cost = up16(rows);
+        grow(E.filt, E.filt_cap, o_cost + (filter == MARAY_PNG_FILTER_ADAPTIVE ? (size_t)n * 40 : 0));
+        a.filter = filter; a.above = above;
+        a.row_filter = E.filt;
+        if (filter == MARAY_PNG_FILTER_ADAPTIVE) a.cost = (uint32_t *)(E.filt + o_cost);
+    }
     return a;
 }
 
@@ -89,7 +97,7 @@ PngEncoder::~PngEncoder()
 {
     (void)hipSetDevice(device);
     if (own_stream) { (void)hipStreamSynchronize(own_stream); (void)hipStreamDestroy(own_stream); }
-    (void)hipFree(slots); (void)hipFree(stream); (void)hipFree(meta); (void)hipFree(raster);
+    (void)hipFree(slots); (void)hipFree(stream); (void)hipFree(meta); (void)hipFree(raster); (void)hipFree(filt); (void)hipFree(carry);
     if (staging) (void)hipHostFree(staging);
     if (h_totals) (void)hipHostFree(h_totals);
     if (h_counts) (void)hipHostFree(h_counts);
@@ -279,9 +287,11 @@ extern "C" int maray_png_dynamic_codes(const uint32_t lit_counts[286], const uin
     catch (const std::exception &e) { set_last_error(e.what()); return MARAY_E_INTERNAL; }
 }
 
-void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out, uint32_t codes)
+void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out, uint32_t codes, uint32_t filter,
+                             const unsigned char *above)
 {
     if (codes != MARAY_PNG_CODES_FIXED && codes != MARAY_PNG_CODES_DYNAMIC) throw Error{MARAY_E_ARG, "unknown PNG codes"};
+    if (!png_filter_known(filter)) throw Error{MARAY_E_ARG, "unknown PNG filter"};
     if (!rows || !w) return;
     if (!d_rgb8) throw Error{MARAY_E_ARG, "null argument"};
     HIP_TRY(hipSetDevice(device));
@@ -290,7 +300,8 @@ void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t r
     std::vector<uint8_t> header;
     for (uint32_t r0 = 0; r0 < rows; r0 += std::min(step, rows - r0)) {
         const uint32_t n = std::min(step, rows - r0);
-        PngBandArgs a = band_args(*this, d_rgb8 + (size_t)r0 * w * 3, w, n, codes);
+        // (a band after the first has the row above it in the raster: src - 3 w)
+        PngBandArgs a = band_args(*this, d_rgb8 + (size_t)r0 * w * 3, w, n, codes, filter, r0 ? d_rgb8 + (size_t)(r0 - 1) * w * 3 : above);
         uint32_t code256 = 0;
         if (dyn) {
             // count the band's tokens, fit the code on the host, hand the device its table and the header's length
@@ -343,18 +354,31 @@ void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t r
 }
 
 void PngEncoder::encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,
-                                 const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out, uint32_t codes)
+                                 const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out, uint32_t codes,
+                                 uint32_t filter)
 {
     if (codes != MARAY_PNG_CODES_FIXED && codes != MARAY_PNG_CODES_DYNAMIC) throw Error{MARAY_E_ARG, "unknown PNG codes"};
+    if (!png_filter_known(filter)) throw Error{MARAY_E_ARG, "unknown PNG filter"};
     if (y0 >= y1 || !w) return;
     HIP_TRY(hipSetDevice(device));
     const uint32_t step = band_rows(w, codes);
     grow(raster, raster_cap, (size_t)std::min(step, y1 - y0) * w * 3);
+    const bool filtered = filter != MARAY_PNG_FILTER_NONE;
+    const size_t row_bytes = (size_t)w * 3;
+    const unsigned char *above = nullptr;
+    // (a filtered piece starts the image: the row above y0 > 0 would have to be rendered first, and no caller needs it)
+    if (filtered && y0 > 0) throw Error{MARAY_E_INTERNAL, "device PNG encoder: a filtered piece must start at row 0"};
+    if (filtered) grow(carry, carry_cap, row_bytes);
     for (uint32_t b0 = y0; b0 < y1; b0 += std::min(step, y1 - b0)) {
         const uint32_t b1 = b0 + std::min(step, y1 - b0);
         render(b0, b1, raster, st);
         HIP_TRY(hipSetDevice(device));
-        encode_rows(raster, w, b1 - b0, st, out, codes);
+        encode_rows(raster, w, b1 - b0, st, out, codes, filter, above);
+        if (filtered && b1 < y1) {
+            // the band's last row, before the next band's render overwrites the band buffer (the same stream: in order)
+            HIP_TRY(hipMemcpyAsync(carry, raster + (size_t)(b1 - b0 - 1) * row_bytes, row_bytes, hipMemcpyDeviceToDevice, st));
+            above = carry;
+        }
     }
 }
 
@@ -432,16 +456,18 @@ std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<cons
     return png_file(w, h, z.data(), z.size());
 }
 
-float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes, uint32_t codes)
+float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes, uint32_t codes,
+                       uint32_t filter)
 {
     if (codes != MARAY_PNG_CODES_FIXED && codes != MARAY_PNG_CODES_DYNAMIC) throw Error{MARAY_E_ARG, "unknown PNG codes"};
+    if (!png_filter_known(filter)) throw Error{MARAY_E_ARG, "unknown PNG filter"};
     const bool dyn = codes == MARAY_PNG_CODES_DYNAMIC;
     if (!d_rgb8 || !w || !rows || reps <= 0) throw Error{MARAY_E_ARG, "png_time_kernels: a raster, w, rows and reps > 0"};
     png_check_size(w, rows);
     if (((uint64_t)w * 3 + 1) * rows > (dyn ? PNG_DYN_BAND_MAX_BYTES : (uint64_t)1 << 30)) throw Error{MARAY_E_LIMIT, "png_time_kernels: more than one band's bytes"};
     PngEncoderLease E(device);
     HIP_TRY(hipSetDevice(device));
-    PngBandArgs a = band_args(*E.e, d_rgb8, w, rows, codes);
+    PngBandArgs a = band_args(*E.e, d_rgb8, w, rows, codes, filter);
     const hipStream_t st = E->own_stream;
     PngBandArgs count = a;                      // dynamic: the counting pass; `a` gets the code fitted to its counts once
     uint32_t len256 = 0;

@@ -77,9 +77,111 @@ __device__ __forceinline__ void or_bits(uint32_t *stage, uint32_t bit, uint32_t 
     if ((uint32_t)(v >> 32) && d + 1u < (uint32_t)STAGE_DW) atomicOr(&stage[d + 1u], (uint32_t)(v >> 32));
 }
 
-__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress(const PngBandArgs a)
+// the pixel at p (any alignment) from the aligned dwords that hold its three bytes
+__device__ __forceinline__ uint32_t load_pixel(const unsigned char *p)
 {
-    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW];
+    const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t *q = (const uint32_t *)(p - mis);
+    const uint32_t d0 = q[0], d1 = mis >= 2u ? q[1] : 0u;
+    return __builtin_amdgcn_alignbyte(d1, d0, mis) & 0xFFFFFFu;
+}
+
+// ---- row filters (include/maray_hip.h, "Row filters") ------------------------------------------------------------------------
+// PNG's filter type t (0 .. 4, bpp = 3) on one pixel, byte by byte on the packed 24 bits: x the pixel, a the pixel on its left,
+// b the pixel above, c the pixel above a.  Average is the floor of the 9-bit sum's half, Paeth's ties go a, b, c.
+__device__ __forceinline__ uint32_t filter_pixel(uint32_t t, uint32_t x, uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t out = 0u;
+#pragma unroll
+    for (uint32_t sh = 0u; sh < 24u; sh += 8u) {
+        const int ba = (int)((a >> sh) & 255u), bb = (int)((b >> sh) & 255u), bc = (int)((c >> sh) & 255u);
+        int pred = 0;
+        if (t == 1u) pred = ba;
+        else if (t == 2u) pred = bb;
+        else if (t == 3u) pred = (ba + bb) >> 1;
+        else if (t == 4u) {
+            const int p = ba + bb - bc, pa = abs(p - ba), pb = abs(p - bb), pc = abs(p - bc);
+            pred = pa <= pb && pa <= pc ? ba : pb <= pc ? bb : bc;
+        }
+        out |= (((x >> sh) - (uint32_t)pred) & 255u) << sh;
+    }
+    return out;
+}
+
+// Where a segment's pixels and the pixels above them lie.  Segments cut the compression, not the filter: a segment that is
+// not its row's first has the previous segment's last pixels on its left.
+struct FilterSeg {
+    const unsigned char *src;       // the segment's first pixel
+    const unsigned char *up;        // the pixel above it; null: the row above is all zeros (row 0 of the image)
+    bool has_left;
+};
+// the raw pixel and the pixel above it of lane 63 of the step before
+struct FilterCarry { uint32_t x, b; };
+
+__device__ __forceinline__ FilterSeg filter_seg(const PngBandArgs &a, uint32_t row, uint32_t s, const unsigned char *src)
+{
+    FilterSeg f;
+    f.src = src;
+    // rows are 3 w bytes apart: the row above is aligned differently from the row itself
+    f.up = row ? src - (size_t)a.w * 3 : a.above ? a.above + (size_t)s * PNG_SEG * 3 : nullptr;
+    f.has_left = s != 0u;
+    return f;
+}
+
+// One step of 64 pixels: lane's pixel x (0 past the segment's end) and its neighbours a, b, c.  Left neighbours come by
+// __shfl_up; lane 0 takes them from the step before (fc), and at the segment's start from the previous segment (two loads
+// more) or, at x = 0 of the row, as zeros.
+__device__ __forceinline__ void filter_neighbours(const FilterSeg &f, uint32_t p0, uint32_t npix, uint32_t lane, FilterCarry *fc, uint32_t *x,
+                                                  uint32_t *a, uint32_t *b, uint32_t *c)
+{
+    const uint32_t px = p0 + lane;
+    const bool valid = px < npix;
+    const uint32_t vx = valid ? load_pixel(f.src + (size_t)px * 3) : 0u;
+    const uint32_t vb = valid && f.up ? load_pixel(f.up + (size_t)px * 3) : 0u;
+    uint32_t va = (uint32_t)__shfl_up((int)vx, 1), vc = (uint32_t)__shfl_up((int)vb, 1);
+    if (lane == 0u) {
+        if (p0) { va = fc->x; vc = fc->b; }
+        else if (f.has_left) { va = load_pixel(f.src - 3); vc = f.up ? load_pixel(f.up - 3) : 0u; }
+        else { va = 0u; vc = 0u; }
+    }
+    fc->x = (uint32_t)__shfl((int)vx, 63);                  // (only a full step is followed by another)
+    fc->b = (uint32_t)__shfl((int)vb, 63);
+    *x = vx; *a = va; *b = vb; *c = vc;
+}
+
+// the lane's filtered pixel under type t (wave-uniform); 0 past the segment's end
+__device__ __forceinline__ uint32_t filter_step(const FilterSeg &f, uint32_t t, uint32_t p0, uint32_t npix, uint32_t lane, FilterCarry *fc)
+{
+    uint32_t x, a, b, c;
+    filter_neighbours(f, p0, npix, lane, fc, &x, &a, &b, &c);
+    return p0 + lane < npix ? filter_pixel(t, x, a, b, c) : 0u;
+}
+
+// One step of the tokeniser on the lane's (filtered) pixel `pix`, exactly as maray_png_compress cuts a step into tokens.
+// Returns 0: this lane starts no token; 1: its pixel is three literals; 2: it starts a match of *run pixels.  `last` carries
+// the step's last pixel on.
+__device__ __forceinline__ uint32_t token_of(uint32_t pix, uint32_t px, uint32_t npix, uint32_t lane, uint32_t *last, uint32_t *run)
+{
+    const bool valid = px < npix;
+    uint32_t prev = (uint32_t)__shfl_up((int)pix, 1);
+    if (lane == 0u) prev = *last;
+    const bool eq = valid && px != 0u && pix == prev;
+    const uint64_t m = __ballot(eq);
+    *last = (uint32_t)__shfl((int)pix, 63);
+    *run = 0u;
+    if (valid && !eq) return 1u;
+    if (eq && (lane == 0u || !((m >> (lane - 1u)) & 1ull))) {
+        const uint64_t rest = ~(m >> lane);
+        *run = rest ? (uint32_t)__ffsll((long long)rest) - 1u : 64u;
+        return 2u;
+    }
+    return 0u;
+}
+
+// F: the filtered form (the row's type from a.row_filter, the pixels through filter_step); else today's kernel
+template <bool F>
+__device__ __forceinline__ void compress_body(const PngBandArgs &a, uint32_t *stage_all)
+{
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t *stage = stage_all + wave * STAGE_DW;
     for (uint32_t i = lane; i < (uint32_t)STAGE_DW; i += 64u) stage[i] = 0u;
@@ -92,19 +194,24 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_compress(const PngBandArgs
         const uint32_t npix = seg_pixels(a.w, s), first = s == 0u ? 1u : 0u;
         const uint32_t n = 3u * npix + first;               // the segment's filtered bytes
         const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
-        // block header BFINAL = 0, BTYPE = 01 (the bits 0, 1, 0), then in a row's first segment the filter byte 0 as a literal
+        // block header BFINAL = 0, BTYPE = 01 (the bits 0, 1, 0), then in a row's first segment the filter byte as a literal
+        const uint32_t ft = F ? a.row_filter[row] : 0u;
+        const FilterSeg fs = F ? filter_seg(a, row, s, src) : FilterSeg{};
         uint32_t bitpos = 3u;
         if (lane == 0u) {
             or_bits(stage, 0u, 2u);
-            if (first) { uint32_t nb; const uint32_t c = literal(0u, &nb); or_bits(stage, 3u, c); }
+            if (first) { uint32_t nb; const uint32_t c = literal(ft, &nb); or_bits(stage, 3u, c); }
         }
         if (first) bitpos += 8u;
         uint32_t sum_a = 0u, sum_b = 0u, last = 0u;
+        FilterCarry fc{0u, 0u};
+        if (F && first && lane == 0u) { sum_a = ft; sum_b = n * ft; }     // the filter byte is byte 0 of its segment
         for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
             const uint32_t px = p0 + lane;
             const bool valid = px < npix;
             uint32_t pix = 0u;
-            if (valid) {
+            if (F) pix = filter_step(fs, ft, p0, npix, lane, &fc);
+            else if (valid) {
                 // the three bytes at src + 3 px from the aligned dwords that hold them (every dword read holds one of them)
                 const unsigned char *p = src + (size_t)px * 3;
                 const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
@@ -172,6 +279,18 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_compress(const PngBandArgs
         const uint32_t ndw = min((seg_len + 3u) >> 2, min(a.slot_bytes >> 2, (uint32_t)STAGE_DW));
         for (uint32_t i = lane; i < ndw; i += 64u) slot[i] = stage[i];
     }
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress(const PngBandArgs a)
+{
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW];
+    compress_body<false>(a, stage_all);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_filtered(const PngBandArgs a)
+{
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW];
+    compress_body<true>(a, stage_all);
 }
 
 // segments per group of the scan: a multiple of 64 that makes at most SCAN_BLOCK groups
@@ -307,15 +426,6 @@ constexpr int STAGE_DW_DYN = PNG_SLOT_MAX_DYN / 4;
 constexpr int HIST_BLOCK = 64 * PNG_HIST_WAVES, HIST_SUM_BLOCK = 320, ZERO_BLOCK = 256, ZERO_MAX_BLOCKS = 2048;
 static_assert(HIST_SUM_BLOCK >= (int)PNG_HIST_STRIDE && PNG_HIST_STRIDE >= PNG_LIT_SYMS, "one lane per count");
 
-// the pixel at p (any alignment) from the aligned dwords that hold its three bytes
-__device__ __forceinline__ uint32_t load_pixel(const unsigned char *p)
-{
-    const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
-    const uint32_t *q = (const uint32_t *)(p - mis);
-    const uint32_t d0 = q[0], d1 = mis >= 2u ? q[1] : 0u;
-    return __builtin_amdgcn_alignbyte(d1, d0, mis) & 0xFFFFFFu;
-}
-
 // One step of 64 pixels of a segment exactly as maray_png_compress cuts it into tokens.  Returns 0: this lane starts no
 // token; 1: its pixel is three literals; 2: it starts a match of *run pixels.  `last` carries the step's last pixel on.
 __device__ __forceinline__ uint32_t step_token(const unsigned char *src, uint32_t p0, uint32_t npix, uint32_t lane, uint32_t *last,
@@ -353,9 +463,9 @@ __device__ __forceinline__ uint32_t length_symbol(uint32_t len, uint32_t *eb, ui
     return 261u + 4u * e + ((l >> e) & 3u);
 }
 
-__global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram(const PngBandArgs a)
+template <bool F>
+__device__ __forceinline__ void histogram_body(const PngBandArgs &a, uint32_t *hist)
 {
-    __shared__ uint32_t hist[PNG_HIST_STRIDE];
     for (uint32_t i = threadIdx.x; i < PNG_HIST_STRIDE; i += HIST_BLOCK) hist[i] = 0u;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -364,11 +474,18 @@ __global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram(const PngBandA
         const uint32_t row = seg / a.nseg, s = seg - row * a.nseg;
         const uint32_t npix = seg_pixels(a.w, s);
         const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
-        if (s == 0u && lane == 0u) atomicAdd(&hist[0], 1u);         // the row's filter byte
+        const uint32_t ft = F ? a.row_filter[row] : 0u;
+        const FilterSeg fs = F ? filter_seg(a, row, s, src) : FilterSeg{};
+        FilterCarry fc{0u, 0u};
+        if (s == 0u && lane == 0u) atomicAdd(&hist[ft], 1u);        // the row's filter byte
         uint32_t last = 0u;
         for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
-            uint32_t pix, run;
-            const uint32_t kind = step_token(src, p0, npix, lane, &last, &pix, &run);
+            uint32_t pix, run, kind;
+            if (F) {
+                pix = filter_step(fs, ft, p0, npix, lane, &fc);
+                kind = token_of(pix, p0 + lane, npix, lane, &last, &run);
+            } else
+                kind = step_token(src, p0, npix, lane, &last, &pix, &run);
             if (kind == 1u) {
                 atomicAdd(&hist[pix & 255u], 1u);
                 atomicAdd(&hist[(pix >> 8) & 255u], 1u);
@@ -381,6 +498,18 @@ __global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram(const PngBandA
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < PNG_HIST_STRIDE; i += HIST_BLOCK) a.hist[(size_t)blockIdx.x * PNG_HIST_STRIDE + i] = hist[i];
+}
+
+__global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram(const PngBandArgs a)
+{
+    __shared__ uint32_t hist[PNG_HIST_STRIDE];
+    histogram_body<false>(a, hist);
+}
+
+__global__ __launch_bounds__(HIST_BLOCK) void maray_png_histogram_filtered(const PngBandArgs a)
+{
+    __shared__ uint32_t hist[PNG_HIST_STRIDE];
+    histogram_body<true>(a, hist);
 }
 
 // count i of the band = the sum of the blocks' counts i (a band has at most 2^28 bytes: no count overflows)
@@ -404,10 +533,9 @@ __device__ __forceinline__ void or_bits64(uint32_t *stage, uint32_t bit, uint64_
     if (w2 && d + 2u < (uint32_t)STAGE_DW_DYN) atomicOr(&stage[d + 2u], w2);
 }
 
-__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn(const PngBandArgs a)
+template <bool F>
+__device__ __forceinline__ void compress_dyn_body(const PngBandArgs &a, uint32_t *table, uint32_t *stage_all)
 {
-    __shared__ uint32_t table[PNG_LIT_SYMS];
-    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW_DYN];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t *stage = stage_all + wave * STAGE_DW_DYN;
     for (uint32_t i = threadIdx.x; i < PNG_LIT_SYMS; i += PC_BLOCK) table[i] = a.table[i];
@@ -422,15 +550,23 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn(const PngBand
         const uint32_t n = 3u * npix + first;
         const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
         uint32_t bitpos = 0u;
-        if (first) {                                        // the filter byte 0 as a literal
-            const uint32_t e = table[0];
+        const uint32_t ft = F ? a.row_filter[row] : 0u;
+        const FilterSeg fs = F ? filter_seg(a, row, s, src) : FilterSeg{};
+        FilterCarry fc{0u, 0u};
+        if (first) {                                        // the filter byte as a literal
+            const uint32_t e = table[ft];
             if (lane == 0u) or_bits64(stage, 0u, e & 0xFFFFu);
             bitpos = e >> 16;
         }
         uint32_t sum_a = 0u, sum_b = 0u, last = 0u;
+        if (F && first && lane == 0u) { sum_a = ft; sum_b = n * ft; }     // the filter byte is byte 0 of its segment
         for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
-            uint32_t pix, run;
-            const uint32_t kind = step_token(src, p0, npix, lane, &last, &pix, &run);
+            uint32_t pix, run, kind;
+            if (F) {
+                pix = filter_step(fs, ft, p0, npix, lane, &fc);
+                kind = token_of(pix, p0 + lane, npix, lane, &last, &run);
+            } else
+                kind = step_token(src, p0, npix, lane, &last, &pix, &run);
             const uint32_t px = p0 + lane;
             uint64_t tok = 0u;
             uint32_t nb = 0u;
@@ -484,6 +620,20 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn(const PngBand
     }
 }
 
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn(const PngBandArgs a)
+{
+    __shared__ uint32_t table[PNG_LIT_SYMS];
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW_DYN];
+    compress_dyn_body<false>(a, table, stage_all);
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void maray_png_compress_dyn_filtered(const PngBandArgs a)
+{
+    __shared__ uint32_t table[PNG_LIT_SYMS];
+    __shared__ uint32_t stage_all[PC_WAVES * STAGE_DW_DYN];
+    compress_dyn_body<true>(a, table, stage_all);
+}
+
 // bytes of the stream a dynamic band may take: the slots' bytes, the header's and a dword's slack, in whole 16 bytes
 __host__ __device__ inline uint64_t dyn_stream_cap(uint32_t n_segs, uint32_t slot_bytes) { return (uint64_t)n_segs * slot_bytes + 512u; }
 
@@ -523,9 +673,107 @@ __global__ __launch_bounds__(PC_BLOCK) void maray_png_gather_bits(const PngBandA
     }
 }
 
+// ---- row filters: which type a row takes (MARAY_PNG_FILTER_ADAPTIVE) -------------------------------------------------------------
+//   maray_png_filter_cost   one wavefront per segment, four per block, like maray_png_compress: the tokeniser's counting for
+//                           all five types at once, nothing emitted.  Per step the lane's pixel and its three neighbours are
+//                           loaded once, then five filtered pixels, five __ballot run masks and the bits of the lane's
+//                           literals or match; per-lane sums over the segment's steps, one packed wavefront reduction at the
+//                           end, and five (bytes, bits) pairs per segment: what the segment would occupy as a fixed-Huffman
+//                           segment (maray_png_compress's seg_len) and its token bits.
+//   maray_png_filter_pick   one wavefront per row: the sums of the row's segments' pairs, and the smallest (bytes, bits, type).
+// No LDS, no barrier, no scratch memory.
+constexpr int FC_WAVES = 4, FC_BLOCK = 64 * FC_WAVES;
+
+// the bits of a pixel's three fixed-Huffman literals (literal's lengths)
+__device__ __forceinline__ uint32_t literal_bits(uint32_t pix)
+{
+    return 24u + ((pix & 255u) >= 144u) + (((pix >> 8) & 255u) >= 144u) + ((pix >> 16) >= 144u);
+}
+
+// the bits of match3(len)
+__device__ __forceinline__ uint32_t match3_bits(uint32_t len)
+{
+    const uint32_t l = len - 3u;
+    if (len == 258u) return 8u + 5u;
+    if (l < 8u) return 7u + 5u;
+    const uint32_t eb = 29u - (uint32_t)__clz((int)l), code = 261u + 4u * eb + ((l >> eb) & 3u);
+    return (code < 280u ? 7u : 8u) + eb + 5u;
+}
+
+__global__ __launch_bounds__(FC_BLOCK) void maray_png_filter_cost(const PngBandArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t seg = blockIdx.x * FC_WAVES + (threadIdx.x >> 6);
+    if (seg >= a.n_segs) return;                            // (wave-uniform; the kernel has no barrier)
+    const uint32_t row = seg / a.nseg, s = seg - row * a.nseg;
+    const uint32_t npix = seg_pixels(a.w, s), first = s == 0u ? 1u : 0u;
+    const unsigned char *src = a.src + ((size_t)row * a.w + (size_t)s * PNG_SEG) * 3;
+    const FilterSeg fs = filter_seg(a, row, s, src);
+    FilterCarry fc{0u, 0u};
+    uint32_t last[5] = {0u, 0u, 0u, 0u, 0u}, acc[5] = {0u, 0u, 0u, 0u, 0u};     // (fully unrolled below: registers)
+    for (uint32_t p0 = 0u; p0 < npix; p0 += 64u) {
+        const uint32_t px = p0 + lane;
+        uint32_t x, pa, pb, pc;
+        filter_neighbours(fs, p0, npix, lane, &fc, &x, &pa, &pb, &pc);
+#pragma unroll
+        for (uint32_t t = 0u; t < 5u; t++) {
+            const uint32_t pix = px < npix ? filter_pixel(t, x, pa, pb, pc) : 0u;
+            uint32_t run;
+            const uint32_t kind = token_of(pix, px, npix, lane, &last[t], &run);
+            acc[t] += kind == 1u ? literal_bits(pix) : kind == 2u ? match3_bits(3u * run) : 0u;
+        }
+    }
+    // a lane's sum is at most 4 x 27 bits, the wavefront's 256 x 27 < 2^16: four of them in one 64-bit word
+    uint64_t lo = (uint64_t)acc[0] | ((uint64_t)acc[1] << 16) | ((uint64_t)acc[2] << 32) | ((uint64_t)acc[3] << 48);
+    uint32_t hi = acc[4];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo += __shfl_xor(lo, d);
+        hi += (uint32_t)__shfl_xor((int)hi, d);
+    }
+    if (lane < 5u) {
+        // maray_png_compress's arithmetic: the block header's 3 bits, the filter byte's 8 (every type is a literal below 144),
+        // the tokens; then end-of-block, the stored block's 3 bits, zeros to the byte, 00 00 FF FF
+        const uint32_t tokens = lane < 4u ? (uint32_t)(lo >> (16u * lane)) & 0xFFFFu : hi;
+        const uint32_t bits = 3u + 8u * first + tokens;
+        uint32_t *out = a.cost + (size_t)seg * 10u + 2u * lane;
+        out[0] = ((bits + 7u + 3u + 7u) >> 3) + 4u;
+        out[1] = bits;
+    }
+}
+
+__global__ __launch_bounds__(FC_BLOCK) void maray_png_filter_pick(const PngBandArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t row = blockIdx.x * FC_WAVES + (threadIdx.x >> 6);
+    if (row >= a.rows) return;
+    uint32_t sum[10] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};     // (a row's bits fit 32 bits: 27 per pixel at most)
+    for (uint32_t s = lane; s < a.nseg; s += 64u) {
+        const uint32_t *c = a.cost + ((size_t)row * a.nseg + s) * 10u;
+#pragma unroll
+        for (int i = 0; i < 10; i++) sum[i] += c[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum[i] += (uint32_t)__shfl_xor((int)sum[i], d);
+    }
+    if (lane == 0u) {
+        uint32_t best = 0u, best_bytes = sum[0], best_bits = sum[1];
+#pragma unroll
+        for (uint32_t t = 1u; t < 5u; t++) {                // the smallest (bytes, bits, t): a later type must be strictly better
+            const uint32_t by = sum[2 * t], bi = sum[2 * t + 1];
+            if (by < best_bytes || (by == best_bytes && bi < best_bits)) { best = t; best_bytes = by; best_bits = bi; }
+        }
+        a.row_filter[row] = (uint8_t)best;
+    }
+}
+
 void check_band(const PngBandArgs &a)
 {
     const bool dyn = a.codes == MARAY_PNG_CODES_DYNAMIC;
+    if (a.filter > MARAY_PNG_FILTER_PAETH || (a.filter && !a.row_filter) || (a.filter == MARAY_PNG_FILTER_ADAPTIVE && (!a.cost || ((uintptr_t)a.cost & 3))))
+        throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad filter arguments"};
     if (!a.src || !a.slots || !a.lens || !a.adler || !a.offsets || !a.stream || !a.totals || !a.w || !a.rows ||
         (a.codes != MARAY_PNG_CODES_FIXED && !dyn) || (dyn && (!a.hist || a.header_bits > PNG_DYN_HEADER_MAX_BITS || ((uintptr_t)a.stream & 15))) ||
         a.nseg != png_row_segments(a.w) || a.slot_bytes != (dyn ? png_slot_bytes_dyn(a.w) : png_slot_bytes(a.w)) ||
@@ -537,19 +785,41 @@ void check_band(const PngBandArgs &a)
 
 }   // namespace
 
+namespace {
+// the rows' types into a.row_filter, in front of the band's first pass over its pixels
+void band_filter(const PngBandArgs &a, hipStream_t st)
+{
+    if (a.filter != MARAY_PNG_FILTER_ADAPTIVE) {            // a forced type: PNG type filter - 1 in every row
+        HIP_TRY(hipMemsetAsync(a.row_filter, (int)(a.filter - 1u), a.rows, st));
+        return;
+    }
+    hipLaunchKernelGGL(maray_png_filter_cost, dim3((a.n_segs + FC_WAVES - 1) / FC_WAVES), dim3(FC_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(maray_png_filter_pick, dim3((a.rows + FC_WAVES - 1) / FC_WAVES), dim3(FC_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+}
+}   // namespace
+
 void png_band_compress(const PngBandArgs &a, hipStream_t st)
 {
     check_band(a);
     (void)hipGetLastError();
+    const bool f = a.filter != MARAY_PNG_FILTER_NONE;
+    if (f && (a.codes != MARAY_PNG_CODES_DYNAMIC || !a.table)) band_filter(a, st);      // (a dynamic band's second pass finds them set)
+    const dim3 segs((a.n_segs + PC_WAVES - 1) / PC_WAVES);
     if (a.codes == MARAY_PNG_CODES_DYNAMIC && !a.table) {
         const uint32_t blocks = png_hist_blocks(a.n_segs);
-        hipLaunchKernelGGL(maray_png_histogram, dim3(blocks), dim3(HIST_BLOCK), 0, st, a);
+        if (f) hipLaunchKernelGGL(maray_png_histogram_filtered, dim3(blocks), dim3(HIST_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL(maray_png_histogram, dim3(blocks), dim3(HIST_BLOCK), 0, st, a);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(maray_png_histogram_sum, dim3(1), dim3(HIST_SUM_BLOCK), 0, st, a.hist, blocks);
-    } else if (a.codes == MARAY_PNG_CODES_DYNAMIC)
-        hipLaunchKernelGGL(maray_png_compress_dyn, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+    } else if (a.codes == MARAY_PNG_CODES_DYNAMIC) {
+        if (f) hipLaunchKernelGGL(maray_png_compress_dyn_filtered, segs, dim3(PC_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL(maray_png_compress_dyn, segs, dim3(PC_BLOCK), 0, st, a);
+    } else if (f)
+        hipLaunchKernelGGL(maray_png_compress_filtered, segs, dim3(PC_BLOCK), 0, st, a);
     else
-        hipLaunchKernelGGL(maray_png_compress, dim3((a.n_segs + PC_WAVES - 1) / PC_WAVES), dim3(PC_BLOCK), 0, st, a);
+        hipLaunchKernelGGL(maray_png_compress, segs, dim3(PC_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
 }
 

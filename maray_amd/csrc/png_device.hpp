@@ -79,10 +79,21 @@ struct PngBandArgs {
     uint32_t header_bits;           // bits of the block header in front of the first token; 0 while the band is being counted
     uint32_t *hist;                 // png_hist_blocks(n_segs) x PNG_HIST_STRIDE partial counts, then PNG_HIST_STRIDE words: their sums
     const uint32_t *table;          // PNG_LIT_SYMS words: reversed code | length << 16; null while the band is being counted
+    // Row filters (MARAY_PNG_FILTER_*; with MARAY_PNG_FILTER_NONE all zero, and the kernels launched are the ones above)
+    uint32_t filter;                // MARAY_PNG_FILTER_*: the option, not a PNG filter type
+    uint8_t *row_filter;            // per row of the band: its PNG filter type 0 .. 4
+    const unsigned char *above;     // the 3 w bytes of the row above the band's first row; null: the band starts at row 0
+    uint32_t *cost;                 // MARAY_PNG_FILTER_ADAPTIVE: per segment and type t, [10 seg + 2 t] = the bytes and
+                                    // [10 seg + 2 t + 1] = the token bits of the segment as a fixed-Huffman segment under t
 };
 // The launchers dispatch on a.codes.  FIXED: maray_png_compress, maray_png_scan, maray_png_gather.  DYNAMIC: compress is
 // maray_png_histogram + maray_png_histogram_sum while a.table is null and maray_png_compress_dyn once it is set; scan is
 // maray_png_scan; gather is maray_png_zero + maray_png_gather_bits.
+// With a.filter set, png_band_compress first fills a.row_filter in the band's first pass (FIXED: the only one; DYNAMIC: the
+// counting pass) -- ADAPTIVE: maray_png_filter_cost (per segment, the five types' costs) and maray_png_filter_pick (per row,
+// the smallest (bytes, bits, type)); a forced type: the constant -- and launches the filtered forms
+// maray_png_compress_filtered, maray_png_histogram_filtered and maray_png_compress_dyn_filtered.  Scan and gather are the
+// same kernels.
 void png_band_compress(const PngBandArgs &a, hipStream_t st);
 void png_band_scan(const PngBandArgs &a, hipStream_t st);
 void png_band_gather(const PngBandArgs &a, hipStream_t st);
@@ -112,6 +123,8 @@ struct PngEncoder {
     unsigned char *stream = nullptr; size_t stream_cap = 0;
     unsigned char *meta = nullptr; size_t meta_cap = 0;         // lens, adler, offsets, totals
     unsigned char *raster = nullptr; size_t raster_cap = 0;     // a band's rows, for the rendering entry points
+    unsigned char *filt = nullptr; size_t filt_cap = 0;         // row filters: the rows' types, then the segments' costs
+    unsigned char *carry = nullptr; size_t carry_cap = 0;       // row filters: the row above the band being rendered
     unsigned char *staging = nullptr; size_t staging_cap = 0;   // pinned host
     uint64_t *h_totals = nullptr;                                // pinned host, 3 words
 
@@ -122,11 +135,15 @@ struct PngEncoder {
     uint32_t band_rows(uint32_t w, uint32_t codes = MARAY_PNG_CODES_FIXED) const;
     unsigned char *band_buffer(size_t bytes);                    // `raster`, grown to hold `bytes` (the animation writer's crops)
     // rows x w pixels at d_rgb8 (device memory, any alignment), enqueued on st and waited for; appends to `out`
-    void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out, uint32_t codes = MARAY_PNG_CODES_FIXED);
-    // rows [y0, y1) band by band: render(b0, b1, d8, st) enqueues the rows' RGB8 into d8 on st
+    // filter: MARAY_PNG_FILTER_*; above: the 3 w bytes of the row above the first one in device memory (null: that is row 0 of
+    // the image); later bands of the call read the row above them in d_rgb8 itself
+    void encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, hipStream_t st, PngPiece &out, uint32_t codes = MARAY_PNG_CODES_FIXED,
+                     uint32_t filter = MARAY_PNG_FILTER_NONE, const unsigned char *above = nullptr);
+    // rows [y0, y1) band by band: render(b0, b1, d8, st) enqueues the rows' RGB8 into d8 on st.  With a filter (y0 = 0 only)
+    // the last row of a band is kept in `carry` for the next one.
     void encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,
                          const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out,
-                         uint32_t codes = MARAY_PNG_CODES_FIXED);
+                         uint32_t codes = MARAY_PNG_CODES_FIXED, uint32_t filter = MARAY_PNG_FILTER_NONE);
 };
 
 // An encoder of `device`: one an earlier call left, or a new one (MARAY_PNG_BAND_ROWS is read here: a kept encoder made
@@ -156,7 +173,9 @@ std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<cons
 // *stream_bytes = the bytes of the gathered stream.
 // With DYNAMIC codes the six kernels of a band whose code is fitted once, before the timed loop (the host's round trip is
 // not a kernel); *stream_bytes = the bytes of the band's piece.
+// With a filter the kernels that set the rows' types are timed with the rest.
 float png_time_kernels(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, int reps, uint64_t *stream_bytes,
-                       uint32_t codes = MARAY_PNG_CODES_FIXED);
+                       uint32_t codes = MARAY_PNG_CODES_FIXED, uint32_t filter = MARAY_PNG_FILTER_NONE);
+inline bool png_filter_known(uint32_t f) { return f <= MARAY_PNG_FILTER_PAETH; }
 
 }   // namespace maray
