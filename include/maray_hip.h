@@ -710,6 +710,67 @@ int maray_hip_time_frame_delta_copy(int device, uint32_t w, uint32_t h, int reps
 int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
                         uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path);
 
+/* ---- raw video (an animation as YUV4MPEG2: RGB -> Y'CbCr on the device) ----------------------------------------------
+ * What a video encoder reads (ffmpeg, x264, SVT-AV1, aomenc): uncompressed planar Y'CbCr behind a one-line text header.
+ * The conversion runs on the device (maray_rgb_to_ycc), so that 1.5 bytes a pixel cross to the host at 4:2:0, not 3, and
+ * no compressor stands in the way: this path creates no PNG encoder.
+ * Conversion.  Input: a packed RGB8 raster, w x h, row pitch exactly 3 w, at any byte alignment.  Output: three packed
+ * planes one after the other, no padding, at any alignment: Y' (w h bytes), Cb, Cr -- exactly the payload of one Y4M FRAME.
+ *   - sampling: MARAY_YCC_420 (default): Cb and Cr are cw x ch, cw = (w + 1) / 2, ch = (h + 1) / 2 (integer division);
+ *     MARAY_YCC_444: Cb and Cr are w x h;
+ *   - matrix: MARAY_YCC_BT601 (default) or MARAY_YCC_BT709, both limited range.  Coefficient rows (y; cb; cr):
+ *       BT.601: (66, 129, 25; -38, -74, 112; 112, -94, -18)       BT.709: (47, 157, 16; -26, -86, 112; 112, -102, -10)
+ *     (each luma row sums to 220, each chroma row to 0);
+ *   - luma: Y' = ((y . (R, G, B) + 128) >> 8) + 16 for every pixel;
+ *   - chroma at 4:4:4: C = ((c . (R, G, B) + 128) >> 8) + 128;
+ *   - chroma at 4:2:0: Rs, Gs, Bs are the sums over the four pixels (min(2i + a, w - 1), min(2j + b, h - 1)), a, b in {0, 1}
+ *     -- indices are clamped to the image, never to a launch -- and C = ((c . (Rs, Gs, Bs) + 512) >> 10) + 128: chroma is
+ *     sited at the centre of the 2 x 2 block (C420jpeg);
+ *   - >> is an arithmetic shift (floor) of a signed 32-bit value.  Everything is an integer: the planes are the same for
+ *     every launch shape, stream and alignment.  Over all 2^24 colours Y' is in [16, 235] and Cb, Cr in [16, 240] (at 4:2:0
+ *     as well), greys give Cb = Cr = 128 exactly: there is no clamp.  The largest distance from the real-valued definition
+ *     is 0.76 of a code value in Y' and 0.99 in Cb/Cr (BT.601), 0.88 and 1.17 (BT.709).
+ * Container.  One header line, `YUV4MPEG2 W<w> H<h> F<fn>:<fd> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n` (C444 at 4:4:4);
+ * then per frame `FRAME\n` and the planes.  fn:fd = delay_den:delay_num, delay_den = 0 meaning 100 as for the APNG; the
+ * fraction is not reduced.  The file is a function of the frames' rasters, the two delays, the sampling and the matrix alone.
+ * Y4M has no tag for the matrix: the caller tells the consumer which one it chose.
+ * How it runs: two plane buffers on the device and two in pinned host memory; per frame the render (through the context's
+ * device entry points; the shutter's for n_sub > 1), the conversion on the same stream, an event, and the planes' copy on a
+ * copy stream; frame k - 1 is written by the calling thread while frame k renders.  One device per animation.
+ * Errors, before a device is looked for: a null pointer, w = 0 or h = 0, n_frames = 0, delay_num = 0, a delay above 65535, an
+ * unknown sampling, matrix or container, a reserved word that is not 0, n_devices > 1: MARAY_E_ARG; a side above
+ * MARAY_DOMAIN_MAX, 3 w h above 2^30: MARAY_E_LIMIT.  Nothing is launched in those cases. */
+#define MARAY_YCC_420 0u
+#define MARAY_YCC_444 1u
+#define MARAY_YCC_BT601 0u
+#define MARAY_YCC_BT709 1u
+#define MARAY_CONTAINER_APNG 0u
+#define MARAY_CONTAINER_Y4M 1u
+typedef struct maray_ycc_opts { uint32_t sampling, matrix, reserved[6]; } maray_ycc_opts;        /* a null pointer: all zeros */
+typedef struct maray_anim_opts { uint32_t container, sampling, matrix, reserved[5]; } maray_anim_opts;
+/* Bytes of one frame's three planes: w h + 2 cw ch.  Needs no device. */
+int maray_ycc_frame_bytes(uint32_t w, uint32_t h, uint32_t sampling, size_t *out);
+/* The kernel alone: the caller's raster to the caller's planes (maray_ycc_frame_bytes of them), enqueued on `stream` (NULL =
+ * the null stream) of `device`; it does not synchronise. */
+int maray_hip_rgb_to_ycc(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_ycc_opts *opts, void *d_planes, void *stream);
+/* n_frames packed frames, 3 w h bytes apart, already in device memory at any alignment -> a complete Y4M file in malloc'ed
+ * host memory (maray_free): the twin of maray_hip_apng_encode_device. */
+int maray_hip_y4m_encode_device(int device, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t delay_num,
+                                uint32_t delay_den, const maray_ycc_opts *opts, void *stream, uint8_t **out, size_t *n_out);
+/* n_images images of a context as a Y4M file; `values` and n_sub exactly as maray_hip_render_apng takes them. */
+int maray_hip_render_y4m(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                         uint32_t delay_num, uint32_t delay_den, const maray_ycc_opts *opts, uint8_t **out, size_t *n_out);
+/* Measurement: average ms of maray_rgb_to_ycc over a w x h raster of the call's own (maray_hip_time_filter's fill) and, in
+ * the same call, of a device-to-device hipMemcpyAsync that moves as many bytes: 4.5 w h at 4:2:0 and 6 w h at 4:4:4 (a copy
+ * of half as many).  copy_ms_avg may be null. */
+int maray_hip_time_rgb_to_ycc(int device, uint32_t w, uint32_t h, const maray_ycc_opts *opts, int reps, float *ms_avg, float *copy_ms_avg);
+/* maray_gen_animation with a container (maray_gen_opts has no spare word).  a = NULL or a->container = MARAY_CONTAINER_APNG:
+ * maray_gen_animation, byte for byte.  MARAY_CONTAINER_Y4M: the images as one Y4M file, streamed to `path` frame by frame --
+ * host memory is two frames, not the whole file; n_plays and the flag MARAY_ENCODER_DYNAMIC are ignored; an error leaves no
+ * file. */
+int maray_gen_animation_ex(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                           uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const maray_anim_opts *a, const char *path);
+
 /* PNG I/O used by gen and the CLI (`img.save`, `image::open(..).to_rgb8()`). */
 int maray_png_write(const char *path, const uint8_t *rgb8, uint32_t w, uint32_t h);
 int maray_png_read(const char *path, uint8_t **rgb8_out, uint32_t *w, uint32_t *h);   /* free with maray_free */

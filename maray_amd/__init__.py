@@ -9,7 +9,9 @@ from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, EN
                   time_png_encode, time_shutter_reduce, transfer_table, var_id, version,
                   apng_encode_device, frame_delta, gen_animation, time_frame_delta,
                   CODES_DYNAMIC, CODES_FIXED, ENCODER_DYNAMIC, png_dynamic_codes,
-                  PNG_FILTER_ADAPTIVE, PNG_FILTER_AVERAGE, PNG_FILTER_NONE, PNG_FILTER_PAETH, PNG_FILTER_SUB, PNG_FILTER_UP, PngOpts)
+                  PNG_FILTER_ADAPTIVE, PNG_FILTER_AVERAGE, PNG_FILTER_NONE, PNG_FILTER_PAETH, PNG_FILTER_SUB, PNG_FILTER_UP, PngOpts,
+                  CONTAINER_APNG, CONTAINER_Y4M, YCC_420, YCC_444, YCC_BT601, YCC_BT709, AnimOpts, YccOpts, rgb_to_ycc, time_rgb_to_ycc, y4m_encode_device,
+                  ycc_frame_bytes)
 
 __all__ = ['Scene', 'Tape', 'Context', 'PinnedRaster', 'MarayError', 'gen', 'gen_to_image', 'gen_cache_clear', 'gen_cache_info', 'device_count', 'lib', 'lib_path',
            'png_read', 'png_write', 'image_read', 'version', 'var_id', 'Program', 'BACKEND_TAPE', 'BACKEND_TAPE_SMEM', 'BACKEND_JIT', 'BACKEND_AUTO', 'FILTER_BOX', 'FILTER_TENT',
@@ -17,4 +19,6 @@ __all__ = ['Scene', 'Tape', 'Context', 'PinnedRaster', 'MarayError', 'gen', 'gen
            'TRANSFER_NONE', 'TRANSFER_SRGB', 'CtxOpts', 'transfer_table', 'time_shutter_reduce',
            'frame_delta', 'apng_encode_device', 'gen_animation', 'time_frame_delta',
            'CODES_FIXED', 'CODES_DYNAMIC', 'ENCODER_DYNAMIC', 'png_dynamic_codes',
-           'PNG_FILTER_NONE', 'PNG_FILTER_ADAPTIVE', 'PNG_FILTER_SUB', 'PNG_FILTER_UP', 'PNG_FILTER_AVERAGE', 'PNG_FILTER_PAETH', 'PngOpts']
+           'PNG_FILTER_NONE', 'PNG_FILTER_ADAPTIVE', 'PNG_FILTER_SUB', 'PNG_FILTER_UP', 'PNG_FILTER_AVERAGE', 'PNG_FILTER_PAETH', 'PngOpts',
+           'YCC_420', 'YCC_444', 'YCC_BT601', 'YCC_BT709', 'CONTAINER_APNG', 'CONTAINER_Y4M', 'YccOpts', 'AnimOpts', 'ycc_frame_bytes', 'rgb_to_ycc',
+           'y4m_encode_device', 'time_rgb_to_ycc']

@@ -19,11 +19,30 @@ CODES_FIXED, CODES_DYNAMIC = 0, 1       # MARAY_PNG_CODES_*
 # MARAY_PNG_FILTER_*: the device PNG encoder's row filter (png_filter=; `filter` is the reconstruction filter everywhere)
 PNG_FILTER_NONE, PNG_FILTER_ADAPTIVE, PNG_FILTER_SUB, PNG_FILTER_UP, PNG_FILTER_AVERAGE, PNG_FILTER_PAETH = range(6)
 TRANSFER_NONE, TRANSFER_SRGB = 0, 1
+YCC_420, YCC_444 = 0, 1                 # MARAY_YCC_*: the chroma sampling of the raw-video planes
+YCC_BT601, YCC_BT709 = 0, 1             # ... and their matrix (both limited range)
+CONTAINER_APNG, CONTAINER_Y4M = 0, 1    # MARAY_CONTAINER_*: what gen_animation writes
 
 
 class PngOpts(C.Structure):
     """maray_png_opts"""
     _fields_ = [('codes', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+
+
+class YccOpts(C.Structure):
+    """maray_ycc_opts"""
+    _fields_ = [('sampling', C.c_uint32), ('matrix', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+
+
+class AnimOpts(C.Structure):
+    """maray_anim_opts"""
+    _fields_ = [('container', C.c_uint32), ('sampling', C.c_uint32), ('matrix', C.c_uint32), ('reserved', C.c_uint32 * 5)]
+
+
+def _ycc_opts(sampling, matrix):
+    o = YccOpts()
+    o.sampling, o.matrix = sampling, matrix
+    return o
 
 
 def _png_opts(codes, png_filter):
@@ -199,6 +218,12 @@ def lib():
         'maray_hip_time_frame_delta': (C.c_int, [C.c_int, u32, u32, C.c_int, C.POINTER(C.c_float)]),
         'maray_hip_time_frame_delta_copy': (C.c_int, [C.c_int, u32, u32, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         'maray_gen_animation': (C.c_int, [vp, C.POINTER(Texture), u32, C.POINTER(GenOpts), vp, u32, u32, u32, u32, C.c_char_p]),
+        'maray_ycc_frame_bytes': (C.c_int, [u32, u32, u32, C.POINTER(C.c_size_t)]),
+        'maray_hip_rgb_to_ycc': (C.c_int, [C.c_int, vp, u32, u32, C.POINTER(YccOpts), vp, vp]),
+        'maray_hip_y4m_encode_device': (C.c_int, [C.c_int, vp, u32, u32, u32, u32, u32, C.POINTER(YccOpts), vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_y4m': (C.c_int, [vp, u32, u32, vp, u32, u32, u32, u32, C.POINTER(YccOpts), C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_rgb_to_ycc': (C.c_int, [C.c_int, u32, u32, C.POINTER(YccOpts), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        'maray_gen_animation_ex': (C.c_int, [vp, C.POINTER(Texture), u32, C.POINTER(GenOpts), vp, u32, u32, u32, u32, C.POINTER(AnimOpts), C.c_char_p]),
         'maray_png_write': (C.c_int, [C.c_char_p, vp, u32, u32]),
         'maray_png_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
         'maray_image_read': (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
@@ -648,6 +673,18 @@ class Context:
         _check(lib().maray_hip_render_apng(self._h, w, h, vp_, rows // sub, sub, num, den, loops, C.byref(p), C.byref(sz)))
         return _take_bytes(p, sz)
 
+    def render_y4m(self, w, h, frames, sub=1, fps=(25, 1), sampling=YCC_420, matrix=YCC_BT601):
+        """n images as the bytes of one YUV4MPEG2 file, rendered and converted to Y'CbCr planes on the device
+        (maray_hip_render_y4m).  frames, sub, fps: as render_apng; sampling=YCC_444: full-resolution chroma; matrix=YCC_BT709:
+        the other matrix (the file has no tag for it)."""
+        rows, vp_, keep = self._frames(frames)
+        if sub < 1 or rows % sub:
+            raise MarayError(-1, 'render_y4m: frames must hold a whole number of images of %d rows' % sub)
+        num, den = _delay(fps)
+        p, sz = C.c_void_p(), C.c_size_t()
+        _check(lib().maray_hip_render_y4m(self._h, w, h, vp_, rows // sub, sub, num, den, C.byref(_ycc_opts(sampling, matrix)), C.byref(p), C.byref(sz)))
+        return _take_bytes(p, sz)
+
     def render_rows_device(self, w, h, y0, y1, d_rgb8=0, d_rgb64=0, stream=0):
         _check(lib().maray_hip_render_rows_device(self._h, w, h, y0, y1, d_rgb8 or None, d_rgb64 or None, stream or None))
 
@@ -765,8 +802,10 @@ def _delay(fps):
 
 
 def gen_animation(scene, path, frames, fps=(25, 1), loops=0, textures=None, backend=BACKEND_AUTO, n_devices=0, samples=0, shutter=0, spans=None,
-                  filter=FILTER_BOX, transfer=TRANSFER_NONE, codes=CODES_FIXED):
-    """An animation of the scene as one APNG at `path`, rendered and encoded on one device (maray_gen_animation).  frames: an
+                  filter=FILTER_BOX, transfer=TRANSFER_NONE, codes=CODES_FIXED, container=CONTAINER_APNG, sampling=YCC_420, matrix=YCC_BT601):
+    """An animation of the scene as one APNG at `path`, rendered and encoded on one device (maray_gen_animation_ex;
+    container=CONTAINER_Y4M: as one YUV4MPEG2 file of Y'CbCr planes converted on the device and streamed to `path` frame by
+    frame, with sampling=YCC_* and matrix=YCC_*; loops and codes mean nothing there).  frames: an
     (n, P) matrix, one row of values per image and one column per declared parameter, or a dict {name_or_id: sequence} -- the
     parameters it does not name keep their current value.  fps, loops: as Context.render_apng; the other options as gen's
     (shutter=n with spans: every image the mean of n sub-frames around its values); codes=CODES_DYNAMIC: dynamic-Huffman
@@ -795,7 +834,10 @@ def gen_animation(scene, path, frames, fps=(25, 1), loops=0, textures=None, back
         raise MarayError(-1, 'gen_animation: unknown PNG codes')
     go.encoder = ENCODER_DYNAMIC if codes == CODES_DYNAMIC else 0
     num, den = _delay(fps)
-    _check(lib().maray_gen_animation(scene._h, arr, n, C.byref(go), a.ctypes.data if a.size else None, a.shape[0], num, den, loops, os.fsencode(path)))
+    ao = AnimOpts()
+    ao.container, ao.sampling, ao.matrix = container, sampling, matrix
+    _check(lib().maray_gen_animation_ex(scene._h, arr, n, C.byref(go), a.ctypes.data if a.size else None, a.shape[0], num, den, loops, C.byref(ao),
+                                        os.fsencode(path)))
 
 
 def frame_delta(d_prev, d_cur, w, h, device=0, stream=0):
@@ -823,6 +865,37 @@ def time_frame_delta(w, h, device=0, reps=10, with_copy=False):
         _check(lib().maray_hip_time_frame_delta(device, w, h, reps, C.byref(ms)))
         return ms.value
     _check(lib().maray_hip_time_frame_delta_copy(device, w, h, reps, C.byref(ms), C.byref(cp)))
+    return ms.value, cp.value
+
+
+def ycc_frame_bytes(w, h, sampling=YCC_420):
+    """Bytes of one frame's Y', Cb and Cr planes (maray_ycc_frame_bytes); needs no device."""
+    n = C.c_size_t()
+    _check(lib().maray_ycc_frame_bytes(w, h, sampling, C.byref(n)))
+    return n.value
+
+
+def rgb_to_ycc(d_rgb8, w, h, d_planes, sampling=YCC_420, matrix=YCC_BT601, device=0, stream=0):
+    """A packed (h, w, 3) uint8 raster in device memory -> ycc_frame_bytes(w, h, sampling) bytes at d_planes: the Y', Cb and Cr
+    planes one after the other (maray_hip_rgb_to_ycc; both at any alignment).  Enqueued on `stream`: it does not synchronise."""
+    _check(lib().maray_hip_rgb_to_ycc(device, d_rgb8 or None, w, h, C.byref(_ycc_opts(sampling, matrix)), d_planes or None, stream or None))
+
+
+def y4m_encode_device(d_frames, n, w, h, fps=(25, 1), sampling=YCC_420, matrix=YCC_BT601, device=0, stream=0):
+    """n packed (h, w, 3) uint8 frames, 3 w h bytes apart in device memory (any alignment) -> the bytes of a YUV4MPEG2 file,
+    converted on the device (maray_hip_y4m_encode_device); the conversions are enqueued on `stream` and waited for."""
+    num, den = _delay(fps)
+    p, sz = C.c_void_p(), C.c_size_t()
+    _check(lib().maray_hip_y4m_encode_device(device, d_frames or None, n, w, h, num, den, C.byref(_ycc_opts(sampling, matrix)), stream or None,
+                                             C.byref(p), C.byref(sz)))
+    return _take_bytes(p, sz)
+
+
+def time_rgb_to_ycc(w, h, sampling=YCC_420, matrix=YCC_BT601, device=0, reps=10):
+    """(average ms of the conversion kernel over a w x h raster, average ms of a device-to-device copy that moves as many bytes,
+    timed in the same call) (maray_hip_time_rgb_to_ycc)."""
+    ms, cp = C.c_float(), C.c_float()
+    _check(lib().maray_hip_time_rgb_to_ycc(device, w, h, C.byref(_ycc_opts(sampling, matrix)), reps, C.byref(ms), C.byref(cp)))
     return ms.value, cp.value
 
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "apng_device.hpp"
+#include "y4m_device.hpp"
 #include "backend.hpp"
 #include "expr.hpp"
 #include "filter.hpp"
@@ -1110,6 +1111,135 @@ int maray_hip_time_frame_delta_copy(int device, uint32_t w, uint32_t h, int reps
 int maray_hip_time_frame_delta(int device, uint32_t w, uint32_t h, int reps, float *ms_avg)
 {
     return maray_hip_time_frame_delta_copy(device, w, h, reps, ms_avg, nullptr);
+}
+
+// ---- raw video (include/maray_hip.h) ----------------------------------------------------------------------------
+int maray_ycc_frame_bytes(uint32_t w, uint32_t h, uint32_t sampling, size_t *out)
+{
+    return guard([&] {
+        REQUIRE(out, "null argument");
+        *out = 0;
+        REQUIRE(sampling == MARAY_YCC_420 || sampling == MARAY_YCC_444, "unknown Y'CbCr sampling");
+        *out = ycc_frame_bytes(w, h, sampling);
+    });
+}
+
+int maray_hip_rgb_to_ycc(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_ycc_opts *opts, void *d_planes, void *stream)
+{
+    return guard([&] {
+        REQUIRE(d_rgb8 && d_planes, "null argument");
+        uint32_t sampling, matrix;
+        ycc_opts_words(opts, &sampling, &matrix);
+        ycc_check_frame(w, h);
+        const hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess) throw Error{MARAY_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)};
+        rgb_to_ycc((const unsigned char *)d_rgb8, w, h, sampling, matrix, (unsigned char *)d_planes, (hipStream_t)stream);
+    });
+}
+
+// The file of the entry points that return it: malloc'ed once for the whole file where its size is known in front, written by
+// the sink straight from the pinned planes, and handed to the caller as it is (maray_free) -- no second copy of the video.
+extern "C++" {
+struct Y4mFile {
+    uint8_t *p = nullptr; size_t cap = 0, n = 0;
+    ~Y4mFile() { free(p); }
+    void reserve(size_t want) {
+        if (want <= cap) return;
+        uint8_t *q = (uint8_t *)realloc(p, want);
+        if (!q) throw Error{MARAY_E_INTERNAL, "out of memory"};
+        p = q; cap = want;
+    }
+    void put(const void *src, size_t bytes) {
+        if (n + bytes > cap) reserve(std::max(n + bytes, cap + cap / 2));
+        memcpy(p + n, src, bytes);
+        n += bytes;
+    }
+    void hand_over(uint8_t **out, size_t *n_out) { reserve(1); *out = p; *n_out = n; p = nullptr; cap = n = 0; }
+    Y4mWriter::Sink sink() { return [this](const void *src, size_t bytes) { put(src, bytes); }; }
+};
+}
+
+int maray_hip_y4m_encode_device(int device, const void *d_frames, uint32_t n_frames, uint32_t w, uint32_t h, uint32_t delay_num,
+                                uint32_t delay_den, const maray_ycc_opts *opts, void *stream, uint8_t **out, size_t *n_out)
+{
+    return guard([&] {
+        REQUIRE(out && n_out, "null argument");
+        *out = nullptr; *n_out = 0;
+        REQUIRE(d_frames, "null argument");
+        uint32_t sampling, matrix;
+        ycc_opts_words(opts, &sampling, &matrix);
+        y4m_check_timing(n_frames, delay_num, delay_den);
+        ycc_check_frame(w, h);
+        Y4mFile file;
+        Y4mWriter W(device, w, h, n_frames, delay_num, delay_den, sampling, matrix, file.sink());
+        file.reserve(W.header.size() + (size_t)n_frames * (6 + W.frame_bytes));
+        for (uint32_t i = 0; i < n_frames; i++) W.add_frame((const unsigned char *)d_frames + (size_t)i * w * 3 * h, (hipStream_t)stream);
+        W.finish();
+        file.hand_over(out, n_out);
+    });
+}
+
+int maray_hip_render_y4m(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                         uint32_t delay_num, uint32_t delay_den, const maray_ycc_opts *opts, uint8_t **out, size_t *n_out)
+{
+    if (!out || !n_out) return fail(MARAY_E_ARG, "null argument");
+    *out = nullptr; *n_out = 0;
+    Y4mFile file;
+    // (room for the whole file at once where the arguments are in range -- a header line is under 128 bytes; render_y4m_to
+    // checks them)
+    if (n_images && w && h && (uint64_t)w * 3 * h <= YCC_FRAME_MAX_BYTES && (!opts || opts->sampling <= MARAY_YCC_444)) {
+        const int rc = guard([&] { file.reserve(128 + (size_t)n_images * (6 + ycc_frame_bytes(w, h, opts ? opts->sampling : (uint32_t)MARAY_YCC_420))); });
+        if (rc) return rc;
+    }
+    if (const int rc = maray::render_y4m_to(c, w, h, values, n_images, n_sub, delay_num, delay_den, opts, file.sink())) return rc;
+    return guard([&] { file.hand_over(out, n_out); });
+}
+
+// maray_hip_render_y4m into a sink (y4m_device.hpp): maray_gen_animation_ex's way in
+extern "C++" int maray::render_y4m_to(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_images, uint32_t n_sub,
+                                     uint32_t delay_num, uint32_t delay_den, const maray_ycc_opts *opts, const Y4mWriter::Sink &sink)
+{
+    return guard([&] {
+        uint32_t sampling, matrix;
+        ycc_opts_words(opts, &sampling, &matrix);
+        y4m_check_timing(n_images, delay_num, delay_den);
+        ycc_check_frame(w, h);
+        REQUIRE(c && c->backend, "null context");
+        check_rows(w, h, 0, h);
+        check_samples(c, w, h, false, true);
+        // every row of every image, before the first launch
+        const size_t P = c->param_ranges.size() / 2;
+        for (uint32_t i = 0; i < n_images; i++) check_shutter(c, values ? values + (size_t)i * n_sub * P : nullptr, n_sub);
+        int device = 0;
+        {
+            std::lock_guard<std::mutex> lk(g_ctx_device_mutex);
+            auto it = g_ctx_device.find(c);
+            if (it == g_ctx_device.end()) throw Error{MARAY_E_ARG, "unknown context"};
+            device = it->second;
+        }
+        Y4mWriter W(device, w, h, n_images, delay_num, delay_den, sampling, matrix, sink);
+        // (the device's render stream, not one of this call's: the back-end keeps the stream of its last launch)
+        const hipStream_t st = y4m_render_stream(device);
+        struct Drain {
+            hipStream_t st;
+            ~Drain() { (void)hipStreamSynchronize(st); }
+        } drain{st};    // (declared after W: the renders are waited for before the writer's buffers go)
+        for (uint32_t i = 0; i < n_images; i++) {
+            c->backend->render_device_shutter(w, h, RowBlocks::range(0, h), values ? values + (size_t)i * n_sub * P : nullptr, n_sub, W.raster(), st);
+            W.add_frame(W.raster(), st);
+        }
+        W.finish();
+    });
+}
+
+int maray_hip_time_rgb_to_ycc(int device, uint32_t w, uint32_t h, const maray_ycc_opts *opts, int reps, float *ms_avg, float *copy_ms_avg)
+{
+    return guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        uint32_t sampling, matrix;
+        ycc_opts_words(opts, &sampling, &matrix);
+        *ms_avg = rgb_to_ycc_time(device, w, h, sampling, matrix, reps, copy_ms_avg);
+    });
 }
 
 int maray_host_alloc(size_t bytes, void **out)

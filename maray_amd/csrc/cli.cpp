@@ -7,7 +7,9 @@
 // image the mean of N frames whose NAME covers SPAN around its value, averaged on the device), --linear (samples and frames
 // are averaged in linear light: include/maray_hip.h, "transfer"), --encoder {host,device} (who
 // writes the PNG: the host's zlib, or the device encoder, per --animate frame too), --apng (--animate writes ONE file, an APNG
-// encoded on the device frame by frame: include/maray_hip.h, "animation"; --fps N[/D] and --loops N are its timing).
+// encoded on the device frame by frame: include/maray_hip.h, "animation"; --fps N[/D] and --loops N are its timing), --y4m
+// (--animate writes ONE file, a YUV4MPEG2 video whose Y'CbCr planes are converted on the device: include/maray_hip.h, "raw
+// video"; --y4m-sampling and --y4m-matrix choose the planes, --fps the rate).
 // -c/--cpus is parsed and ignored, exactly like the reference (`_cpus`, examples/maray.rs:55).
 #include <cmath>
 #include <cstdio>
@@ -38,7 +40,12 @@ static void usage()
             "      --apng                   With --animate: one file, an animated PNG (APNG) whose frames are encoded on the GPU, of\n"
             "                               every frame after the first only the rectangle that changed; --output takes no `%%d`,\n"
             "                               --gpus must be 1 or absent\n"
-            "      --fps <n[/d]>            --apng: n / d images per second (default: 25)\n"
+            "      --y4m                    With --animate: one file, a YUV4MPEG2 video (what ffmpeg, x264, SVT-AV1 and aomenc read):\n"
+            "                               limited-range Y'CbCr planes converted on the GPU; --output takes no `%%d`, --gpus must be\n"
+            "                               1 or absent, not together with --apng\n"
+            "      --y4m-sampling <s>       --y4m: 420 | 444 (default: 420, chroma sited as in JPEG)\n"
+            "      --y4m-matrix <m>         --y4m: 601 | 709 (default: 601); the file has no tag for it: tell the encoder\n"
+            "      --fps <n[/d]>            --apng, --y4m: n / d images per second (default: 25)\n"
             "      --loops <n>              --apng: how often the animation plays; 0 = for ever (default: 0)\n"
             "      --shutter <name=span>    Motion blur (repeatable): every image is the mean of N frames in which `name` covers\n"
             "                               an interval of width span centred on its value; declares `name` if -p did not\n"
@@ -99,6 +106,9 @@ int main(int argc, char **argv)
     uint32_t shutter_samples = 0;
     bool linear = false;                // --linear
     bool apng = false;                  // --apng
+    bool y4m = false, y4m_words = false;                // --y4m; a --y4m-sampling or --y4m-matrix was given
+    maray_anim_opts ao;
+    memset(&ao, 0, sizeof ao);
     bool png_codes_given = false, dynamic_codes = false;      // --png-codes
     uint32_t fps_num = 25, fps_den = 1, loops = 0;
     maray_gen_opts go;
@@ -129,6 +139,21 @@ int main(int argc, char **argv)
         }
         else if (a == "--linear") linear = true;
         else if (a == "--apng") apng = true;
+        else if (a == "--y4m") y4m = true;
+        else if (a == "--y4m-sampling") {
+            const std::string e = val();
+            y4m_words = true;
+            if (e == "420") ao.sampling = MARAY_YCC_420;
+            else if (e == "444") ao.sampling = MARAY_YCC_444;
+            else { fprintf(stderr, "Error: --y4m-sampling takes 420 or 444, not `%s`\n", e.c_str()); usage(); return 2; }
+        }
+        else if (a == "--y4m-matrix") {
+            const std::string e = val();
+            y4m_words = true;
+            if (e == "601") ao.matrix = MARAY_YCC_BT601;
+            else if (e == "709") ao.matrix = MARAY_YCC_BT709;
+            else { fprintf(stderr, "Error: --y4m-matrix takes 601 or 709, not `%s`\n", e.c_str()); usage(); return 2; }
+        }
         else if (a == "--fps") {
             const std::string f = val();
             char *rest = nullptr;
@@ -215,7 +240,13 @@ int main(int argc, char **argv)
     if (apng && !frames) { fprintf(stderr, "Error: --apng writes an animation: it needs --animate NAME=FROM:TO:FRAMES\n"); return 2; }
     if (apng && output.find('%') != std::string::npos) { fprintf(stderr, "Error: --apng writes one file: --output must not contain a `%%d` conversion\n"); return 2; }
     if (apng && go.n_devices > 1) { fprintf(stderr, "Error: --apng renders and encodes on one device: --gpus must be 1\n"); return 2; }
-    if (frames && !apng && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
+    if (y4m && apng) { fprintf(stderr, "Error: --y4m and --apng both write the animation as one file: choose one\n"); usage(); return 2; }
+    if (y4m_words && !y4m) { fprintf(stderr, "Error: --y4m-sampling and --y4m-matrix choose the planes of a --y4m file: they need --y4m\n"); usage(); return 2; }
+    if (y4m && !frames) { fprintf(stderr, "Error: --y4m writes an animation: it needs --animate NAME=FROM:TO:FRAMES\n"); usage(); return 2; }
+    if (y4m && output.find('%') != std::string::npos) { fprintf(stderr, "Error: --y4m writes one file: --output must not contain a `%%d` conversion\n"); usage(); return 2; }
+    if (y4m && go.n_devices > 1) { fprintf(stderr, "Error: --y4m renders and converts on one device: --gpus must be 1\n"); usage(); return 2; }
+    const bool one_file = apng || y4m;
+    if (frames && !one_file && !numbered(output)) { fprintf(stderr, "Error: --animate writes several images: --output needs one `%%d` conversion, e.g. frame%%03d.png\n"); return 2; }
 
     maray_scene *scene = nullptr;
     if (maray_scene_open(input.c_str(), &scene)) { fprintf(stderr, "Error: %s\n", maray_last_error()); return 1; }
@@ -275,7 +306,7 @@ int main(int argc, char **argv)
     if (!frames) rc = maray_gen(scene, tex.data(), (uint32_t)tex.size(), &go, rep, output.c_str());
     // FROM + i (TO - FROM) / (FRAMES - 1) in f64; the last frame is TO itself (the range's end, whatever the rounding)
     auto frame_value = [&](uint32_t f) { return frames == 1 ? from : f == frames - 1 ? to : from + (double)f * (to - from) / (double)(frames - 1); };
-    if (apng) {
+    if (one_file) {
         // one row of values per image: the animated parameter's, and every other parameter's current value
         uint32_t n_par = 0;
         maray_scene_param_count(scene, &n_par);
@@ -286,9 +317,10 @@ int main(int argc, char **argv)
                 maray_scene_param_info(scene, k, nullptr, nullptr, nullptr, &v);
                 values[(size_t)f * n_par + k] = k == anim_index ? frame_value(f) : v;
             }
-        rc = maray_gen_animation(scene, tex.data(), (uint32_t)tex.size(), &go, values.data(), frames, fps_den, fps_num, loops, output.c_str());
+        ao.container = y4m ? MARAY_CONTAINER_Y4M : MARAY_CONTAINER_APNG;
+        rc = maray_gen_animation_ex(scene, tex.data(), (uint32_t)tex.size(), &go, values.data(), frames, fps_den, fps_num, loops, &ao, output.c_str());
     }
-    for (uint32_t f = 0; !apng && f < frames && !rc; f++) {
+    for (uint32_t f = 0; !one_file && f < frames && !rc; f++) {
         const double v = frame_value(f);
         char path[4096];
         snprintf(path, sizeof path, output.c_str(), (int)f);

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <sys/stat.h>
 #include <list>
 #include <map>
 #include <memory>
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "apng_device.hpp"
+#include "y4m_device.hpp"
 #include "backend.hpp"
 #include "host_pipe.hpp"
 #include "lower.hpp"
@@ -519,12 +521,24 @@ extern "C" int maray_gen(const maray_scene *s, const maray_texture *tex, uint32_
 }
 
 // ---- gen for an animation (include/maray_hip.h, "animation") --------------------------------------------------------
-extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
-                                   uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path)
+// `a` = null: maray_gen_animation; else maray_gen_animation_ex, whose container decides what the rendered images become
+static int gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                         uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const maray_anim_opts *a, const char *path)
 {
     if (!s || !path) return fail_with(MARAY_E_ARG, "null argument");
     if (!n_images) return fail_with(MARAY_E_ARG, "an animation needs at least one image");
     if (delay_num > 65535 || delay_den > 65535) return fail_with(MARAY_E_ARG, "delay_num and delay_den must fit 16 bits");
+    const uint32_t container = a ? a->container : (uint32_t)MARAY_CONTAINER_APNG;
+    if (container != MARAY_CONTAINER_APNG && container != MARAY_CONTAINER_Y4M) return fail_with(MARAY_E_ARG, "unknown animation container");
+    maray_ycc_opts yo;
+    memset(&yo, 0, sizeof yo);
+    if (a) {
+        yo.sampling = a->sampling; yo.matrix = a->matrix;
+        for (uint32_t r : a->reserved) if (r) return fail_with(MARAY_E_ARG, "maray_anim_opts: a reserved word is not 0");
+    }
+    if (yo.sampling != MARAY_YCC_420 && yo.sampling != MARAY_YCC_444) return fail_with(MARAY_E_ARG, "unknown Y'CbCr sampling");
+    if (yo.matrix != MARAY_YCC_BT601 && yo.matrix != MARAY_YCC_BT709) return fail_with(MARAY_E_ARG, "unknown Y'CbCr matrix");
+    if (container == MARAY_CONTAINER_Y4M && !delay_num) return fail_with(MARAY_E_ARG, "a Y4M frame rate is delay_den / delay_num: delay_num must not be 0");
     return gen_guard([&]() -> int {
     // the option words, as gen_to_image checks them
     const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
@@ -543,7 +557,8 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
     if (w > MARAY_DOMAIN_MAX || h > MARAY_DOMAIN_MAX) return fail_with(MARAY_E_LIMIT, "image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " pixels in x or y");
     if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
         return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
-    apng_check_frame(w, h);
+    if (container == MARAY_CONTAINER_Y4M) ycc_check_frame(w, h);
+    else apng_check_frame(w, h);
     uint32_t n_par = 0;
     if (const int rc = maray_scene_param_count(s, &n_par)) return rc;
     if (n_par && !values) return fail_with(MARAY_E_ARG, "null argument: a scene with parameters needs the images' values");
@@ -613,6 +628,30 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
     maray_ctx *ctx = kept.ctx;
     if (!ctx)
         if (const int rc = maray_hip_ctx_create_refined(dev, &prog, &refine, tex, n_tex, &co, &ctx)) return rc;
+    if (container == MARAY_CONTAINER_Y4M) {
+        // streamed: the file is created when the first frame is ready, and does not outlive a failure
+        struct File {
+            const char *path; FILE *f = nullptr; bool failed = false, opened = false;
+            ~File() { if (f) fclose(f); }
+        } out{path};
+        const int rc = render_y4m_to(ctx, w, h, P ? rows.data() : nullptr, n_images, n_sub, delay_num, delay_den, &yo, [&](const void *p, size_t n) {
+            if (!out.f && !out.failed && !(out.f = fopen(out.path, "wb"))) out.failed = true;
+            out.opened = out.opened || out.f;
+            if (out.failed) throw Error{MARAY_E_IO, std::string("cannot create ") + out.path};
+            if (fwrite(p, 1, n, out.f) != n) { out.failed = true; throw Error{MARAY_E_IO, "short write"}; }
+        });
+        if (out.f) { if (fclose(out.f)) out.failed = true; out.f = nullptr; }
+        if (rc || out.failed) {
+            const std::string msg = rc ? maray_last_error() : "short write";
+            struct stat sb;         // (what this call created, and only a regular file: never a device or a pipe it was given)
+            if (out.opened && !stat(path, &sb) && S_ISREG(sb.st_mode)) remove(path);
+            maray_hip_ctx_free(ctx);
+            return fail_with(rc ? rc : MARAY_E_IO, msg);
+        }
+        gen_cache_give(*entry, dev, ctx, kept.ctx ? kept.hint_mpixels : co.hint_mpixels);
+        set_last_error("");
+        return MARAY_OK;
+    }
     uint8_t *bytes = nullptr;
     size_t n_bytes = 0;
     // the encoder word is ignored but for the flag: dynamic codes for every frame
@@ -629,4 +668,18 @@ extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *te
     set_last_error("");
     return MARAY_OK;
     });
+}
+
+extern "C" int maray_gen_animation(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                                   uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const char *path)
+{
+    return gen_animation(s, tex, n_tex, opts, values, n_images, delay_num, delay_den, n_plays, nullptr, path);
+}
+
+extern "C" int maray_gen_animation_ex(const maray_scene *s, const maray_texture *tex, uint32_t n_tex, const maray_gen_opts *opts, const double *values,
+                                      uint32_t n_images, uint32_t delay_num, uint32_t delay_den, uint32_t n_plays, const maray_anim_opts *a,
+                                      const char *path)
+{
+    static const maray_anim_opts none = {MARAY_CONTAINER_APNG, MARAY_YCC_420, MARAY_YCC_BT601, {0, 0, 0, 0, 0}};
+    return gen_animation(s, tex, n_tex, opts, values, n_images, delay_num, delay_den, n_plays, a ? a : &none, path);
 }
