@@ -457,6 +457,26 @@ int maray_hip_debug_guard_words(maray_ctx *c, uint64_t *words, size_t cap, size_
 /* The same for the words the most recent launch READ: those of maray_hip_debug_guard_words, which the ROW pass and the second
  * bounds wrote, until the set has been through its census; from then on what maray_jit_census_apply left of them. */
 int maray_hip_debug_census_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
+/* The cover of guarded ORs (MARAY_BACKEND_JIT, wherever a census is taken).  A boolean OR of guarded shapes that the census may
+ * decide gets a cover bit: a bit of the last guard word that no guard uses (never a word more; a program without free bits
+ * gets none).  Behind a set's census maray_jit_cover -- the PIXEL kernel's text without its stores, over the census'd words --
+ * records per rectangle whether the OR of the shapes that read no parameter the ROW section does not read and hold no Sin that
+ * may defer its tile is 1 on every pixel inside the picture; maray_jit_cover_apply writes a third table of words in which such
+ * a rectangle has its cover bit set and those of the OR's eligible guard bits cleared that no other reduction has a leaf on.  A set with at least one cover bit is rendered by
+ * maray_jit_pixels_cov, maray_jit_pixels with one scalar test per such OR: bit set, the OR is all-ones and no shape is entered.
+ * Once per filling of a set, like the census.  MARAY_JIT_GUARD_COVER=0 in the environment when the context is created: none of
+ * it (rasters are identical either way; not part of a code key).
+ * maray_hip_cover_count: maray_jit_cover launches the context has enqueued.
+ * maray_jit_cover_bits: the plan as int32 values: n, then per OR with a bit: its bit, its root op, its number of guarded
+ * leaves, and per leaf: its last op, its guard bit, 1 if the measurement leaves it out (tainted), 1 if its bit is cleared under
+ * a cover bit (census-eligible).  At most `cap` values are written, *n_values = how many there are.
+ * maray_jit_source_cover: the three kernels' source ("" when the program gets no bit; free with maray_free).
+ * maray_hip_debug_cover_words: like maray_hip_debug_census_words; the third table where the most recent launch read it.
+ * maray_jit_cover_bits and maray_jit_source_cover need no GPU. */
+int maray_hip_cover_count(const maray_ctx *c, uint64_t *cover_launches);
+int maray_jit_cover_bits(const maray_program *prog, int32_t *values, uint32_t cap, uint32_t *n_values);
+int maray_jit_source_cover(const maray_program *prog, char **src_out);
+int maray_hip_debug_cover_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

@@ -181,6 +181,10 @@ def lib():
         'maray_jit_source_census': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
         'maray_hip_debug_guard_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
         'maray_hip_debug_census_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
+        'maray_hip_cover_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_jit_cover_bits': (C.c_int, [C.POINTER(Program), vp, u32, C.POINTER(u32)]),
+        'maray_jit_source_cover': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
+        'maray_hip_debug_cover_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
         'maray_hip_ctx_free': (None, [vp]),
         'maray_hip_render_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
         'maray_hip_render_tiles': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, TILE_FN, vp]),
@@ -505,6 +509,35 @@ class Tape:
         finally:
             lib().maray_free(p)
 
+    def cover_plan(self):
+        """maray_jit_cover_bits: the boolean ORs of guarded shapes that get a cover bit, a list of dicts {bit, root, leaves}, leaves
+        = a list of (last op, guard bit, tainted, eligible).  [] when the program gets none."""
+        n = C.c_uint32()
+        _check(lib().maray_jit_cover_bits(C.byref(self.program), None, 0, C.byref(n)))
+        v = np.zeros(n.value, np.int32)
+        _check(lib().maray_jit_cover_bits(C.byref(self.program), v.ctypes.data, n.value, C.byref(n)))
+        v, out, at = [int(q) for q in v], [], 1
+        for _ in range(v[0]):
+            bit, root, nl = v[at:at + 3]
+            at += 3
+            out.append({'bit': bit, 'root': root, 'leaves': [(v[at + 4 * k], v[at + 4 * k + 1], bool(v[at + 4 * k + 2]), bool(v[at + 4 * k + 3])) for k in range(nl)]})
+            at += 4 * nl
+        return out
+
+    def cover_bits(self):
+        """The cover bits of the program (positions in a rectangle's guard words; none of them is a guard's), one per OR of cover_plan()."""
+        return [r['bit'] for r in self.cover_plan()]
+
+    @property
+    def jit_source_cover(self):
+        """Source of maray_jit_pixels_cov, maray_jit_cover and maray_jit_cover_apply; '' when the program gets no cover bit."""
+        p = C.c_void_p()
+        _check(lib().maray_jit_source_cover(C.byref(self.program), C.byref(p)))
+        try:
+            return C.string_at(p).decode()
+        finally:
+            lib().maray_free(p)
+
     def refine_arrays(self):
         """(consts, ops, n_slots) of the REFINE section as numpy copies; None when the program has none."""
         r = self.refine
@@ -722,6 +755,22 @@ class Context:
         n = C.c_uint64()
         _check(lib().maray_hip_census_count(self._h, C.byref(n)))
         return n.value
+
+    @property
+    def cover_count(self):
+        """maray_jit_cover launches this context has enqueued so far (maray_hip_cover_count)."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_cover_count(self._h, C.byref(n)))
+        return n.value
+
+    def debug_cover_words(self):
+        """Test access (maray_hip_debug_cover_words): like debug_census_words(); where the last launch ran maray_jit_pixels_cov, the
+        words with cover bits that it read."""
+        n, per = C.c_size_t(), C.c_uint32()
+        _check(lib().maray_hip_debug_cover_words(self._h, None, 0, C.byref(n), C.byref(per)))
+        out = np.zeros(n.value, np.uint64)
+        _check(lib().maray_hip_debug_cover_words(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(per)))
+        return out.reshape(-1, per.value)
 
     def debug_guard_words(self):
         """Test access (maray_hip_debug_guard_words): the guard words of the set the last launch used, (rectangles, words per

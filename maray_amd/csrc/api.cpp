@@ -1524,6 +1524,49 @@ int maray_hip_debug_census_words(maray_ctx *c, uint64_t *words, size_t cap, size
     });
 }
 
+int maray_hip_cover_count(const maray_ctx *c, uint64_t *cover_launches)
+{
+    return guard([&] { REQUIRE(c && c->backend && cover_launches, "null argument"); *cover_launches = c->backend->cover_count(); });
+}
+
+int maray_jit_cover_bits(const maray_program *prog, int32_t *values, uint32_t cap, uint32_t *n_values)
+{
+    return guard([&] {
+        REQUIRE(prog && n_values && (values || !cap), "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        const CoverPlan cp = jit_cover_plan(loaded);
+        std::vector<int32_t> v{(int32_t)cp.reds.size()};
+        for (const CoverPlan::Red &r : cp.reds) {
+            v.insert(v.end(), {r.bit, (int32_t)r.root, (int32_t)r.leaf_end.size()});
+            for (size_t k = 0; k < r.leaf_end.size(); k++) v.insert(v.end(), {(int32_t)r.leaf_end[k], (int32_t)r.leaf_bit[k], (int32_t)r.leaf_taint[k], (int32_t)r.leaf_eligible[k]});
+        }
+        *n_values = (uint32_t)v.size();
+        for (uint32_t j = 0; j < v.size() && j < cap; j++) values[j] = v[j];
+    });
+}
+
+int maray_jit_source_cover(const maray_program *prog, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        const std::string s = jit_source_cover(loaded);
+        *src_out = (char *)malloc(s.size() + 1);
+        REQUIRE(*src_out, "out of memory");
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
+int maray_hip_debug_cover_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend && n_words && words_per_rect && (words || !cap), "null argument");
+        *n_words = c->backend->debug_cover_words(words, cap, words_per_rect);
+    });
+}
+
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }
 
 int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels)

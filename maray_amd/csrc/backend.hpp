@@ -45,6 +45,10 @@ struct Backend {
     virtual size_t debug_guard_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // ... and the words the last launch read: those with the bits its set's census cleared, where it has been through one (maray_hip_debug_census_words)
     virtual size_t debug_census_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
+    // maray_jit_cover launches enqueued so far (maray_hip_cover_count), and the words the last launch read, cover bits included
+    // where it ran maray_jit_pixels_cov (maray_hip_debug_cover_words)
+    virtual uint64_t cover_count() const { return 0; }
+    virtual size_t debug_cover_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
@@ -99,6 +103,20 @@ std::string jit_source_census(const maray_program &prog, std::vector<uint64_t> *
 // its code object (null when the source is empty): a module and a cache entry of its own, like jit_code_refine's
 struct JitCensusCode { std::vector<char> code; std::vector<uint64_t> eligible; };
 std::shared_ptr<const JitCensusCode> jit_code_census(const maray_program &prog);
+// The cover bits of a program (maray_jit_cover_bits): per boolean reduction the census may decide, one free bit of the last
+// guard word that says "this OR of shapes is 1 on every pixel of the rectangle"; its guarded leaves (their last op, their guard
+// bit, tainted: not counted by the measurement, eligible: cleared where the cover bit is set)
+struct CoverPlan {
+    struct Red { int32_t bit = -1; uint32_t root = 0; std::vector<uint32_t> leaf_end, leaf_bit; std::vector<uint8_t> leaf_taint, leaf_eligible; };
+    std::vector<Red> reds;
+    uint32_t n_words = 0;               // guard words per rectangle
+};
+CoverPlan jit_cover_plan(const maray_program &prog);
+// maray_jit_pixels_cov + maray_jit_cover + maray_jit_cover_apply (one module); "" when the program gets no cover bit
+std::string jit_source_cover(const maray_program &prog, CoverPlan *plan = nullptr, int min_waves = 0);
+// its code object (null when the source is empty): a module and a cache entry of its own (<key>.mrcv), like jit_code_census'
+struct JitCoverCode { std::vector<char> code; uint32_t n_cover = 0; };      // n_cover: reductions with a bit (2 flag bytes each per rectangle)
+std::shared_ptr<const JitCoverCode> jit_code_cover(const maray_program &prog);
 std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
 std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error

@@ -197,6 +197,8 @@ struct FilterBackend final : Backend {
     uint64_t census_count() const override { return inner->census_count(); }
     size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_guard_words(words, cap, per_rect); }
     size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_census_words(words, cap, per_rect); }
+    uint64_t cover_count() const override { return inner->cover_count(); }
+    size_t debug_cover_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_cover_words(words, cap, per_rect); }
 };
 
 }   // namespace

@@ -48,8 +48,10 @@ struct RowTables {
     unsigned *order = nullptr; size_t order_cap = 0;          // the launch order computed from gbits (maray_jit_order)
     unsigned char *hits = nullptr; size_t hits_cap = 0;       // the census's flags, 64 per guard word (maray_jit_census)
     unsigned long long *cbits = nullptr; size_t cbits_cap = 0;      // gbits with the bits the census cleared: what the launches of a set read once it is through (maray_jit_census_apply)
+    unsigned long long *vbits = nullptr; size_t vbits_cap = 0;      // cbits with cover bits in place of the leaves of ORs that are 1 on every pixel of a rectangle (maray_jit_cover_apply)
+    unsigned char *cflags = nullptr; size_t cflags_cap = 0;         // the cover's flags, 2 per rectangle and reduction with a bit (maray_jit_cover)
     void release() {
-        (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order); (void)hipFree(hits); (void)hipFree(cbits);
+        (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order); (void)hipFree(hits); (void)hipFree(cbits); (void)hipFree(vbits); (void)hipFree(cflags);
         *this = RowTables{};
     }
 };
@@ -75,6 +77,24 @@ struct JitBackend final : Backend {
     // the census module's parameter table is not among d_par: it is written by the launch that takes a census, not by every
     // frame of an animation (a copy per module and frame is what a host-bound shutter waits for)
     hipDeviceptr_t d_par_census = nullptr;
+    // maray_jit_cover + maray_jit_cover_apply + maray_jit_pixels_cov (jit_source_cover): the cover is taken once per kept filling
+    // of a set, behind its census; a set in which it set at least one bit is rendered by maray_jit_pixels_cov over vbits
+    std::shared_ptr<const JitCoverCode> code_cover;
+    hipModule_t mod_cover = nullptr;
+    hipFunction_t f_cover = nullptr, f_cover_apply = nullptr, f_pix_cov = nullptr;
+    bool cover_on = true;               // MARAY_JIT_GUARD_COVER=0: none of this (read once, when the context is created; in no code key)
+    uint64_t n_cover = 0;
+    // How many cover bits a set's apply kernel set: counted on the device, copied behind the kernel into pinned memory and read
+    // by the first later launch that finds the copy complete (an event per set, queried, never waited for).  Until then, and
+    // when the count is 0, the set's launches are what they were: maray_jit_pixels over cbits.
+    enum CoverState : uint8_t { COVER_NONE = 0, COVER_PENDING, COVER_SOME, COVER_EMPTY };
+    CoverState cover_state[RowReuse::N_SETS] = {};
+    hipEvent_t cover_ev[RowReuse::N_SETS] = {};
+    unsigned *d_cover_n = nullptr, *h_cover_n = nullptr;     // one word per set
+    // the cover module's parameter table: written when it is behind the values a launch of one of its kernels renders with
+    hipDeviceptr_t d_par_cover = nullptr;
+    uint64_t par_serial = 1, par_cover_serial = 0;
+    bool last_cov = false;              // the most recent launch ran maray_jit_pixels_cov over vbits
     uint32_t ss = 1;                    // samples per output pixel and axis: > 1 launches maray_jit_pixels_ss (launch_ss)
     std::shared_ptr<const std::vector<char>> code_ss;
     hipModule_t mod_ss = nullptr;
@@ -117,6 +137,10 @@ struct JitBackend final : Backend {
         if (mod_rows) (void)hipModuleUnload(mod_rows);
         if (mod_refine) (void)hipModuleUnload(mod_refine);
         if (mod_census) (void)hipModuleUnload(mod_census);
+        if (mod_cover) (void)hipModuleUnload(mod_cover);
+        for (hipEvent_t e : cover_ev) if (e) (void)hipEventDestroy(e);
+        (void)hipFree(d_cover_n);
+        if (h_cover_n) (void)hipHostFree(h_cover_n);
         if (mod_ss) (void)hipModuleUnload(mod_ss);
         (void)hipFree(d_flags);
         (void)hipFree(d_tex);
@@ -176,11 +200,18 @@ struct JitBackend final : Backend {
         std::future<std::shared_ptr<const JitCensusCode>> census_code;
         if (census_on && reuse.enabled && ss == 1 && prog.n_row_ops)
             census_code = std::async(std::launch::async, [&prog] { return jit_code_census(prog); });
+        // ... and the fifth, wherever a census is taken
+        if (const char *e_ = getenv("MARAY_JIT_GUARD_COVER")) if (e_[0] == '0') cover_on = false;
+        std::future<std::shared_ptr<const JitCoverCode>> cover_code;
+        if (cover_on && census_code.valid())
+            cover_code = std::async(std::launch::async, [&prog] { return jit_code_cover(prog); });
         try { code = jit_code_for(prog); }               // built by the first context of the process, or read from the cache
-        catch (...) { if (refine_code.valid()) refine_code.wait(); if (census_code.valid()) census_code.wait(); throw; }
+        catch (...) { if (refine_code.valid()) refine_code.wait(); if (census_code.valid()) census_code.wait(); if (cover_code.valid()) cover_code.wait(); throw; }
         try { if (refine_code.valid()) code_refine = refine_code.get(); }
-        catch (...) { if (census_code.valid()) census_code.wait(); throw; }
-        if (census_code.valid()) code_census = census_code.get();
+        catch (...) { if (census_code.valid()) census_code.wait(); if (cover_code.valid()) cover_code.wait(); throw; }
+        try { if (census_code.valid()) code_census = census_code.get(); }
+        catch (...) { if (cover_code.valid()) cover_code.wait(); throw; }
+        if (cover_code.valid()) code_cover = cover_code.get();
         lap("code objects");
         HIP_TRY(hipModuleLoadData(&mod, code->pix.data()));
         HIP_TRY(hipModuleGetFunction(&f_pix, mod, "maray_jit_pixels"));
@@ -214,17 +245,26 @@ struct JitBackend final : Backend {
                 HIP_TRY(hipModuleGetFunction(&f_census_apply, mod_census, "maray_jit_census_apply"));
                 lap("load CENSUS module");
             }
+            if (code_cover && f_census) {
+                HIP_TRY(hipModuleLoadData(&mod_cover, code_cover->code.data()));
+                HIP_TRY(hipModuleGetFunction(&f_cover, mod_cover, "maray_jit_cover"));
+                HIP_TRY(hipModuleGetFunction(&f_cover_apply, mod_cover, "maray_jit_cover_apply"));
+                HIP_TRY(hipModuleGetFunction(&f_pix_cov, mod_cover, "maray_jit_pixels_cov"));
+                HIP_TRY(hipMalloc((void **)&d_cover_n, RowReuse::N_SETS * sizeof(unsigned)));
+                HIP_TRY(hipHostMalloc((void **)&h_cover_n, RowReuse::N_SETS * sizeof(unsigned), hipHostMallocDefault));
+                lap("load COVER module");
+            }
         }
         if (prog.n_params) {
             param_values.assign(prog.n_params, NAN);
-            for (hipModule_t m : {mod, mod_rows, mod_ss, mod_refine, mod_census}) {
+            for (hipModule_t m : {mod, mod_rows, mod_ss, mod_refine, mod_census, mod_cover}) {
                 if (!m) continue;
                 hipDeviceptr_t p = nullptr;
                 size_t bytes = 0;
                 HIP_TRY(hipModuleGetGlobal(&p, &bytes, m, "mr_par_tab"));
                 if (bytes != (size_t)prog.n_params * sizeof(double)) throw Error{MARAY_E_INTERNAL, "parameter table of a module has another size than the program"};
                 HIP_TRY(hipMemcpyHtoD(p, param_values.data(), bytes));          // NaN until set
-                if (m == mod_census) d_par_census = p; else d_par.push_back(p);
+                if (m == mod_census) d_par_census = p; else if (m == mod_cover) d_par_cover = p; else d_par.push_back(p);
             }
             ring.init(prog.n_params);
             P.param_ranges = nullptr;
@@ -286,7 +326,19 @@ struct JitBackend final : Backend {
         for (hipDeviceptr_t p : d_par) HIP_TRY(hipMemcpyHtoDAsync(p, slot, bytes, st));
         ring.sent(st);
         params_dirty = false;
+        par_serial++;
         return true;
+    }
+
+    // the cover module's table, in front of a launch of one of its kernels on `st`, if it is behind the context's values
+    void send_params_cover(hipStream_t st) {
+        if (!d_par_cover || par_cover_serial == par_serial) return;
+        double *slot = ring.take();
+        const size_t bytes = param_values.size() * sizeof(double);
+        memcpy(slot, param_values.data(), bytes);
+        HIP_TRY(hipMemcpyHtoDAsync(d_par_cover, slot, bytes, st));
+        ring.sent(st);
+        par_cover_serial = par_serial;
     }
 
     // The set of ROW tables a launch reads, filled by maray_jit_rows on `st` unless a set already holds the outputs of this
@@ -317,10 +369,13 @@ struct JitBackend final : Backend {
         const size_t od_n = want_order ? rows_total : 0;
         const size_t hb_n = want_census ? gb_n * 64 : 0;           // a flag per guard bit
         const size_t cb_n = want_census ? gb_n : 0;                // ... and the words the census leaves
+        const size_t vb_n = want_census && f_cover ? gb_n : 0;     // ... and the cover; its flags
+        const size_t cf_n = vb_n ? gb_n / std::max<uint32_t>(n_gwords, 1) * 2 * code_cover->n_cover : 0;
         const bool refill = s >= 0;             // reuse is off: the scratch holds this key and is written again
         if (!refill)
-            s = reuse.place(key, yv_n * sizeof(double) + gb_n * sizeof(unsigned long long) + od_n * sizeof(unsigned) + hb_n + cb_n * sizeof(unsigned long long),
-                            [&](int v) { return tabs[v].yvals_cap >= yv_n && tabs[v].gbits_cap >= gb_n && tabs[v].order_cap >= od_n && tabs[v].hits_cap >= hb_n && tabs[v].cbits_cap >= cb_n; },
+            s = reuse.place(key, yv_n * sizeof(double) + gb_n * sizeof(unsigned long long) + od_n * sizeof(unsigned) + hb_n + cb_n * sizeof(unsigned long long) + vb_n * sizeof(unsigned long long) + cf_n,
+                            [&](int v) { return tabs[v].yvals_cap >= yv_n && tabs[v].gbits_cap >= gb_n && tabs[v].order_cap >= od_n && tabs[v].hits_cap >= hb_n && tabs[v].cbits_cap >= cb_n &&
+                                                tabs[v].vbits_cap >= vb_n && tabs[v].cflags_cap >= cf_n; },
                             [&](int v) { tabs[v].release(); });      // (hipFree waits for the device: at a promotion or an eviction only)
         RowTables &t = tabs[s];
         ensure(t.yvals, t.yvals_cap, yv_n);
@@ -329,7 +384,7 @@ struct JitBackend final : Backend {
         // A kept set gets its order table with the other two, whether or not an order is ever computed in it: fits() asks for
         // all three, so a set whose keys rotate away before their second launch can still be taken over as it is (the
         // scratch's grows in launch(), when an order is due)
-        if (s) { ensure(t.order, t.order_cap, od_n); ensure(t.hits, t.hits_cap, hb_n); ensure(t.cbits, t.cbits_cap, cb_n); }      // (the census's flags likewise)
+        if (s) { ensure(t.order, t.order_cap, od_n); ensure(t.hits, t.hits_cap, hb_n); ensure(t.cbits, t.cbits_cap, cb_n); ensure(t.vbits, t.vbits_cap, vb_n); ensure(t.cflags, t.cflags_cap, cf_n); }      // (the census's flags likewise)
         // bits past the last guard belong to no job and are never written: zero them once per table (the pixel kernel tests whole words)
         if (t.gbits_cap != had) HIP_TRY(hipMemsetAsync(t.gbits, 0, t.gbits_cap * sizeof(unsigned long long), st));
         if (P.n_row_ops) {
@@ -352,6 +407,7 @@ struct JitBackend final : Backend {
                 n_refine_passes++;
             }
         }
+        cover_state[s] = COVER_NONE;
         if (refill) reuse.touch(s); else reuse.filled(s);      // the set carries its key only now: the kernel that fills it is enqueued
         last_gbits_n = set_gbits_n[s] = gb_n;
         return cur_set = s;
@@ -482,10 +538,53 @@ struct JitBackend final : Backend {
                 reuse.sets[set].census = true;          // only now: the kernels are enqueued
             }
         }
+        // The cover (maray_jit_cover, jit_source_cover): the census's launch over the census'd words records per rectangle which ORs
+        // of shapes are 1 on every pixel; maray_jit_cover_apply writes the set's third table, vbits.  Behind the census's apply
+        // kernel, in front of the launch order, on this stream; once per filling of a set.
+        if (want_census && f_cover && reuse.cover_due(set, matched)) {
+            const size_t words = set_gbits_n[set], rects = words / n_gwords, flags = rects * 2 * code_cover->n_cover;
+            if (words && words <= 0xFFFFFFFFull / 64) {
+                ensure(T.vbits, T.vbits_cap, words);
+                ensure(T.cflags, T.cflags_cap, flags);
+                if (!cover_ev[set]) HIP_TRY(hipEventCreateWithFlags(&cover_ev[set], hipEventDisableTiming));
+                HIP_TRY(hipMemsetAsync(T.cflags, 0, flags, st));
+                HIP_TRY(hipMemsetAsync(d_cover_n + set, 0, sizeof(unsigned), st));
+                send_params_cover(st);
+                unsigned char *no8 = nullptr; double *no64 = nullptr; unsigned *fl = nullptr; const unsigned *no_order = nullptr;
+                const double *yv = T.yvals;
+                const unsigned long long *cb = T.cbits;
+                unsigned ww = w, yy0 = y0, tile_base = 0, row_base = 0, ntx = n_tx, rows = rows_total, rpw = 1;
+                unsigned char *cf = T.cflags;
+                void *cargs[] = {&no8, &no64, &yv, &d_tex, &fl, &tile_base, &cb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &no_order, &rows, &rpw, &cf};
+                HIP_TRY(hipModuleLaunchKernel(f_cover, gx, rows_total, 1, 256, 1, 1, 0, st, cargs, nullptr));
+                unsigned long long *vb = T.vbits;
+                unsigned nw = (unsigned)words;
+                unsigned *cnt = d_cover_n + set;
+                void *aargs[] = {&cb, &cf, &vb, &nw, &cnt};
+                HIP_TRY(hipModuleLaunchKernel(f_cover_apply, (nw + 255u) / 256u, 1, 1, 256, 1, 1, 0, st, aargs, nullptr));
+                HIP_TRY(hipMemcpyAsync(h_cover_n + set, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(cover_ev[set], st));
+                n_cover++;
+                cover_state[set] = COVER_PENDING;
+                reuse.sets[set].cover = true;           // only now: the kernels are enqueued
+            }
+        }
+        // has the count of a cover taken by an earlier launch arrived?  (a query: nothing waits)
+        if (reuse.sets[set].cover && cover_state[set] == COVER_PENDING && matched) {
+            const hipError_t q = hipEventQuery(cover_ev[set]);
+            if (q == hipSuccess) cover_state[set] = h_cover_n[set] ? COVER_SOME : COVER_EMPTY;
+            else if (q == hipErrorNotReady) (void)hipGetLastError();      // not an error: the status is not left behind as HIP's last one
+            else HIP_TRY(q);
+        }
+        const bool use_cov = f_pix_cov && matched && reuse.sets[set].cover && cover_state[set] == COVER_SOME;
         // launch order of the PIXEL kernel (maray_jit_order): once per key, from the set's guard bits, whether this launch
         // ran the ROW kernel or found them there; used by every later launch of that key (time_rows too)
         // the guard words this launch and its order read: the census's where the set has been through one
-        const unsigned long long *gwords = reuse.sets[set].census ? T.cbits : T.gbits;
+        const unsigned long long *gwords = use_cov ? T.vbits : reuse.sets[set].census ? T.cbits : T.gbits;
+        // (the order reads the words this launch reads: vbits only for a set whose apply kernel is known to have set a bit)
+        const unsigned long long *owords = gwords;
+        if (use_cov) send_params_cover(st);
+        last_cov = use_cov;
         const unsigned *row_order = nullptr;
         if (want_order && matched) {
             RowReuse::Set &S = reuse.sets[set];
@@ -496,7 +595,7 @@ struct JitBackend final : Backend {
             if (!S.order && S.launches >= 2) {
                 ensure(T.order, T.order_cap, (size_t)rows_total);
                 unsigned rr = rows_total, n_tx_ = (w + 255) / 256 * guard_sub;
-                void *oargs[] = {&gwords, &T.order, &rr, &n_tx_, &yrows};
+                void *oargs[] = {&owords, &T.order, &rr, &n_tx_, &yrows};
                 HIP_TRY(hipModuleLaunchKernel(f_order, 1, 1, 1, 256, 1, 1, n_groups * 4, st, oargs, nullptr));
                 n_order_kernels++;
                 S.order = true;             // only now: the kernel that computes it is enqueued
@@ -518,7 +617,7 @@ struct JitBackend final : Backend {
             unsigned ntx = n_tx;
             unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
             void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw};
-            HIP_TRY(hipModuleLaunchKernel(f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
+            HIP_TRY(hipModuleLaunchKernel(use_cov ? f_pix_cov : f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
         if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, T.yvals);   // no-op unless a tile was deferred
     }
@@ -588,15 +687,17 @@ struct JitBackend final : Backend {
     void launch_counts(uint64_t *row_passes, uint64_t *order_kernels) const override { *row_passes = n_row_passes; *order_kernels = n_order_kernels; }
     uint64_t refine_count() const override { return n_refine_passes; }
     uint64_t census_count() const override { return n_census; }
+    uint64_t cover_count() const override { return n_cover; }
+    size_t debug_cover_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true, true); }
     size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, false); }
     size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true); }
     // the ROW pass's and the second bounds' words of the set the last launch used, or (census) the words that launch read
-    size_t debug_words(uint64_t *words, size_t cap, uint32_t *per_rect, bool census) {
+    size_t debug_words(uint64_t *words, size_t cap, uint32_t *per_rect, bool census, bool cover = false) {
         if (!n_gwords || cur_set < 0 || !tabs[cur_set].gbits) throw Error{MARAY_E_ARG, "no guard words: a program without guards, or no launch yet"};
         HIP_TRY(hipSetDevice(device));
         if (have_last) HIP_TRY(hipStreamSynchronize(last_stream));
         const size_t n = last_gbits_n;
-        const unsigned long long *src = census && reuse.sets[cur_set].census ? tabs[cur_set].cbits : tabs[cur_set].gbits;
+        const unsigned long long *src = cover && last_cov ? tabs[cur_set].vbits : census && reuse.sets[cur_set].census ? tabs[cur_set].cbits : tabs[cur_set].gbits;
         if (words && cap) HIP_TRY(hipMemcpy(words, src, std::min(n, cap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         *per_rect = n_gwords;
         return n;

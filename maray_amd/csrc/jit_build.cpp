@@ -679,4 +679,57 @@ std::shared_ptr<const JitCensusCode> jit_code_census(const maray_program &prog)
     return fut.get();
 }
 
+// The cover module of a program (jit_source_cover: maray_jit_pixels_cov, maray_jit_cover, maray_jit_cover_apply): a fifth
+// module, kept like the census's -- in the process and on disk under a key of its own (<key>.mrcv: the code object, the number
+// of reductions with a cover bit and a checksum; 0 and no code: the program gets none) made of the program's name.  Built by a
+// helper process beside the others.  MARAY_JIT_GUARD_COVER is in no key: it decides whether a context asks for the module.
+std::shared_ptr<const JitCoverCode> jit_code_cover(const maray_program &prog)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_future<std::shared_ptr<const JitCoverCode>>> built;
+    std::string key;
+    {
+        const std::string name = program_name(prog) + "|cover";
+        key = hex128(fnv1a(name.data(), name.size(), 0xcbf29ce484222325ull), fnv1a(name.data(), name.size(), 0x84222325cbf29ce4ull));
+    }
+    std::promise<std::shared_ptr<const JitCoverCode>> mine;
+    std::shared_future<std::shared_ptr<const JitCoverCode>> fut;
+    bool build = false;
+    {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = built.find(key);
+        if (it != built.end()) fut = it->second;
+        else {
+            if (built.size() > 32) built.clear();
+            fut = mine.get_future().share(); built.emplace(key, fut); build = true;
+        }
+    }
+    if (!build) return fut.get();
+    try {
+        auto out = std::make_shared<JitCoverCode>();
+        const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrcv";
+        std::vector<char> blob;
+        if (!path.empty() && blob_read(path, blob) && blob.size() >= 4) {       // code object + the count (0: no cover bit)
+            memcpy(&out->n_cover, blob.data() + blob.size() - 4, 4);
+            blob.resize(blob.size() - 4);
+            out->code.swap(blob);
+        } else {
+            CoverPlan plan;
+            const std::string src = jit_source_cover(prog, &plan);
+            if (!src.empty()) compile_aside(src, "cover", "COVER", out->code);
+            out->n_cover = src.empty() ? 0u : (uint32_t)plan.reds.size();
+            blob = out->code;
+            blob.insert(blob.end(), (const char *)&out->n_cover, (const char *)&out->n_cover + 4);
+            if (!path.empty()) blob_write(dir, path, blob);
+        }
+        if (out->code.empty() || !out->n_cover || out->n_cover > 64) out.reset();       // nothing to launch
+        mine.set_value(out);
+    } catch (...) {
+        mine.set_exception(std::current_exception());
+        std::lock_guard<std::mutex> lk(m);
+        built.erase(key);                               // a failed build is not remembered (the waiters still see its error)
+    }
+    return fut.get();
+}
+
 }   // namespace maray

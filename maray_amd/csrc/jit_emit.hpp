@@ -276,6 +276,17 @@ struct Emitter {
     bool census = false;
     uint64_t census_row_params = ~0ull;         // bit p: the ROW section reads PARAM p (a set's key holds its value); the others taint
     std::vector<uint8_t> census_leaf, census_bad;
+    std::vector<uint8_t> red_nested;                          // census, out: per reduction, its root sits inside a region
+    std::vector<std::vector<uint8_t>> red_leaf_taint;         // census, out: per reduction and guarded leaf, the leaf is tainted
+    // PIXEL: the cover forms (jit_source_cover).  cover_bit, per reduction of rplan: the free bit of the last guard word that
+    // says "this OR is 1 on every pixel of the rectangle", or -1.  `cover` (maray_jit_cover) measures it: beside a reduction's
+    // accumulator a second one ORs the untainted guarded leaves alone, the loops leave on ITS lanes being covered, and the root
+    // records two byte flags for the pass's rectangle, mr_cvf[2 j] (seen) and mr_cvf[2 j + 1] (some pixel inside the picture,
+    // mr_cin, is not covered), j = the reduction's rank among those with a bit.  `use_cover` (maray_jit_pixels_cov): the root
+    // tests the bit and takes MR_ALL without entering its loops.  Every line either form adds holds "mr_cv".
+    bool cover = false, use_cover = false;
+    std::vector<int32_t> cover_bit;
+    int32_t cover_of(int32_t id) const { return (cover || use_cover) && id >= 0 && (size_t)id < cover_bit.size() ? cover_bit[id] : -1; }
     explicit Emitter(const maray_program &p) : P(p) {}
 
     // word wi of the guard words of the rectangle at hand: an SGPR pair by name (<= 12 words); beyond, lane wi % 64 of a
@@ -658,12 +669,22 @@ struct Emitter {
                 // follows an s_setpc (s_getpc returns the address of the instruction after itself: the table starts 12 bytes on)
                 const RedPlan::Red &red = rp->reds[id];
                 if (census) for (uint32_t b : red.leaf_bit) { census_mark(census_leaf, b); if (!open.empty()) census_mark(census_bad, b); }
+                if (census) { if (red_nested.size() <= (size_t)id) red_nested.resize(id + 1, 0); red_nested[id] = !open.empty(); }
+                const int32_t cvbit = rbool ? cover_of(id) : -1;
+                const std::string cvacc = "mr_cvacc" + std::to_string(serial) + "_" + std::to_string(id);
                 const std::string rid = std::to_string(serial) + "_" + std::to_string(id);
                 const std::string racc = "mr_racc" + rid;
                 if (rbool) {
                     out += "    mr_mask " + racc + " = MR_NONE";
                     for (const std::string &m : red_free[id]) out += " | " + m;
                     out += ";\n";
+                    if (cvbit >= 0 && cover) out += "    mr_mask " + cvacc + " = MR_NONE;\n";
+                    if (cvbit >= 0 && use_cover) {
+                        char hex[24];
+                        snprintf(hex, sizeof hex, "0x%xu", 1u << ((uint32_t)cvbit % 32));
+                        const std::string w = guard_word((uint32_t)cvbit / 64);
+                        out += "    if (((unsigned)" + ((uint32_t)cvbit % 64 >= 32 ? "(" + w + " >> 32)" : w) + " & " + hex + ") != 0u) " + racc + " = MR_ALL; else {      // mr_cv: 1 on every pixel of the rectangle\n";
+                    }
                 } else {
                     // +0.0 stands for the leaves whose bit is clear; with every bit set there is none: NaN, the identity of max
                     std::string all;
@@ -690,7 +711,7 @@ struct Emitter {
                     const std::string w = std::to_string(wi), next = "mr_rn" + rid + "_" + w;
                     const std::string nz = guard_word_nonzero(wi);
                     if (!nz.empty()) out += "    if (" + nz + ")\n";
-                    out += "    for (mr_mask mr_rm = " + guard_word(wi) + " & " + hex + "; mr_rm != 0ull" + (rbool && !census ? " && !mr_covered(" + racc + ")" : std::string()) + "; ) {\n"
+                    out += "    for (mr_mask mr_rm = " + guard_word(wi) + " & " + hex + "; mr_rm != 0ull" + (rbool && !census ? " && !mr_covered(" + (cvbit >= 0 && cover ? cvacc : racc) + ")" : std::string()) + "; ) {\n"
                            "        const unsigned mr_rk = (unsigned)__builtin_ctzll(mr_rm);\n"
                            "        mr_rm &= mr_rm - 1ull;\n"
                            "        asm goto(\"s_getpc_b64 s[20:21]\\n\\ts_add_u32 s20, s20, %0\\n\\ts_addc_u32 s21, s21, 0\\n\\ts_setpc_b64 s[20:21]\"";
@@ -716,6 +737,12 @@ struct Emitter {
                                red_leaf_text[id][leaf_of_bit[b]] + "    } goto " + next + ";\n";
                     }
                     out += "    " + next + ": ;\n    }\n";
+                }
+                if (cvbit >= 0 && use_cover) out += "    }      // mr_cv\n";
+                if (cvbit >= 0 && cover) {
+                    int32_t j = 0;
+                    for (int32_t k = 0; k < id; k++) j += cover_of(k) >= 0;
+                    out += "    if (mr_lane == 0u && mr_cin != 0ull) { mr_cvf[" + std::to_string(2 * j) + "] = 1; if ((" + cvacc + " & mr_cin) != mr_cin) mr_cvf[" + std::to_string(2 * j + 1) + "] = 1; }\n";
                 }
                 ktab_block.clear();
                 if (rbool) be = racc; else e = racc;
@@ -767,7 +794,12 @@ struct Emitter {
                 const std::string ra = "mr_racc" + std::to_string(serial) + "_" + std::to_string(id);
                 if (rp->reds[id].boolean) out += "    " + ra + " |= " + (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")") + ";\n";
                 else out += "    " + ra + " = mr_max(" + ra + ", " + dbl(&r, "m", i, 0) + ");\n";
+                if (cover && rp->reds[id].boolean && cover_of(id) >= 0 && !(leaf_taint || taint || r.taint))
+                    out += "    mr_cvacc" + std::to_string(serial) + "_" + std::to_string(id) + " |= " + (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")") + ";\n";
                 if (census) {
+                    if (red_leaf_taint.size() <= (size_t)id) red_leaf_taint.resize(id + 1);
+                    red_leaf_taint[id].resize(rp->reds[id].leaf_end.size(), 0);
+                    red_leaf_taint[id][rp->leaf[i]] = leaf_taint || taint || r.taint;
                     const uint32_t bit = rp->reds[id].leaf_bit[rp->leaf[i]];
                     const std::string hit = rp->reds[id].boolean ? (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")")
                                                                  : "mr_ballot(__double_as_longlong(" + dbl(&r, "m", i, 0) + ") != 0ll)";

@@ -13,6 +13,7 @@
 // allocates registers), constants become exact hex-float literals or entries of a constant table, y values are scalar
 // loads from the row table.  Compiled with -ffp-contract=off so no a*b+c is fused behind the tape's back.
 #include "jit_emit.hpp"
+#include "row_reuse.hpp"
 
 namespace maray {
 
@@ -847,11 +848,10 @@ static std::string tile_end(bool defer)
 // Layouts that were measured and lost (a wavefront per 64 pixels with guard words staged in LDS, a busy tile on the
 // block's four wavefronts side by side, persistent wavefronts, two pixels per lane, two rows per wavefront, guard words by
 // scalar loads, a sky loop of its own ...) are history: DESIGN.md section 7.1, profiles/r2_ablations.jsonl.
-std::string jit_source(const maray_program &P, int min_waves)
+// the kernel itself, from `head` (its name and parameters) to its closing brace, into S.E.out: maray_jit_pixels, and with the
+// emitter's use_cover flag set maray_jit_pixels_cov (jit_source_cover)
+static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs &K, const std::string &head)
 {
-    validate_program(P);
-    const JitKnobs K = jit_knobs();
-    PixelSetup S(P, K, min_waves);
     Emitter &E = S.E;
     const GuardWords g(S.n_gwords, S.sub);
     const bool defer = may_defer_tiles(P), wide_general = jit_wide_general(P, S.n_gwords, K);
@@ -861,9 +861,7 @@ std::string jit_source(const maray_program &P, int min_waves)
         E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
     };
     std::string &s = E.out;
-    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
-         std::to_string(P.n_pix_ops) + " ops; general variant " + (wide_general ? "four pixels per lane" : "one pixel per lane, four passes per tile") + "\n" +
-         PIXELS_PROLOGUE + pixels_head(S.min_waves) + S.texture_loads() + strip_guard_fetch(g) +
+    s += head + S.texture_loads() + strip_guard_fetch(g) +
          "    const bool mr_wide = rgb64 == nullptr;                                   // wide variants: element e of lane l is pixel x0 + 4 l + e, else x0 + 64 e + l\n"
          "    const unsigned mr_xl = mr_wide ? 4u * mr_lane : mr_lane, mr_xs = mr_wide ? 1u : 64u;\n"
          "    const unsigned mr_src = (mr_lane * 4u) / 3u, mr_shift = ((mr_lane * 4u) % 3u) * 8u;   // RGB8 packing of one 64-pixel run\n"
@@ -890,6 +888,17 @@ std::string jit_source(const maray_program &P, int min_waves)
         s += narrow_close(defer) + tile_end(defer);
     }
     s += "    }\n}\n";
+}
+
+std::string jit_source(const maray_program &P, int min_waves)
+{
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    PixelSetup S(P, K, min_waves);
+    S.E.out += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+               std::to_string(P.n_pix_ops) + " ops; general variant " + (jit_wide_general(P, S.n_gwords, K) ? "four pixels per lane" : "one pixel per lane, four passes per tile") + "\n" +
+               PIXELS_PROLOGUE;
+    pixels_kernel(S, P, K, pixels_head(S.min_waves));
     return S.splice_constants(MR_STORE_RUN);
 }
 
@@ -990,6 +999,177 @@ std::string jit_source_census(const maray_program &P, std::vector<uint64_t> *eli
     s += census_apply_kernel(eligible);
     if (eligible_out) *eligible_out = eligible;
     return S.splice_constants("");
+}
+
+// ---- maray_jit_cover, maray_jit_cover_apply, maray_jit_pixels_cov ------------------------------------------------------------------
+// Which boolean reductions of a program get a cover bit (Emitter::cover_bit): those the census may decide -- the root in no
+// region, at least one guarded leaf on an eligible bit -- as far as the last guard word has bits that no guard uses
+// (cover_free_bits, row_reuse.hpp).  A dry run of the census form says which those are and which leaves are tainted.
+// bit_of_red: per reduction of the section's RedPlan.
+namespace {
+struct CoverSetup { CoverPlan plan; std::vector<int32_t> bit_of_red; };
+
+CoverSetup cover_setup(const maray_program &P, const JitKnobs &K)
+{
+    CoverSetup cs;
+    PixelSetup S(P, K, 0);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    if (!g.n || S.reductions.empty() || jit_wide_general(P, S.n_gwords, K)) return cs;
+    if (g.per_lane() && g.sub > 1) E.gw_lane_base = "mr_gsub";
+    E.census = true;
+    E.census_row_params = row_param_mask(P);
+    E.td = "double"; E.tm = "mr_mask"; E.assume_guards_zero = false; E.rplan = &S.reductions;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    auto eligible = [&](uint32_t b) { return b < E.census_leaf.size() && E.census_leaf[b] && !(b < E.census_bad.size() && E.census_bad[b]); };
+    std::vector<uint32_t> want;
+    for (uint32_t id = 0; id < S.reductions.reds.size(); id++) {
+        const RedPlan::Red &red = S.reductions.reds[id];
+        bool any = false;
+        for (uint32_t b : red.leaf_bit) any |= eligible(b);
+        if (red.boolean && any && id < E.red_nested.size() && !E.red_nested[id] && id < E.red_leaf_taint.size()) want.push_back(id);
+    }
+    // A guard bit belongs to a bound, not to a shape: the lowering interns bounds, so leaves of two reductions (boolean or max)
+    // may sit on one bit.  The census ORs the hits of all of them; a cover may clear a bit only for the ONE reduction that is
+    // covered, so a bit with leaves in more than one reduction is never cleared (the covered OR still skips its own loops)
+    std::vector<uint32_t> owners(64 * g.n, 0);
+    for (const RedPlan::Red &red : S.reductions.reds)
+        for (uint32_t b : red.leaf_bit) if (b < owners.size()) owners[b]++;
+    std::vector<int32_t> bits(want.size(), -1);
+    const uint32_t got = cover_free_bits(S.plan.n_pos, g.n, (uint32_t)want.size(), bits.data());
+    cs.bit_of_red.assign(S.reductions.reds.size(), -1);
+    cs.plan.n_words = g.n;
+    for (uint32_t k = 0; k < got; k++) {
+        const RedPlan::Red &red = S.reductions.reds[want[k]];
+        CoverPlan::Red r;
+        r.bit = bits[k]; r.root = red.root; r.leaf_end = red.leaf_end; r.leaf_bit = red.leaf_bit;
+        r.leaf_taint = E.red_leaf_taint[want[k]];
+        r.leaf_taint.resize(red.leaf_bit.size(), 1);
+        for (uint32_t b : red.leaf_bit) r.leaf_eligible.push_back(eligible(b) && b < owners.size() && owners[b] == 1);
+        cs.plan.reds.push_back(r);
+        cs.bit_of_red[want[k]] = bits[k];
+    }
+    return cs;
+}
+}   // namespace
+
+CoverPlan jit_cover_plan(const maray_program &P)
+{
+    validate_program(P);
+    return cover_setup(P, jit_knobs()).plan;
+}
+
+// Writes a set's third table of words: the census'd words, and for each (rectangle, reduction) whose flags say "seen and
+// no pixel missed" the reduction's cover bit set and its leaf bits that are census-eligible and carry no leaf of another reduction -- those gate nothing else -- cleared.  One
+// work-item per word; the masks are literals of the text.  *n_set counts the cover bits set (the host launches
+// maray_jit_pixels_cov over the table only if there are any).
+static std::string cover_apply_kernel(const CoverPlan &cp)
+{
+    const uint32_t nw = cp.n_words, nc = (uint32_t)cp.reds.size();
+    std::string s = "extern \"C\" __global__ void __launch_bounds__(256) maray_jit_cover_apply(const unsigned long long *__restrict__ cbits, const unsigned char *__restrict__ flags,\n"
+                    "                                                                        unsigned long long *__restrict__ out, unsigned n_words, unsigned *__restrict__ n_set)\n{\n"
+                    "    const unsigned i = blockIdx.x * 256u + threadIdx.x;                  // (the host keeps the words of a launch below 2^32)\n"
+                    "    if (i >= n_words) return;\n"
+                    "    const unsigned char *f = flags + (size_t)(i / " + std::to_string(nw) + "u) * " + std::to_string(2 * nc) + "u;      // the flags of the word's rectangle\n"
+                    "    unsigned long long word = cbits[i];\n"
+                    "    switch (i % " + std::to_string(nw) + "u) {\n";
+    for (uint32_t w = 0; w < nw; w++) {
+        std::string body;
+        for (uint32_t j = 0; j < nc; j++) {
+            uint64_t clear = 0, set = 0;
+            for (size_t k = 0; k < cp.reds[j].leaf_bit.size(); k++)
+                if (cp.reds[j].leaf_eligible[k] && cp.reds[j].leaf_bit[k] / 64 == w) clear |= 1ull << (cp.reds[j].leaf_bit[k] % 64);
+            if ((uint32_t)cp.reds[j].bit / 64 == w) set = 1ull << ((uint32_t)cp.reds[j].bit % 64);
+            if (!clear && !set) continue;
+            char hex[96];
+            snprintf(hex, sizeof hex, "word = (word & ~0x%llxull) | 0x%llxull;", (unsigned long long)clear, (unsigned long long)set);
+            body += "        if (f[" + std::to_string(2 * j) + "] && !f[" + std::to_string(2 * j + 1) + "]) { " + hex + (set ? " atomicAdd(n_set, 1u);" : "") + " }\n";
+        }
+        if (!body.empty()) s += "    case " + std::to_string(w) + ":\n" + body + "        break;\n";
+    }
+    s += "    }\n"
+         "    out[i] = word;\n"
+         "}\n";
+    return s;
+}
+
+// Source of the cover module: maray_jit_pixels_cov, maray_jit_cover and maray_jit_cover_apply; "" when the program gets no
+// cover bit.  All three from the generator of maray_jit_pixels -- the prologue, the head, the guard words' fetches, the pass's
+// tables and the section are that kernel's text, and the constant table (one for the module) is that kernel's entry for entry:
+//  * maray_jit_pixels_cov is maray_jit_pixels with one scalar test at the root of a reduction that has a cover bit: the bit
+//    set in the pass's guard word, the OR is MR_ALL and its loops are not entered;
+//  * maray_jit_cover is the narrow form without stores, like maray_jit_census, over the set's census'd words: it records per
+//    (rectangle, reduction) `seen` and `miss` (Emitter::cover), 2 bytes per reduction with a bit, rectangles numbered like
+//    their guard words.
+// Exactness: OR on lane masks is associative and commutative; with the bit set the untainted leaves alone are 1 on every
+// pixel of the rectangle inside the picture under the set's key, so the OR is all-ones there whatever the leaves that are
+// not entered would have computed; lanes outside the picture are never stored.
+std::string jit_source_cover(const maray_program &P, CoverPlan *plan_out, int min_waves)
+{
+    if (plan_out) *plan_out = CoverPlan();
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    const CoverSetup cs = cover_setup(P, K);
+    if (cs.plan.reds.empty()) return "";
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    E.cover_bit = cs.bit_of_red;
+    E.census_row_params = row_param_mask(P);
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; cover forms: " + std::to_string(cs.plan.reds.size()) + " OR(s) of shapes may be known to be 1 on every pixel of a rectangle\n" +
+         PIXELS_PROLOGUE;
+    const size_t ktab0 = E.ktab_vals.size();
+    std::string head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_pixels_cov(");
+    E.use_cover = true;
+    pixels_kernel(S, P, K, head);
+    E.use_cover = false;
+    // maray_jit_cover: the constant table and the label numbers start over, so that its section is that kernel's text too
+    const std::vector<double> table = E.ktab_vals;
+    E.ktab_vals.resize(ktab0);
+    E.ktab_block.clear();
+    E.red_serial = 0;
+    head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_cover(");
+    const char tail[] = "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw)";
+    head.replace(head.find(tail), sizeof tail - 1, "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw, unsigned char *__restrict__ mr_cover)");
+    s += "\n" + head + S.texture_loads() + strip_guard_fetch(g) +
+         "    (void)rgb8; (void)rgb64;\n"
+         "    for (unsigned t = 0; t < tiles; t++) {\n"
+         "    const unsigned x0 = (tile0 + t) * 256u;\n"
+         "    if (x0 >= w) break;\n"
+         "/*MR_KBASE*/" + tile_guard_fetch(g) +
+         sky_test(g) + "    continue;\n    }\n"
+         "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + PIXELS_PASS_TABLES + pass_guard_words(g) +
+         "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
+         "    const double X = (double)x;\n"
+         "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
+         "    float mr_defer = 0.0f;\n"
+         "    (void)X; (void)mr_defer;\n"
+         "    const mr_mask mr_cin = mr_ballot(x < w);                                 // the lanes inside the picture\n"
+         "    // the flags of this pass's rectangle: rectangles are numbered like their guard words\n"
+         "    unsigned char *mr_cvf = mr_cover + (((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * " + std::to_string(g.sub) + "u + " +
+         (g.sub > 1 ? g.esub : std::string("0u")) + ") * " + std::to_string(2 * cs.plan.reds.size()) + "u;\n";
+    {   // (the variant of a tile without a guard bit: emitted and dropped, as in jit_source_census)
+        const size_t keep = s.size();
+        E.td = "mr_d"; E.tm = "mr_m"; E.assume_guards_zero = true; E.rplan = nullptr;
+        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+        s.resize(keep);
+    }
+    E.cover = true;
+    E.td = "double"; E.tm = "mr_mask"; E.assume_guards_zero = false; E.rplan = &S.reductions;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    E.cover = false;
+    s += "    (void)o0; (void)o1; (void)o2;\n"
+         "    }\n"
+         "    }\n}\n";
+    if (E.ktab_vals.size() != table.size() || memcmp(E.ktab_vals.data(), table.data(), table.size() * sizeof(double)) != 0)
+        throw Error{MARAY_E_INTERNAL, "the cover kernels disagree about the constant table"};
+    s += cover_apply_kernel(cs.plan);
+    if (plan_out) *plan_out = cs.plan;
+    return S.splice_constants(MR_STORE_RUN);
 }
 
 

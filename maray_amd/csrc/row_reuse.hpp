@@ -47,6 +47,17 @@ struct RowKey {
     }
 };
 
+// The cover bits of a program: `want` bits from those of the last of `n_words` guard words that no guard uses (bits n_used ..
+// 64 n_words - 1).  Never a word more: returns how many were granted, lowest free bit first, into bits[0 .. granted).
+inline uint32_t cover_free_bits(uint32_t n_used, uint32_t n_words, uint32_t want, int32_t *bits)
+{
+    if (!n_words || n_used > 64u * n_words) return 0;
+    const uint32_t first = n_used > 64u * (n_words - 1) ? n_used : 64u * (n_words - 1);
+    const uint32_t n_free = 64u * n_words - first, granted = want < n_free ? want : n_free;
+    for (uint32_t k = 0; k < granted; k++) bits[k] = (int32_t)(first + k);
+    return granted;
+}
+
 struct RowReuse {
     static constexpr int MAX_KEPT = 8;                      // design limits, not measurements
     static constexpr size_t MAX_BYTES = (size_t)256 << 20;
@@ -57,6 +68,7 @@ struct RowReuse {
         RowKey key;
         bool keyed = false;         // the tables hold the ROW outputs of `key` (set only once the ROW kernel is enqueued)
         bool order = false;         // ... and the launch order computed from its guard bits
+        bool cover = false;         // ... and the third table, in which a cover bit stands for the leaves of an OR that is 1 on every pixel of a rectangle (maray_jit_cover); set with or after `census`, withdrawn wherever it is
         bool census = false;        // ... and the second table of guard words the census made of them (maray_jit_census): without the bits of leaves that are zero on every pixel of a rectangle
         uint32_t launches = 0;      // launches that used the set under this key: the second one (the first that found it filled) computes the order
         uint64_t stamp = 0;         // last use (kept sets: least recently used goes first)
@@ -89,6 +101,10 @@ struct RowReuse {
     // for a ROW pass writes the words again.  matched: the set holds this launch's key.  The caller sets Set::census once the
     // kernels are enqueued, and enqueues them in front of the order kernel, which counts the bits that are left.
     bool census_due(int s, bool matched) const { return enabled && matched && sets[s].keyed && !sets[s].census && sets[s].launches >= 2; }
+
+    // The cover (maray_jit_cover) reads the census'd words: due on the launch that takes the census or any later one that finds
+    // the set through its census and not yet covered.  The caller sets Set::cover once the kernels are enqueued.
+    bool cover_due(int s, bool matched) const { return enabled && matched && sets[s].keyed && sets[s].census && !sets[s].cover; }
 
     bool was_seen(uint64_t h) const {
         for (uint64_t v : seen) if (v == h) return true;
@@ -140,6 +156,7 @@ struct RowReuse {
         sets[s].keyed = false;
         sets[s].order = false;
         sets[s].census = false;
+        sets[s].cover = false;
         sets[s].launches = 0;                           // (touch() by filled() counts this launch)
         sets[s].key = key;
         return s;
