@@ -675,6 +675,50 @@ int maray_hip_render_png_opts(maray_ctx *c, uint32_t w, uint32_t h, const double
 int maray_hip_time_png_encode_opts(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_opts *opts, int reps, float *ms_avg,
                                    uint64_t *stream_bytes);
 
+/* Indexed colour: PNG colour type 3 for rasters of at most 256 colours, opt-in through a family of its own (maray_png_opts
+ * cannot grow); MARAY_PNG_COLOR_RGB is everything above, byte for byte.  Everything not named here is the truecolour contract
+ * unchanged: 78 01, segments in row-major order, one fixed-Huffman block per segment followed by the empty stored block that
+ * ends on a byte boundary, 01 00 00 FF FF, the Adler-32, IDAT chunks of at most 2^30 bytes, CRCs, the size checks.
+ *   - palette: the n <= 256 distinct colours of the WHOLE raster, ascending by R * 65536 + G * 256 + B; a pixel's index is its
+ *     colour's position in that order.  PLTE holds exactly n entries; there is no tRNS; chunk order IHDR, PLTE, IDAT.., IEND;
+ *   - bit depth: d = 1 for n <= 2, 2 for n <= 4, 4 for n <= 16, else 8 (the smallest PNG allows); IHDR says depth d, colour
+ *     type 3, no interlace;
+ *   - filtered data: row y is one filter byte 0 followed by rb = ceil(w d / 8) packed bytes, the leftmost pixel in the
+ *     high-order bits, the unused low bits of a row's last byte zero;
+ *   - segments: a row's packed bytes are cut into segments of 768 bytes (the last of a row may be shorter); the filter byte
+ *     belongs to the row's first segment, so a segment is at most 769 bytes, the truecolour maximum, and the slot bound
+ *     ceil(9 n / 8) + 16 carries over.  Segments are compressed independently;
+ *   - tokens: the filter byte is a literal, a segment's first packed byte is a literal.  The packed bytes of a segment are
+ *     taken in steps of 64.  A byte equal to the byte before it IN THE SAME SEGMENT is "repeated" (the first byte of a later
+ *     step is compared with the last byte of the step before).  A maximal run of L repeated bytes inside one step (a run is
+ *     closed at a step's end: L <= 64) is ONE match of distance 1 when L >= 3 -- the standard length code and extra bits, then
+ *     distance code 0, five zero bits -- and L literals when L is 1 or 2.  Every other byte is a literal, standard fixed codes;
+ *   - what the bytes depend on: the raster alone -- identical for every MARAY_PNG_BAND_ROWS, stream and call;
+ *   - Adler-32: over the filtered bytes as above, by the same per-segment shares; a band's byte count is rows (rb + 1).
+ * The modes: MARAY_PNG_COLOR_RGB is exactly the plain entry point.  MARAY_PNG_COLOR_INDEXED writes the indexed file; a raster
+ * of more than 256 colours is MARAY_E_LIMIT ("more than 256 colours"), no file is produced and the encoder stays usable.
+ * MARAY_PNG_COLOR_AUTO writes the indexed file where it exists and otherwise exactly the RGB file.  This family is fixed codes
+ * and filter 0 only.  An unknown mode or a reserved word that is not 0 is MARAY_E_ARG, reported before a device is looked for.
+ * How it runs: maray_png_colors (a capped grid; every block collects its pixels' colours in a set in LDS and stores them to
+ * a slab of its own) and maray_png_colors_merge (one block: the slabs' union, and the palette of earlier bands, ranked) over
+ * the whole raster; one copy of 1,028 bytes (the count and the palette) and a wait; the decision; then per band
+ * maray_png_index (RGB8 rows -> packed index rows in an encoder-owned buffer), maray_png_compress_idx (the tokeniser above,
+ * one wavefront per segment), maray_png_scan, maray_png_gather and the two copies of the truecolour path.
+ * maray_hip_render_png_color renders an image that fits one band ONCE and encodes it from the band buffer; a taller image is
+ * rendered TWICE per band, first to collect the colours, then to encode (rendering is deterministic for given values, the
+ * shutter form included); with MARAY_PNG_COLOR_AUTO and more than 256 colours the second pass is the truecolour path.
+ * maray_gen, the CLI and the animation writers do not take the mode. */
+enum { MARAY_PNG_COLOR_RGB = 0, MARAY_PNG_COLOR_INDEXED = 1, MARAY_PNG_COLOR_AUTO = 2 };
+typedef struct { uint32_t color, reserved[7]; } maray_png_color_opts;     /* 32 bytes; null = all zeros */
+int maray_hip_png_encode_device_color(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_color_opts *opts, void *stream, uint8_t **png_out, size_t *n_out);
+int maray_hip_render_png_color(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, const maray_png_color_opts *opts, uint8_t **png_out, size_t *n_out);
+/* all the kernels of one band, the collection included (the palette is fetched once, before the timed loop); with
+ * MARAY_PNG_COLOR_AUTO on more than 256 colours: the collection's kernels plus the truecolour band's */
+int maray_hip_time_png_encode_color(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_color_opts *opts, int reps, float *ms_avg, uint64_t *stream_bytes);
+/* The sorted palette alone: *n_colors = the count, or 257 for "more than 256" (the palette's contents are then unspecified);
+ * up to 256 entries of R, G, B.  maray_hip_png_bytes_to_host counts the palette's 1,028 bytes too. */
+int maray_hip_png_palette(int device, const void *d_rgb8, uint32_t w, uint32_t h, void *stream, uint32_t *n_colors, uint8_t palette[768]);
+
 /* ---- animation (one APNG, encoded on the device frame by frame) ----------------------------------------------------
  * An animation is written as ONE file: an APNG, i.e. a PNG whose IDAT image is frame 0 (any PNG reader shows it) followed
  * by the later frames, each a complete zlib stream -- the device PNG encoder's, above -- of a SUB-RECTANGLE of the canvas.

@@ -10,6 +10,7 @@ from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, EN
                   apng_encode_device, frame_delta, gen_animation, time_frame_delta,
                   CODES_DYNAMIC, CODES_FIXED, ENCODER_DYNAMIC, png_dynamic_codes,
                   PNG_FILTER_ADAPTIVE, PNG_FILTER_AVERAGE, PNG_FILTER_NONE, PNG_FILTER_PAETH, PNG_FILTER_SUB, PNG_FILTER_UP, PngOpts,
+                  PNG_COLOR_AUTO, PNG_COLOR_INDEXED, PNG_COLOR_RGB, PngColorOpts, png_palette,
                   CONTAINER_APNG, CONTAINER_Y4M, YCC_420, YCC_444, YCC_BT601, YCC_BT709, AnimOpts, YccOpts, rgb_to_ycc, time_rgb_to_ycc, y4m_encode_device,
                   ycc_frame_bytes)
 
@@ -20,5 +21,6 @@ __all__ = ['Scene', 'Tape', 'Context', 'PinnedRaster', 'MarayError', 'gen', 'gen
            'frame_delta', 'apng_encode_device', 'gen_animation', 'time_frame_delta',
            'CODES_FIXED', 'CODES_DYNAMIC', 'ENCODER_DYNAMIC', 'png_dynamic_codes',
            'PNG_FILTER_NONE', 'PNG_FILTER_ADAPTIVE', 'PNG_FILTER_SUB', 'PNG_FILTER_UP', 'PNG_FILTER_AVERAGE', 'PNG_FILTER_PAETH', 'PngOpts',
+           'PNG_COLOR_RGB', 'PNG_COLOR_INDEXED', 'PNG_COLOR_AUTO', 'PngColorOpts', 'png_palette',
            'YCC_420', 'YCC_444', 'YCC_BT601', 'YCC_BT709', 'CONTAINER_APNG', 'CONTAINER_Y4M', 'YccOpts', 'AnimOpts', 'ycc_frame_bytes', 'rgb_to_ycc',
            'y4m_encode_device', 'time_rgb_to_ycc']

@@ -18,6 +18,8 @@ ENCODER_DYNAMIC = 0x100                 # a flag on ENCODER_DEVICE: dynamic-Huff
 CODES_FIXED, CODES_DYNAMIC = 0, 1       # MARAY_PNG_CODES_*
 # MARAY_PNG_FILTER_*: the device PNG encoder's row filter (png_filter=; `filter` is the reconstruction filter everywhere)
 PNG_FILTER_NONE, PNG_FILTER_ADAPTIVE, PNG_FILTER_SUB, PNG_FILTER_UP, PNG_FILTER_AVERAGE, PNG_FILTER_PAETH = range(6)
+# MARAY_PNG_COLOR_*: the device PNG encoder's colour mode (png_color=): truecolour, indexed, or indexed where at most 256 colours
+PNG_COLOR_RGB, PNG_COLOR_INDEXED, PNG_COLOR_AUTO = range(3)
 TRANSFER_NONE, TRANSFER_SRGB = 0, 1
 YCC_420, YCC_444 = 0, 1                 # MARAY_YCC_*: the chroma sampling of the raw-video planes
 YCC_BT601, YCC_BT709 = 0, 1             # ... and their matrix (both limited range)
@@ -27,6 +29,11 @@ CONTAINER_APNG, CONTAINER_Y4M = 0, 1    # MARAY_CONTAINER_*: what gen_animation 
 class PngOpts(C.Structure):
     """maray_png_opts"""
     _fields_ = [('codes', C.c_uint32), ('filter', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+
+
+class PngColorOpts(C.Structure):
+    """maray_png_color_opts"""
+    _fields_ = [('color', C.c_uint32), ('reserved', C.c_uint32 * 7)]
 
 
 class YccOpts(C.Structure):
@@ -48,6 +55,15 @@ def _ycc_opts(sampling, matrix):
 def _png_opts(codes, png_filter):
     o = PngOpts()
     o.codes, o.filter = codes, png_filter
+    return o
+
+
+def _png_color_opts(png_color, codes, png_filter, who):
+    """The options of the `_color` family, which is fixed codes and filter 0 only."""
+    if codes != CODES_FIXED or png_filter != PNG_FILTER_NONE:
+        raise MarayError(-1, '%s: a png_color mode takes neither codes nor png_filter' % who)
+    o = PngColorOpts()
+    o.color = png_color
     return o
 
 
@@ -214,6 +230,10 @@ def lib():
         'maray_hip_png_encode_device_opts': (C.c_int, [C.c_int, vp, u32, u32, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_render_png_opts': (C.c_int, [vp, u32, u32, vp, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         'maray_hip_time_png_encode_opts': (C.c_int, [C.c_int, vp, u32, u32, vp, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_hip_png_encode_device_color': (C.c_int, [C.c_int, vp, u32, u32, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_render_png_color': (C.c_int, [vp, u32, u32, vp, u32, vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        'maray_hip_time_png_encode_color': (C.c_int, [C.c_int, vp, u32, u32, vp, C.c_int, C.POINTER(C.c_float), u64p]),
+        'maray_hip_png_palette': (C.c_int, [C.c_int, vp, u32, u32, vp, C.POINTER(u32), vp]),
         'maray_png_dynamic_codes': (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         'maray_hip_png_bytes_to_host': (C.c_uint64, []),
         'maray_hip_frame_delta': (C.c_int, [C.c_int, vp, vp, u32, u32, vp, C.POINTER(u32)]),
@@ -684,12 +704,18 @@ class Context:
         cb = TILE_FN((lambda user, a, b: on_tile(a, b)) if on_tile else 0)
         _check(lib().maray_hip_render_tiles_shutter(self._h, w, h, flat, len(tiles), vp_, n, image.ctypes.data, cb, None))
 
-    def render_png(self, w, h, frames=None, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
+    def render_png(self, w, h, frames=None, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE, png_color=PNG_COLOR_RGB):
         """The whole w x h image as the bytes of a PNG, rendered and encoded on the device (maray_hip_render_png_opts); frames: as
         for render_rows_shutter (None: the plain render); codes=CODES_DYNAMIC: a Huffman code fitted to every band;
-        png_filter=PNG_FILTER_*: the rows' PNG filter (ADAPTIVE: per row the type that makes the row smallest)."""
+        png_filter=PNG_FILTER_*: the rows' PNG filter (ADAPTIVE: per row the type that makes the row smallest);
+        png_color=PNG_COLOR_INDEXED / PNG_COLOR_AUTO: an indexed-colour file for at most 256 colours
+        (maray_hip_render_png_color; fixed codes and filter 0 only)."""
         n, vp_, keep = (0, None, None) if frames is None else self._frames(frames)
         p, sz = C.c_void_p(), C.c_size_t()
+        if png_color != PNG_COLOR_RGB:
+            o = _png_color_opts(png_color, codes, png_filter, 'render_png')
+            _check(lib().maray_hip_render_png_color(self._h, w, h, vp_, n, C.byref(o), C.byref(p), C.byref(sz)))
+            return _take_bytes(p, sz)
         _check(lib().maray_hip_render_png_opts(self._h, w, h, vp_, n, C.byref(_png_opts(codes, png_filter)), C.byref(p), C.byref(sz)))
         return _take_bytes(p, sz)
 
@@ -955,22 +981,40 @@ def _take_bytes(p, sz):
         lib().maray_free(p)
 
 
-def png_encode_device(d_ptr, w, h, device=0, stream=0, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
+def png_encode_device(d_ptr, w, h, device=0, stream=0, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE, png_color=PNG_COLOR_RGB):
     """A packed (h, w, 3) uint8 raster in device memory (any alignment) -> the bytes of a PNG, encoded on the device
     (maray_hip_png_encode_device_opts); enqueued on `stream` and waited for.  codes=CODES_DYNAMIC: a Huffman code fitted to
-    every band of rows instead of the fixed codes; png_filter=PNG_FILTER_*: the rows' PNG filter."""
+    every band of rows instead of the fixed codes; png_filter=PNG_FILTER_*: the rows' PNG filter; png_color=PNG_COLOR_INDEXED /
+    PNG_COLOR_AUTO: an indexed-colour file for at most 256 colours (maray_hip_png_encode_device_color; fixed codes, filter 0)."""
     p, sz = C.c_void_p(), C.c_size_t()
+    if png_color != PNG_COLOR_RGB:
+        o = _png_color_opts(png_color, codes, png_filter, 'png_encode_device')
+        _check(lib().maray_hip_png_encode_device_color(device, d_ptr or None, w, h, C.byref(o), stream or None, C.byref(p), C.byref(sz)))
+        return _take_bytes(p, sz)
     _check(lib().maray_hip_png_encode_device_opts(device, d_ptr or None, w, h, C.byref(_png_opts(codes, png_filter)), stream or None, C.byref(p),
                                                   C.byref(sz)))
     return _take_bytes(p, sz)
 
 
-def time_png_encode(d_ptr, w, h, device=0, reps=10, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE):
+def time_png_encode(d_ptr, w, h, device=0, reps=10, codes=CODES_FIXED, png_filter=PNG_FILTER_NONE, png_color=PNG_COLOR_RGB):
     """(average ms of the encoder's kernels over the raster as one band, bytes of the stream they make); with a png_filter the
-    kernels that choose the rows' types are among them."""
+    kernels that choose the rows' types are among them; with a png_color mode the kernels that collect the colours
+    (maray_hip_time_png_encode_color)."""
     ms, nb = C.c_float(), C.c_uint64()
+    if png_color != PNG_COLOR_RGB:
+        o = _png_color_opts(png_color, codes, png_filter, 'time_png_encode')
+        _check(lib().maray_hip_time_png_encode_color(device, d_ptr or None, w, h, C.byref(o), reps, C.byref(ms), C.byref(nb)))
+        return ms.value, nb.value
     _check(lib().maray_hip_time_png_encode_opts(device, d_ptr or None, w, h, C.byref(_png_opts(codes, png_filter)), reps, C.byref(ms), C.byref(nb)))
     return ms.value, nb.value
+
+
+def png_palette(d_ptr, w, h, device=0, stream=0):
+    """The distinct colours of a packed (h, w, 3) uint8 raster in device memory, collected on the device (maray_hip_png_palette):
+    (n, uint8[n, 3]) in ascending order of R * 65536 + G * 256 + B, or (257, an empty array) for more than 256 colours."""
+    n, pal = C.c_uint32(), np.zeros((256, 3), np.uint8)
+    _check(lib().maray_hip_png_palette(device, d_ptr or None, w, h, stream or None, C.byref(n), pal.ctypes.data))
+    return n.value, pal[:n.value if n.value <= 256 else 0].copy()
 
 
 def png_dynamic_codes(lit_counts, dist_counts):

@@ -1023,6 +1023,139 @@ int maray_hip_time_png_encode_opts(int device, const void *d_rgb8, uint32_t w, u
 
 uint64_t maray_hip_png_bytes_to_host(void) { return png_bytes_to_host(); }
 
+// ---- indexed colour (include/maray_hip.h, "Indexed colour") ---------------------------------------------------------
+// the mode of a maray_png_color_opts (null: all zeros), checked before a device is looked for
+static uint32_t png_color_mode(const maray_png_color_opts *opts)
+{
+    const uint32_t color = opts ? opts->color : (uint32_t)MARAY_PNG_COLOR_RGB;
+    REQUIRE(color <= MARAY_PNG_COLOR_AUTO, "unknown PNG color mode");
+    for (int i = 0; opts && i < 7; i++) REQUIRE(!opts->reserved[i], "maray_png_color_opts: a reserved word is not 0");
+    return color;
+}
+
+// the decision: true = the indexed file; false = the truecolour file (AUTO); INDEXED on more than 256 colours throws
+static bool png_indexed_file(uint32_t color, uint32_t n_colors)
+{
+    if (n_colors <= 256) return true;
+    if (color == MARAY_PNG_COLOR_INDEXED) throw Error{MARAY_E_LIMIT, "the raster holds more than 256 colours"};
+    return false;
+}
+
+int maray_hip_png_encode_device_color(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_color_opts *opts, void *stream,
+                                      uint8_t **png_out, size_t *n_out)
+{
+    uint32_t color = MARAY_PNG_COLOR_RGB;
+    const int rc = guard([&] {
+        REQUIRE(png_out && n_out, "null argument");
+        *png_out = nullptr; *n_out = 0;
+        color = png_color_mode(opts);
+        if (color == MARAY_PNG_COLOR_RGB) return;
+        REQUIRE(d_rgb8, "null argument");
+        REQUIRE(w && h, "empty image");
+        png_check_size(w, h);
+        PngEncoderLease E(device);
+        const unsigned char *src = (const unsigned char *)d_rgb8;
+        const hipStream_t st = (hipStream_t)stream;
+        uint8_t palette[768];
+        E->collect_colors(src, (uint64_t)w * h, st, false);
+        const uint32_t n = E->fetch_palette(st, palette);
+        PngPiece piece;
+        piece.y0 = 0; piece.y1 = h;
+        if (png_indexed_file(color, n)) {
+            E->encode_rows_indexed(src, w, h, n, st, piece);
+            png_hand_over(png_assemble_indexed(w, h, palette, n, {&piece}), png_out, n_out);
+        } else {
+            E->encode_rows(src, w, h, st, piece);
+            png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
+        }
+    });
+    if (rc == MARAY_OK && color == MARAY_PNG_COLOR_RGB) return maray_hip_png_encode_device(device, d_rgb8, w, h, stream, png_out, n_out);
+    return rc;
+}
+
+int maray_hip_render_png_color(maray_ctx *c, uint32_t w, uint32_t h, const double *values, uint32_t n_frames, const maray_png_color_opts *opts,
+                               uint8_t **png_out, size_t *n_out)
+{
+    uint32_t color = MARAY_PNG_COLOR_RGB;
+    const int rc = guard([&] {
+        REQUIRE(png_out && n_out, "null argument");
+        *png_out = nullptr; *n_out = 0;
+        color = png_color_mode(opts);
+        if (color == MARAY_PNG_COLOR_RGB) return;
+        REQUIRE(c && c->backend, "null context");
+        REQUIRE(w && h, "empty image");
+        check_rows(w, h, 0, h);
+        png_check_size(w, h);
+        check_samples(c, w, h, false, values != nullptr);
+        if (values) check_shutter(c, values, n_frames);
+        int device = 0;
+        {
+            std::lock_guard<std::mutex> lk(g_ctx_device_mutex);
+            auto it = g_ctx_device.find(c);
+            if (it == g_ctx_device.end()) throw Error{MARAY_E_ARG, "unknown context"};
+            device = it->second;
+        }
+        PngEncoderLease E(device);
+        const hipStream_t st = E->own_stream;
+        auto render = [&](uint32_t b0, uint32_t b1, unsigned char *d8, hipStream_t s) {
+            if (values) c->backend->render_device_shutter(w, h, RowBlocks::range(b0, b1), values, n_frames, d8, s);
+            else c->backend->render_device(w, h, RowBlocks::range(b0, b1), d8, nullptr, s);
+        };
+        const uint32_t step = E->band_rows(w);
+        unsigned char *d8 = E->band_buffer((size_t)std::min(step, h) * w * 3);
+        // the colours: band by band into one palette; an image of one band stays in the band buffer
+        for (uint32_t b0 = 0; b0 < h; b0 += step) {
+            const uint32_t b1 = b0 + std::min(step, h - b0);
+            render(b0, b1, d8, st);
+            E->collect_colors(d8, (uint64_t)(b1 - b0) * w, st, b0 != 0);
+        }
+        uint8_t palette[768];
+        const uint32_t n = E->fetch_palette(st, palette);
+        PngPiece piece;
+        piece.y0 = 0; piece.y1 = h;
+        if (!png_indexed_file(color, n)) {
+            if (h <= step) E->encode_rows(d8, w, h, st, piece);
+            else E->encode_rendered(w, 0, h, st, render, piece);
+            png_hand_over(png_assemble(w, h, {&piece}), png_out, n_out);
+            return;
+        }
+        for (uint32_t b0 = 0; b0 < h; b0 += step) {
+            const uint32_t b1 = b0 + std::min(step, h - b0);
+            if (h > step) render(b0, b1, d8, st);               // (the second render of a band)
+            E->encode_rows_indexed(d8, w, b1 - b0, n, st, piece);
+        }
+        png_hand_over(png_assemble_indexed(w, h, palette, n, {&piece}), png_out, n_out);
+    });
+    if (rc == MARAY_OK && color == MARAY_PNG_COLOR_RGB) return maray_hip_render_png(c, w, h, values, n_frames, png_out, n_out);
+    return rc;
+}
+
+int maray_hip_time_png_encode_color(int device, const void *d_rgb8, uint32_t w, uint32_t h, const maray_png_color_opts *opts, int reps, float *ms_avg,
+                                    uint64_t *stream_bytes)
+{
+    uint32_t color = MARAY_PNG_COLOR_RGB;
+    const int rc = guard([&] {
+        REQUIRE(ms_avg, "null argument");
+        color = png_color_mode(opts);
+        if (color != MARAY_PNG_COLOR_RGB) *ms_avg = png_time_kernels_color(device, (const unsigned char *)d_rgb8, w, h, color, reps, stream_bytes);
+    });
+    if (rc == MARAY_OK && color == MARAY_PNG_COLOR_RGB) return maray_hip_time_png_encode(device, d_rgb8, w, h, reps, ms_avg, stream_bytes);
+    return rc;
+}
+
+int maray_hip_png_palette(int device, const void *d_rgb8, uint32_t w, uint32_t h, void *stream, uint32_t *n_colors, uint8_t palette[768])
+{
+    return guard([&] {
+        REQUIRE(n_colors && palette && d_rgb8, "null argument");
+        *n_colors = 0;
+        REQUIRE(w && h, "empty image");
+        png_check_size(w, h);
+        PngEncoderLease E(device);
+        E->collect_colors((const unsigned char *)d_rgb8, (uint64_t)w * h, (hipStream_t)stream, false);
+        *n_colors = E->fetch_palette((hipStream_t)stream, palette);
+    });
+}
+
 // ---- animation (include/maray_hip.h) ---------------------------------------------------------------------------
 int maray_hip_frame_delta(int device, const void *d_prev, const void *d_cur, uint32_t w, uint32_t h, void *stream, uint32_t box[4])
 {

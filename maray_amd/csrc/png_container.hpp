@@ -45,6 +45,25 @@ inline std::vector<uint8_t> png_file(uint32_t w, uint32_t h, const uint8_t *z, s
     return out;
 }
 
+// The file of a w x h indexed-colour image (colour type 3) of bit depth 1, 2, 4 or 8 whose palette is the n <= 256 colours
+// palette[0 .. 3 n) and whose zlib stream is z[0 .. zn): signature, IHDR, PLTE, IDAT chunks, IEND.  No tRNS.
+inline std::vector<uint8_t> png_file_indexed(uint32_t w, uint32_t h, uint32_t depth, const uint8_t *palette, uint32_t n, const uint8_t *z, size_t zn)
+{
+    std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    out.reserve(zn + 12 * (zn >> 30) + 128 + 3 * (size_t)n);
+    std::vector<uint8_t> ihdr;
+    put_be32(ihdr, w); put_be32(ihdr, h);
+    ihdr.push_back((uint8_t)depth); ihdr.push_back(3); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
+    chunk(out, "IHDR", ihdr.data(), ihdr.size());
+    chunk(out, "PLTE", palette, 3 * (size_t)n);
+    for (size_t off = 0; off < zn || off == 0; off += (size_t)1 << 30) {
+        chunk(out, "IDAT", z + off, std::min<size_t>((size_t)1 << 30, zn - off));
+        if (zn == 0) break;
+    }
+    chunk(out, "IEND", nullptr, 0);
+    return out;
+}
+
 // ---- APNG (the animation writer, apng_device.cpp): a PNG whose IDAT image is frame 0 and whose later frames are complete
 // zlib streams of sub-rectangles in fdAT chunks.  fcTL and fdAT share one run of sequence numbers, 0, 1, 2, ...
 constexpr size_t PNG_CHUNK_MAX = (size_t)1 << 30;

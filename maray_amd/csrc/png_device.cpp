@@ -85,6 +85,8 @@ PngBandArgs band_args(PngEncoder &E, const unsigned char *src, uint32_t w, uint3
 
 }   // namespace
 
+void png_grow(unsigned char *&p, size_t &cap, size_t want) { grow(p, cap, want); }
+
 PngEncoder::PngEncoder(int dev) : device(dev), band_rows_env(band_rows_from_env())
 {
     HIP_TRY(hipSetDevice(dev));
@@ -98,6 +100,8 @@ PngEncoder::~PngEncoder()
     (void)hipSetDevice(device);
     if (own_stream) { (void)hipStreamSynchronize(own_stream); (void)hipStreamDestroy(own_stream); }
     (void)hipFree(slots); (void)hipFree(stream); (void)hipFree(meta); (void)hipFree(raster); (void)hipFree(filt); (void)hipFree(carry);
+    (void)hipFree(index); (void)hipFree(colors);
+    if (h_palette) (void)hipHostFree(h_palette);
     if (staging) (void)hipHostFree(staging);
     if (h_totals) (void)hipHostFree(h_totals);
     if (h_counts) (void)hipHostFree(h_counts);
@@ -331,13 +335,7 @@ void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t r
         // fixed: the band's bytes; dynamic: its tokens' bits, behind the header's
         const uint64_t total = dyn ? (a.header_bits + h_totals[0] + 7) / 8 : h_totals[0];
         if ((dyn ? h_totals[0] / 8 : total) > (uint64_t)a.n_segs * a.slot_bytes) throw Error{MARAY_E_INTERNAL, "device PNG encoder: a band's stream exceeds its bound"};
-        if (total > staging_cap) {
-            if (staging) HIP_TRY(hipHostFree(staging));
-            staging = nullptr; staging_cap = 0;
-            const size_t want = std::max<size_t>((size_t)total + (size_t)total / 4, (size_t)1 << 20);
-            HIP_TRY(hipHostMalloc((void **)&staging, want, hipHostMallocDefault));
-            staging_cap = want;
-        }
+        want_staging((size_t)total);
         HIP_TRY(hipMemcpyAsync(staging, a.stream, (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const size_t base = out.z.size();
@@ -351,6 +349,16 @@ void PngEncoder::encode_rows(const unsigned char *d_rgb8, uint32_t w, uint32_t r
         out.adler.append(p);
         g_bytes_to_host += total + 24;
     }
+}
+
+void PngEncoder::want_staging(size_t bytes)
+{
+    if (bytes <= staging_cap) return;
+    if (staging) HIP_TRY(hipHostFree(staging));
+    staging = nullptr; staging_cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, (size_t)1 << 20);
+    HIP_TRY(hipHostMalloc((void **)&staging, want, hipHostMallocDefault));
+    staging_cap = want;
 }
 
 void PngEncoder::encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,

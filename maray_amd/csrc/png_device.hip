@@ -22,6 +22,7 @@
 #include <string>
 
 #include "png_device.hpp"
+#include "png_indexed.hpp"
 
 namespace maray {
 
@@ -371,7 +372,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void maray_png_scan(const PngBandArgs a
         uint64_t tl = 0;
         uint32_t ta = 0, tb = 0;
         for (uint32_t v = 0; v < WAVES; v++) { tl += w_len[v]; ta += mod_adler(w_a[v]); tb += mod_adler(w_b[v]); }
-        const uint32_t n = (a.rows * (3u * a.w + 1u)) % PNG_ADLER_MOD;       // (a band has at most 2^30 filtered bytes)
+        const uint32_t row_bytes = a.row_bytes ? a.row_bytes : 3u * a.w + 1u;
+        const uint32_t n = (a.rows * row_bytes) % PNG_ADLER_MOD;             // (a band has at most 2^30 filtered bytes)
         a.totals[0] = tl;
         a.totals[1] = (uint64_t)n | ((uint64_t)(ta % PNG_ADLER_MOD) << 32);
         a.totals[2] = tb % PNG_ADLER_MOD;
@@ -772,14 +774,20 @@ __global__ __launch_bounds__(FC_BLOCK) void maray_png_filter_pick(const PngBandA
 void check_band(const PngBandArgs &a)
 {
     const bool dyn = a.codes == MARAY_PNG_CODES_DYNAMIC;
+    if (a.row_bytes) {                                      // an indexed band: fixed codes, filter 0, its own segments
+        const uint32_t rb = a.row_bytes - 1u;
+        if (!rb || dyn || a.filter || a.nseg != png_idx_row_segments(rb) || a.slot_bytes != png_idx_slot_bytes(rb) ||
+            (uint64_t)a.rows * a.row_bytes > 1ull << 30)
+            throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad indexed band arguments"};
+    }
     if (a.filter > MARAY_PNG_FILTER_PAETH || (a.filter && !a.row_filter) || (a.filter == MARAY_PNG_FILTER_ADAPTIVE && (!a.cost || ((uintptr_t)a.cost & 3))))
         throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad filter arguments"};
     if (!a.src || !a.slots || !a.lens || !a.adler || !a.offsets || !a.stream || !a.totals || !a.w || !a.rows ||
         (a.codes != MARAY_PNG_CODES_FIXED && !dyn) || (dyn && (!a.hist || a.header_bits > PNG_DYN_HEADER_MAX_BITS || ((uintptr_t)a.stream & 15))) ||
-        a.nseg != png_row_segments(a.w) || a.slot_bytes != (dyn ? png_slot_bytes_dyn(a.w) : png_slot_bytes(a.w)) ||
+        (!a.row_bytes && (a.nseg != png_row_segments(a.w) || a.slot_bytes != (dyn ? png_slot_bytes_dyn(a.w) : png_slot_bytes(a.w)))) ||
         a.slot_bytes > (dyn ? PNG_SLOT_MAX_DYN : PNG_SLOT_MAX) ||
         (uint64_t)a.rows * a.nseg != a.n_segs || ((uintptr_t)a.slots & 15) ||
-        (uint64_t)a.rows * (3ull * a.w + 1ull) > (dyn ? PNG_DYN_BAND_MAX_BYTES : 1ull << 30))
+        (!a.row_bytes && (uint64_t)a.rows * (3ull * a.w + 1ull) > (dyn ? PNG_DYN_BAND_MAX_BYTES : 1ull << 30)))
         throw Error{MARAY_E_INTERNAL, "device PNG encoder: bad band arguments"};
 }
 

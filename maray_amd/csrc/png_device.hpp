@@ -85,6 +85,9 @@ struct PngBandArgs {
     const unsigned char *above;     // the 3 w bytes of the row above the band's first row; null: the band starts at row 0
     uint32_t *cost;                 // MARAY_PNG_FILTER_ADAPTIVE: per segment and type t, [10 seg + 2 t] = the bytes and
                                     // [10 seg + 2 t + 1] = the token bits of the segment as a fixed-Huffman segment under t
+    // Indexed colour (png_indexed.hpp; else 0): src holds rows of row_bytes - 1 packed index bytes, nseg and slot_bytes are
+    // png_idx_row_segments and png_idx_slot_bytes of that, and a row has row_bytes filtered bytes instead of 3 w + 1
+    uint32_t row_bytes;
 };
 // The launchers dispatch on a.codes.  FIXED: maray_png_compress, maray_png_scan, maray_png_gather.  DYNAMIC: compress is
 // maray_png_histogram + maray_png_histogram_sum while a.table is null and maray_png_compress_dyn once it is set; scan is
@@ -144,7 +147,23 @@ struct PngEncoder {
     void encode_rendered(uint32_t w, uint32_t y0, uint32_t y1, hipStream_t st,
                          const std::function<void(uint32_t, uint32_t, unsigned char *, hipStream_t)> &render, PngPiece &out,
                          uint32_t codes = MARAY_PNG_CODES_FIXED, uint32_t filter = MARAY_PNG_FILTER_NONE);
+    void want_staging(size_t bytes);                             // `staging`, grown to hold `bytes`
+
+    // ---- indexed colour (png_indexed.hpp; the methods are png_indexed.cpp's) ----
+    unsigned char *index = nullptr; size_t index_cap = 0;       // a band's packed index rows
+    unsigned char *colors = nullptr; size_t colors_cap = 0;     // the palette (1 + 256 words), then the collecting blocks' slabs
+    uint32_t *h_palette = nullptr;                               // pinned host: 1 + 256 words
+    // the distinct colours of npix pixels at d_rgb8 into the encoder's palette, enqueued on st; add: to the ones it holds
+    void collect_colors(const unsigned char *d_rgb8, uint64_t npix, hipStream_t st, bool add);
+    // waits for st and brings the palette to the host (1,028 bytes): the number of colours, 257 for more than 256, and for up
+    // to 256 their R, G, B in ascending order
+    uint32_t fetch_palette(hipStream_t st, uint8_t rgb[768]);
+    // encode_rows for an indexed file: the rows' indices into the palette the encoder holds (n_colors of them), packed and
+    // compressed band by band
+    void encode_rows_indexed(const unsigned char *d_rgb8, uint32_t w, uint32_t rows, uint32_t n_colors, hipStream_t st, PngPiece &out);
 };
+// p, grown to `want` bytes of device memory (what it held is gone)
+void png_grow(unsigned char *&p, size_t &cap, size_t want);
 
 // An encoder of `device`: one an earlier call left, or a new one (MARAY_PNG_BAND_ROWS is read here: a kept encoder made
 // under another value is not handed out).  release() keeps up to two per device for the next call.
@@ -169,6 +188,11 @@ void png_count_bytes_to_host(uint64_t n);
 std::vector<uint8_t> png_close_stream(uint32_t h_end, const std::vector<const PngPiece *> &pieces);
 // The file: png_close_stream of pieces that cover [0, h), in the container (png_container.hpp).
 std::vector<uint8_t> png_assemble(uint32_t w, uint32_t h, const std::vector<const PngPiece *> &pieces);
+// The indexed file (png_indexed.cpp): the same stream around pieces of packed index rows, the palette's n colours in PLTE
+std::vector<uint8_t> png_assemble_indexed(uint32_t w, uint32_t h, const uint8_t *palette, uint32_t n, const std::vector<const PngPiece *> &pieces);
+// png_time_kernels with a colour mode other than MARAY_PNG_COLOR_RGB (png_indexed.cpp): the colour kernels, then the indexed
+// band's or, for MARAY_PNG_COLOR_AUTO on more than 256 colours, the truecolour band's; the palette is fetched once, untimed
+float png_time_kernels_color(int device, const unsigned char *d_rgb8, uint32_t w, uint32_t rows, uint32_t color, int reps, uint64_t *stream_bytes);
 // Average ms of compress + scan + gather over the caller's w x rows raster in device memory, as one band (measurements);
 // *stream_bytes = the bytes of the gathered stream.
 // With DYNAMIC codes the six kernels of a band whose code is fitted once, before the timed loop (the host's round trip is
