@@ -477,6 +477,27 @@ int maray_hip_cover_count(const maray_ctx *c, uint64_t *cover_launches);
 int maray_jit_cover_bits(const maray_program *prog, int32_t *values, uint32_t cap, uint32_t *n_values);
 int maray_jit_source_cover(const maray_program *prog, char **src_out);
 int maray_hip_debug_cover_words(maray_ctx *c, uint64_t *words, size_t cap, size_t *n_words, uint32_t *words_per_rect);
+/* Row words (MARAY_BACKEND_JIT, wherever a cover is taken -- or a census, for a program without cover bits -- for programs with
+ * up to 12 guard words and rectangles of 64 pixels, and launches whose guard groups are more than one row high).  Behind a
+ * set's cover maray_jit_rowscan forms the words of every (rectangle, row): the band's, without the census-eligible bits of
+ * leaves that are 0 on that row and with the cover bits of the ORs whose untainted leaves cover it.  maray_jit_rowscan_apply sets
+ * the ROW FLAG, one more free bit of the last guard word (a program without one gets no row words), in a fourth table for the
+ * rectangles where at least a quarter of the band's rows differ from the band.  A set with at least one flag is rendered by
+ * maray_jit_pixels_rw: maray_jit_pixels_cov, whose flagged rectangles take their words of the row at hand.  The module is built
+ * by the first launch that is due a scan (which waits for it), never when a context is created.  The tables count against the
+ * kept sets' budget; a set they do not fit takes none.  MARAY_JIT_ROW_WORDS=0 in the environment when the context is created:
+ * none of it (rasters are identical either way; not part of a code key).
+ * maray_hip_rowscan_count: maray_jit_rowscan launches the context has enqueued.
+ * maray_jit_rowwords_flag: the row flag's bit, -1 when the program gets no row words.  maray_jit_source_rowwords: the two
+ * kernels' source ("" when it gets none; free with maray_free).  Neither needs a GPU.
+ * maray_hip_debug_row_words (test access): of the set the most recent launch used, the fourth table (like
+ * maray_hip_debug_cover_words) and the row words, n_gwords per (row of the call, rectangle); *n_xbits = *n_rwords = 0 for a set
+ * that has been through no scan; *used = 1 when that launch ran maray_jit_pixels_rw. */
+int maray_hip_rowscan_count(const maray_ctx *c, uint64_t *rowscan_launches);
+int maray_jit_rowwords_flag(const maray_program *prog, int32_t *flag_bit);
+int maray_jit_source_rowwords(const maray_program *prog, char **src_out);
+int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t *n_xbits, uint64_t *rwords, size_t rcap, size_t *n_rwords,
+                              uint32_t *words_per_rect, int *used);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

@@ -201,6 +201,10 @@ def lib():
         'maray_jit_cover_bits': (C.c_int, [C.POINTER(Program), vp, u32, C.POINTER(u32)]),
         'maray_jit_source_cover': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
         'maray_hip_debug_cover_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)]),
+        'maray_hip_rowscan_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_jit_rowwords_flag': (C.c_int, [C.POINTER(Program), C.POINTER(C.c_int32)]),
+        'maray_jit_source_rowwords': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
+        'maray_hip_debug_row_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32), C.POINTER(C.c_int)]),
         'maray_hip_ctx_free': (None, [vp]),
         'maray_hip_render_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
         'maray_hip_render_tiles': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, TILE_FN, vp]),
@@ -558,6 +562,22 @@ class Tape:
         finally:
             lib().maray_free(p)
 
+    def rowwords_flag(self):
+        """maray_jit_rowwords_flag: the row flag's position in a rectangle's guard words, -1 when the program gets no row words."""
+        b = C.c_int32()
+        _check(lib().maray_jit_rowwords_flag(C.byref(self.program), C.byref(b)))
+        return b.value
+
+    @property
+    def jit_source_rowwords(self):
+        """Source of maray_jit_pixels_rw and maray_jit_rowscan; '' when the program gets no row words."""
+        p = C.c_void_p()
+        _check(lib().maray_jit_source_rowwords(C.byref(self.program), C.byref(p)))
+        try:
+            return C.string_at(p).decode()
+        finally:
+            lib().maray_free(p)
+
     def refine_arrays(self):
         """(consts, ops, n_slots) of the REFINE section as numpy copies; None when the program has none."""
         r = self.refine
@@ -797,6 +817,24 @@ class Context:
         out = np.zeros(n.value, np.uint64)
         _check(lib().maray_hip_debug_cover_words(self._h, out.ctypes.data, n.value, C.byref(n), C.byref(per)))
         return out.reshape(-1, per.value)
+
+    @property
+    def rowscan_count(self):
+        """maray_jit_rowscan launches this context has enqueued so far (maray_hip_rowscan_count)."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_rowscan_count(self._h, C.byref(n)))
+        return n.value
+
+    def debug_row_words(self):
+        """Test access (maray_hip_debug_row_words): of the set the last launch used, (xbits, rwords, used): the fourth table of
+        guard words, (rectangles, words per rectangle) uint64 with the row flags; the row words, (rows x rectangles per row, words
+        per rectangle), of which only the flagged rectangles' are meaningful; whether that launch ran maray_jit_pixels_rw.
+        Both arrays are empty for a set that has been through no row scan."""
+        nx, nr, per, used = C.c_size_t(), C.c_size_t(), C.c_uint32(), C.c_int()
+        _check(lib().maray_hip_debug_row_words(self._h, None, 0, C.byref(nx), None, 0, C.byref(nr), C.byref(per), C.byref(used)))
+        xb, rw = np.zeros(nx.value, np.uint64), np.zeros(nr.value, np.uint64)
+        _check(lib().maray_hip_debug_row_words(self._h, xb.ctypes.data, nx.value, C.byref(nx), rw.ctypes.data, nr.value, C.byref(nr), C.byref(per), C.byref(used)))
+        return xb.reshape(-1, per.value), rw.reshape(-1, per.value), bool(used.value)
 
     def debug_guard_words(self):
         """Test access (maray_hip_debug_guard_words): the guard words of the set the last launch used, (rectangles, words per

@@ -1700,6 +1700,43 @@ int maray_hip_debug_cover_words(maray_ctx *c, uint64_t *words, size_t cap, size_
     });
 }
 
+int maray_hip_rowscan_count(const maray_ctx *c, uint64_t *rowscan_launches)
+{
+    return guard([&] { REQUIRE(c && c->backend && rowscan_launches, "null argument"); *rowscan_launches = c->backend->rowscan_count(); });
+}
+
+int maray_jit_rowwords_flag(const maray_program *prog, int32_t *flag_bit)
+{
+    return guard([&] {
+        REQUIRE(prog && flag_bit, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        *flag_bit = jit_rowwords_plan(loaded).flag_bit;
+    });
+}
+
+int maray_jit_source_rowwords(const maray_program *prog, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        const std::string s = jit_source_rowwords(loaded);
+        *src_out = (char *)malloc(s.size() + 1);
+        REQUIRE(*src_out, "out of memory");
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
+int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t *n_xbits, uint64_t *rwords, size_t rcap, size_t *n_rwords,
+                              uint32_t *words_per_rect, int *used)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend && n_xbits && n_rwords && words_per_rect && used && (xbits || !xcap) && (rwords || !rcap), "null argument");
+        *n_xbits = c->backend->debug_row_words(xbits, xcap, rwords, rcap, n_rwords, words_per_rect, used);
+    });
+}
+
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }
 
 int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels)

@@ -49,6 +49,11 @@ struct Backend {
     // where it ran maray_jit_pixels_cov (maray_hip_debug_cover_words)
     virtual uint64_t cover_count() const { return 0; }
     virtual size_t debug_cover_words(uint64_t *, size_t, uint32_t *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
+    // maray_jit_rowscan launches enqueued so far (maray_hip_rowscan_count), and the fourth table and the row words of the set the
+    // last launch used (maray_hip_debug_row_words): returns the words of xbits and *n_rwords, copies at most the caps; 0 and 0 for
+    // a set that has been through no row scan
+    virtual uint64_t rowscan_count() const { return 0; }
+    virtual size_t debug_row_words(uint64_t *, size_t, uint64_t *, size_t, size_t *, uint32_t *, int *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.
@@ -117,6 +122,16 @@ std::string jit_source_cover(const maray_program &prog, CoverPlan *plan = nullpt
 // its code object (null when the source is empty): a module and a cache entry of its own (<key>.mrcv), like jit_code_census'
 struct JitCoverCode { std::vector<char> code; uint32_t n_cover = 0; };      // n_cover: reductions with a bit (2 flag bytes each per rectangle)
 std::shared_ptr<const JitCoverCode> jit_code_cover(const maray_program &prog);
+// The row words of a program (jit_source.cpp, "maray_jit_rowscan"): flag_bit = the free bit of the last guard word that says "this
+// rectangle's words are taken per row" (-1: the program gets no row words), the words per rectangle and the reductions with a cover bit
+struct RowWordsPlan { int32_t flag_bit = -1; uint32_t n_words = 0, n_cover = 0; };
+RowWordsPlan jit_rowwords_plan(const maray_program &prog);
+// maray_jit_pixels_rw + maray_jit_rowscan (one module); "" when the program gets no row words
+std::string jit_source_rowwords(const maray_program &prog, RowWordsPlan *plan = nullptr, int min_waves = 0);
+// its code object (null when the source is empty): a module and a cache entry of its own (<key>.mrrw), like jit_code_cover's.  Built by the
+// first launch that wants it, never when a context is created
+struct JitRowWordsCode { std::vector<char> code; int32_t flag_bit = -1; };
+std::shared_ptr<const JitRowWordsCode> jit_code_rowwords(const maray_program &prog);
 std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
 std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error

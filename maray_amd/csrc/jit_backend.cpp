@@ -25,6 +25,7 @@
 #include "jit_parts.hpp"
 #include "maray_hip.h"
 #include "row_reuse.hpp"
+#include "rowwords.hpp"
 #include "shutter.hpp"
 
 namespace maray {
@@ -50,8 +51,12 @@ struct RowTables {
     unsigned long long *cbits = nullptr; size_t cbits_cap = 0;      // gbits with the bits the census cleared: what the launches of a set read once it is through (maray_jit_census_apply)
     unsigned long long *vbits = nullptr; size_t vbits_cap = 0;      // cbits with cover bits in place of the leaves of ORs that are 1 on every pixel of a rectangle (maray_jit_cover_apply)
     unsigned char *cflags = nullptr; size_t cflags_cap = 0;         // the cover's flags, 2 per rectangle and reduction with a bit (maray_jit_cover)
+    unsigned long long *rwords = nullptr; size_t rwords_cap = 0;    // the words of every (row, rectangle): the band's words refined on that row (maray_jit_rowscan); read only for flagged rectangles
+    unsigned char *changed = nullptr; size_t changed_cap = 0;       // per rectangle and row of its band: the row's words differ from the band's
+    unsigned long long *xbits = nullptr; size_t xbits_cap = 0;      // vbits (cbits for a program without cover bits) with the row flag of the rectangles that take their words per row (maray_jit_rowscan_apply)
     void release() {
         (void)hipFree(yvals); (void)hipFree(gbits); (void)hipFree(order); (void)hipFree(hits); (void)hipFree(cbits); (void)hipFree(vbits); (void)hipFree(cflags);
+        (void)hipFree(rwords); (void)hipFree(changed); (void)hipFree(xbits);
         *this = RowTables{};
     }
 };
@@ -94,7 +99,28 @@ struct JitBackend final : Backend {
     // the cover module's parameter table: written when it is behind the values a launch of one of its kernels renders with
     hipDeviceptr_t d_par_cover = nullptr;
     uint64_t par_serial = 1, par_cover_serial = 0;
-    bool last_cov = false;              // the most recent launch ran maray_jit_pixels_cov over vbits
+    bool last_cov = false;              // the most recent launch ran maray_jit_pixels_cov over vbits (or maray_jit_pixels_rw over a covered set's xbits: vbits with row flags)
+    // maray_jit_rowscan + maray_jit_pixels_rw (jit_source_rowwords) and maray_jit_rowscan_apply (rowwords.hip): the row scan is taken
+    // once per kept filling of a set, behind its cover; a set in which the apply kernel flagged at least one rectangle is rendered
+    // by maray_jit_pixels_rw over xbits and rwords.  The module is built and loaded by the first launch that is due a scan
+    // (rowwords_module): a context's creation and a one-shot render never pay for it.
+    std::shared_ptr<const JitRowWordsCode> code_rw;
+    hipModule_t mod_rw = nullptr;
+    hipFunction_t f_rowscan = nullptr, f_pix_rw = nullptr;
+    bool rw_on = true;                  // MARAY_JIT_ROW_WORDS=0: none of this (read once, when the context is created; in no code key)
+    bool rw_asked = false;              // the module has been asked for (whether or not the program gets one)
+    unsigned rw_threshold = 0;          // MARAY_ROW_WORDS_T: changed rows from which a rectangle is flagged (0: a quarter of the band's rows); a measurement knob
+    uint64_t n_rowscan = 0;
+    CoverState rw_state[RowReuse::N_SETS] = {};      // the flag count of a set's apply kernel, like the cover's count
+    hipEvent_t rw_ev[RowReuse::N_SETS] = {};
+    unsigned *d_rw_n = nullptr, *h_rw_n = nullptr;          // one word per set
+    size_t set_rw_n[RowReuse::N_SETS] = {};         // row words each set's last scan covered
+    hipDeviceptr_t d_par_rw = nullptr;
+    uint64_t par_rw_serial = 0;
+    bool last_rw = false;               // the most recent launch ran maray_jit_pixels_rw
+    // the program, kept for the lazy build (P's arrays are not the context's to keep)
+    std::vector<double> own_consts, own_ranges;
+    std::vector<uint64_t> own_row_ops, own_pix_ops;
     uint32_t ss = 1;                    // samples per output pixel and axis: > 1 launches maray_jit_pixels_ss (launch_ss)
     std::shared_ptr<const std::vector<char>> code_ss;
     hipModule_t mod_ss = nullptr;
@@ -138,6 +164,10 @@ struct JitBackend final : Backend {
         if (mod_refine) (void)hipModuleUnload(mod_refine);
         if (mod_census) (void)hipModuleUnload(mod_census);
         if (mod_cover) (void)hipModuleUnload(mod_cover);
+        if (mod_rw) (void)hipModuleUnload(mod_rw);
+        for (hipEvent_t e : rw_ev) if (e) (void)hipEventDestroy(e);
+        (void)hipFree(d_rw_n);
+        if (h_rw_n) (void)hipHostFree(h_rw_n);
         for (hipEvent_t e : cover_ev) if (e) (void)hipEventDestroy(e);
         (void)hipFree(d_cover_n);
         if (h_cover_n) (void)hipHostFree(h_cover_n);
@@ -226,6 +256,21 @@ struct JitBackend final : Backend {
         } else if (has_sin) slow = make_tape_backend(dev, prog, tex, n_tex, false);     // drains the tiles the pixel kernel defers; other programs never defer
         P = prog;
         P.consts = nullptr; P.row_ops = nullptr; P.pix_ops = nullptr;
+        if (const char *e_ = getenv("MARAY_JIT_ROW_WORDS")) if (e_[0] == '0') rw_on = false;
+        // two hooks for tests and measurements, taken only when the whole string is a number in range: the threshold of
+        // maray_jit_rowscan_apply (1 .. 128 rows), and the byte budget of the kept sets, row words included (row_reuse.hpp)
+        auto number = [](const char *name, unsigned long long lo, unsigned long long hi, unsigned long long *v) {
+            const char *e_ = getenv(name);
+            if (!e_ || !e_[0]) return false;
+            char *end = nullptr;
+            const unsigned long long x = strtoull(e_, &end, 10);
+            if (*end || e_[0] == '-' || x < lo || x > hi) return false;
+            *v = x;
+            return true;
+        };
+        unsigned long long knob = 0;
+        if (number("MARAY_ROW_WORDS_T", 1, 128, &knob)) rw_threshold = (unsigned)knob;
+        if (number("MARAY_ROW_KEPT_BYTES", 0, (unsigned long long)RowReuse::MAX_BYTES, &knob)) reuse.max_bytes = (size_t)knob;
         if (prog.n_row_ops) {
             HIP_TRY(hipModuleLoadData(&mod_rows, code->rows.data()));
             HIP_TRY(hipModuleGetFunction(&f_rows, mod_rows, "maray_jit_rows"));
@@ -254,6 +299,14 @@ struct JitBackend final : Backend {
                 HIP_TRY(hipHostMalloc((void **)&h_cover_n, RowReuse::N_SETS * sizeof(unsigned), hipHostMallocDefault));
                 lap("load COVER module");
             }
+            // row words: wherever a census is taken, for rectangles one pass wide whose words are fetched per strip; the program is
+            // kept for the module's build, which the first launch that is due a scan asks for
+            if (rw_on && f_census && guard_sub == 4 && n_gwords <= GW_INLINE_MAX && guard_rows > 1) {
+                own_consts.assign(prog.consts, prog.consts + prog.n_consts);
+                own_row_ops.assign(prog.row_ops, prog.row_ops + prog.n_row_ops);
+                own_pix_ops.assign(prog.pix_ops, prog.pix_ops + prog.n_pix_ops);
+                if (prog.n_params && prog.param_ranges) own_ranges.assign(prog.param_ranges, prog.param_ranges + 2 * (size_t)prog.n_params);
+            } else rw_on = false;
         }
         if (prog.n_params) {
             param_values.assign(prog.n_params, NAN);
@@ -341,6 +394,57 @@ struct JitBackend final : Backend {
         par_cover_serial = par_serial;
     }
 
+    // the row-word module's table, likewise
+    void send_params_rw(hipStream_t st) {
+        if (!d_par_rw || par_rw_serial == par_serial) return;
+        double *slot = ring.take();
+        const size_t bytes = param_values.size() * sizeof(double);
+        memcpy(slot, param_values.data(), bytes);
+        HIP_TRY(hipMemcpyHtoDAsync(d_par_rw, slot, bytes, st));
+        ring.sent(st);
+        par_rw_serial = par_serial;
+    }
+
+    // The row-word module: built (a helper process, or read from the cache) and loaded by the first launch that is due a row
+    // scan -- that launch waits for it; until then, and for a program that gets none, launches are what they were.  Asked for
+    // once.  The context's handles are set only when everything is in place; a build or a load that fails leaves the context
+    // without row words -- the launch that asked goes on as it would with the knob off, and says so once on stderr (the
+    // module is an optimisation of launches that are correct without it: a render must not fail where knob-off succeeds).
+    void rowwords_module() {
+        if (rw_asked) return;
+        rw_asked = true;
+        hipModule_t m = nullptr;
+        unsigned *dn = nullptr, *hn = nullptr;
+        try {
+            maray_program Q = P;
+            Q.consts = own_consts.data(); Q.row_ops = own_row_ops.data(); Q.pix_ops = own_pix_ops.data();
+            Q.param_ranges = own_ranges.empty() ? nullptr : own_ranges.data();
+            std::shared_ptr<const JitRowWordsCode> c = jit_code_rowwords(Q);
+            if (!c || (uint32_t)c->flag_bit / 64 != n_gwords - 1) { rw_on = false; return; }       // the program gets none
+            hipFunction_t fs = nullptr, fp = nullptr;
+            hipDeviceptr_t par = nullptr;
+            HIP_TRY(hipModuleLoadData(&m, c->code.data()));
+            HIP_TRY(hipModuleGetFunction(&fs, m, "maray_jit_rowscan"));
+            HIP_TRY(hipModuleGetFunction(&fp, m, "maray_jit_pixels_rw"));
+            if (P.n_params) {
+                size_t bytes = 0;
+                HIP_TRY(hipModuleGetGlobal(&par, &bytes, m, "mr_par_tab"));
+                if (bytes != (size_t)P.n_params * sizeof(double)) throw Error{MARAY_E_INTERNAL, "parameter table of a module has another size than the program"};
+            }
+            HIP_TRY(hipMalloc((void **)&dn, RowReuse::N_SETS * sizeof(unsigned)));
+            HIP_TRY(hipHostMalloc((void **)&hn, RowReuse::N_SETS * sizeof(unsigned), hipHostMallocDefault));
+            code_rw = c; mod_rw = m; f_rowscan = fs; f_pix_rw = fp; d_rw_n = dn; h_rw_n = hn; d_par_rw = par;
+            par_rw_serial = 0;          // behind whatever the context holds: sent in front of the module's first kernel
+        } catch (const Error &e) {
+            if (hn) (void)hipHostFree(hn);
+            (void)hipFree(dn);
+            if (m) (void)hipModuleUnload(m);
+            (void)hipGetLastError();
+            rw_on = false;
+            fprintf(stderr, "maray: no row words for this context (launches go on without them): %s\n", e.msg.c_str());
+        }
+    }
+
     // The set of ROW tables a launch reads, filled by maray_jit_rows on `st` unless a set already holds the outputs of this
     // launch's key: the geometry and the bits of the ROW-read parameters (with MARAY_JIT_ROW_REUSE=0 of all parameters, and
     // a launch that asks for a ROW pass runs it whatever the tables hold).  rows_pass == false never runs the kernel: the
@@ -408,6 +512,7 @@ struct JitBackend final : Backend {
             }
         }
         cover_state[s] = COVER_NONE;
+        rw_state[s] = COVER_NONE;
         if (refill) reuse.touch(s); else reuse.filled(s);      // the set carries its key only now: the kernel that fills it is enqueued
         last_gbits_n = set_gbits_n[s] = gb_n;
         return cur_set = s;
@@ -576,15 +681,61 @@ struct JitBackend final : Backend {
             else if (q == hipErrorNotReady) (void)hipGetLastError();      // not an error: the status is not left behind as HIP's last one
             else HIP_TRY(q);
         }
-        const bool use_cov = f_pix_cov && matched && reuse.sets[set].cover && cover_state[set] == COVER_SOME;
+        // The row scan (maray_jit_rowscan, jit_source_rowwords): the cover's launch once more, over the words the cover left (the
+        // census's for a program without cover bits), forms every (rectangle, row)'s own words; maray_jit_rowscan_apply flags the
+        // rectangles where enough rows differ from the band, in the set's fourth table, xbits.  Behind the cover's apply kernel on
+        // this stream, once per filling of a set; its tables count against the kept sets' budget and a set they do not fit takes
+        // none.  Not for launches whose guard groups are one row high.
+        if (rw_on && want_census && yrows > 1 && reuse.rowwords_due(set, matched, f_cover != nullptr)) {
+            rowwords_module();
+            const size_t words = set_gbits_n[set], rects = words / std::max<uint32_t>(n_gwords, 1);
+            const size_t rw_n = (size_t)rows_total * (rects / n_groups) * n_gwords, ch_n = rects * yrows;
+            if (f_rowscan && words && words <= 0xFFFFFFFFull / 64 && rects <= 0xFFFFFFFFull &&
+                reuse.rowwords_admit(set, (rw_n + words) * sizeof(unsigned long long) + ch_n)) {
+                ensure(T.rwords, T.rwords_cap, rw_n);
+                ensure(T.changed, T.changed_cap, ch_n);
+                ensure(T.xbits, T.xbits_cap, words);
+                if (!rw_ev[set]) HIP_TRY(hipEventCreateWithFlags(&rw_ev[set], hipEventDisableTiming));
+                HIP_TRY(hipMemsetAsync(T.changed, 0, ch_n, st));
+                HIP_TRY(hipMemsetAsync(d_rw_n + set, 0, sizeof(unsigned), st));
+                send_params_rw(st);
+                unsigned char *no8 = nullptr; double *no64 = nullptr; unsigned *fl = nullptr; const unsigned *no_order = nullptr;
+                const double *yv = T.yvals;
+                const unsigned long long *src = reuse.sets[set].cover ? T.vbits : T.cbits;
+                unsigned ww = w, yy0 = y0, tile_base = 0, row_base = 0, ntx = n_tx, rows = rows_total, rpw = 1;
+                unsigned long long *rwp = T.rwords;
+                unsigned char *chp = T.changed;
+                void *sargs[] = {&no8, &no64, &yv, &d_tex, &fl, &tile_base, &src, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &no_order, &rows, &rpw, &rwp, &chp};
+                HIP_TRY(hipModuleLaunchKernel(f_rowscan, gx, rows_total, 1, 256, 1, 1, 0, st, sargs, nullptr));
+                const unsigned threshold = rw_threshold ? rw_threshold : std::max(1u, yrows / 4u);
+                HIP_TRY((hipError_t)rowwords_apply_launch(src, T.changed, T.xbits, (unsigned)rects, n_gwords, yrows, threshold,
+                                                          1ull << ((uint32_t)code_rw->flag_bit % 64), d_rw_n + set, (void *)st));
+                HIP_TRY(hipMemcpyAsync(h_rw_n + set, d_rw_n + set, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipEventRecord(rw_ev[set], st));
+                n_rowscan++;
+                set_rw_n[set] = rw_n;
+                rw_state[set] = COVER_PENDING;
+            }
+            if (rw_asked) reuse.sets[set].rowwords = true;       // only now: the kernels are enqueued (or the set takes none: its state stays COVER_NONE)
+        }
+        if (reuse.sets[set].rowwords && rw_state[set] == COVER_PENDING && matched) {
+            const hipError_t q = hipEventQuery(rw_ev[set]);
+            if (q == hipSuccess) rw_state[set] = h_rw_n[set] ? COVER_SOME : COVER_EMPTY;
+            else if (q == hipErrorNotReady) (void)hipGetLastError();
+            else HIP_TRY(q);
+        }
+        const bool use_rw = f_pix_rw && matched && reuse.sets[set].rowwords && rw_state[set] == COVER_SOME;
+        const bool use_cov = !use_rw && f_pix_cov && matched && reuse.sets[set].cover && cover_state[set] == COVER_SOME;
         // launch order of the PIXEL kernel (maray_jit_order): once per key, from the set's guard bits, whether this launch
         // ran the ROW kernel or found them there; used by every later launch of that key (time_rows too)
         // the guard words this launch and its order read: the census's where the set has been through one
-        const unsigned long long *gwords = use_cov ? T.vbits : reuse.sets[set].census ? T.cbits : T.gbits;
+        const unsigned long long *gwords = use_rw ? T.xbits : use_cov ? T.vbits : reuse.sets[set].census ? T.cbits : T.gbits;
         // (the order reads the words this launch reads: vbits only for a set whose apply kernel is known to have set a bit)
         const unsigned long long *owords = gwords;
         if (use_cov) send_params_cover(st);
-        last_cov = use_cov;
+        if (use_rw) send_params_rw(st);
+        last_cov = use_cov || (use_rw && reuse.sets[set].cover);
+        last_rw = use_rw;
         const unsigned *row_order = nullptr;
         if (want_order && matched) {
             RowReuse::Set &S = reuse.sets[set];
@@ -616,8 +767,9 @@ struct JitBackend final : Backend {
             const unsigned long long *gb = gwords;               // indexed by the row of the whole call
             unsigned ntx = n_tx;
             unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
-            void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw};
-            HIP_TRY(hipModuleLaunchKernel(use_cov ? f_pix_cov : f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
+            const unsigned long long *rwp = T.rwords;            // (maray_jit_pixels_rw alone has the parameter)
+            void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw, &rwp};
+            HIP_TRY(hipModuleLaunchKernel(use_rw ? f_pix_rw : use_cov ? f_pix_cov : f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
         if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, T.yvals);   // no-op unless a tile was deferred
     }
@@ -689,6 +841,21 @@ struct JitBackend final : Backend {
     uint64_t census_count() const override { return n_census; }
     uint64_t cover_count() const override { return n_cover; }
     size_t debug_cover_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true, true); }
+    uint64_t rowscan_count() const override { return n_rowscan; }
+    size_t debug_row_words(uint64_t *xb, size_t xcap, uint64_t *rw, size_t rcap, size_t *n_rwords, uint32_t *per_rect, int *used) override {
+        if (!n_gwords || cur_set < 0 || !tabs[cur_set].gbits) throw Error{MARAY_E_ARG, "no guard words: a program without guards, or no launch yet"};
+        HIP_TRY(hipSetDevice(device));
+        if (have_last) HIP_TRY(hipStreamSynchronize(last_stream));
+        *per_rect = n_gwords;
+        *used = last_rw ? 1 : 0;
+        *n_rwords = 0;
+        if (!reuse.sets[cur_set].rowwords || rw_state[cur_set] == COVER_NONE) return 0;
+        const size_t n = last_gbits_n, nr = set_rw_n[cur_set];
+        if (xb && xcap) HIP_TRY(hipMemcpy(xb, tabs[cur_set].xbits, std::min(n, xcap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (rw && rcap) HIP_TRY(hipMemcpy(rw, tabs[cur_set].rwords, std::min(nr, rcap) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        *n_rwords = nr;
+        return n;
+    }
     size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, false); }
     size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true); }
     // the ROW pass's and the second bounds' words of the set the last launch used, or (census) the words that launch read

@@ -732,4 +732,58 @@ std::shared_ptr<const JitCoverCode> jit_code_cover(const maray_program &prog)
     return fut.get();
 }
 
+// The row-word module of a program (jit_source_rowwords: maray_jit_pixels_rw, maray_jit_rowscan): a sixth module, kept like the
+// cover's -- in the process and on disk under a key of its own (<key>.mrrw: the code object, the row flag's bit and a checksum;
+// -1 and no code: the program gets none) made of the program's name.  No context asks for it when it is created: the first
+// launch that is due a row scan does (JitBackend::launch), so a one-shot render neither builds nor waits for it.
+// MARAY_JIT_ROW_WORDS is in no key: it decides whether a context ever asks.
+std::shared_ptr<const JitRowWordsCode> jit_code_rowwords(const maray_program &prog)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_future<std::shared_ptr<const JitRowWordsCode>>> built;
+    std::string key;
+    {
+        const std::string name = program_name(prog) + "|rowwords";
+        key = hex128(fnv1a(name.data(), name.size(), 0xcbf29ce484222325ull), fnv1a(name.data(), name.size(), 0x84222325cbf29ce4ull));
+    }
+    std::promise<std::shared_ptr<const JitRowWordsCode>> mine;
+    std::shared_future<std::shared_ptr<const JitRowWordsCode>> fut;
+    bool build = false;
+    {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = built.find(key);
+        if (it != built.end()) fut = it->second;
+        else {
+            if (built.size() > 32) built.clear();
+            fut = mine.get_future().share(); built.emplace(key, fut); build = true;
+        }
+    }
+    if (!build) return fut.get();
+    try {
+        auto out = std::make_shared<JitRowWordsCode>();
+        const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrrw";
+        std::vector<char> blob;
+        if (!path.empty() && blob_read(path, blob) && blob.size() >= 4) {       // code object + the flag's bit (-1: no row words)
+            memcpy(&out->flag_bit, blob.data() + blob.size() - 4, 4);
+            blob.resize(blob.size() - 4);
+            out->code.swap(blob);
+        } else {
+            RowWordsPlan plan;
+            const std::string src = jit_source_rowwords(prog, &plan);
+            if (!src.empty()) compile_aside(src, "rowwords", "ROW-WORD", out->code);
+            out->flag_bit = src.empty() ? -1 : plan.flag_bit;
+            blob = out->code;
+            blob.insert(blob.end(), (const char *)&out->flag_bit, (const char *)&out->flag_bit + 4);
+            if (!path.empty()) blob_write(dir, path, blob);
+        }
+        if (out->code.empty() || out->flag_bit < 0 || out->flag_bit >= 64 * 1024) out.reset();       // nothing to launch
+        mine.set_value(out);
+    } catch (...) {
+        mine.set_exception(std::current_exception());
+        std::lock_guard<std::mutex> lk(m);
+        built.erase(key);                               // a failed build is not remembered (the waiters still see its error)
+    }
+    return fut.get();
+}
+
 }   // namespace maray

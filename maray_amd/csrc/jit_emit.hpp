@@ -286,6 +286,11 @@ struct Emitter {
     // tests the bit and takes MR_ALL without entering its loops.  Every line either form adds holds "mr_cv".
     bool cover = false, use_cover = false;
     std::vector<int32_t> cover_bit;
+    // PIXEL: the row scan (jit_source_rowwords, maray_jit_rowscan): `census` and `cover` both set, and what either records goes
+    // to wave-uniform registers of the pass instead of byte flags -- a leaf that is != 0 on a pixel of the row inside the
+    // picture sets its bit in mr_rwh<word>, a reduction whose untainted leaves cover the row sets bit j (its rank among those
+    // with a cover bit) of mr_rwcv.  A pass is one rectangle wide, so it sees all of its (rectangle, row).
+    bool rowscan = false;
     int32_t cover_of(int32_t id) const { return (cover || use_cover) && id >= 0 && (size_t)id < cover_bit.size() ? cover_bit[id] : -1; }
     explicit Emitter(const maray_program &p) : P(p) {}
 
@@ -742,7 +747,8 @@ struct Emitter {
                 if (cvbit >= 0 && cover) {
                     int32_t j = 0;
                     for (int32_t k = 0; k < id; k++) j += cover_of(k) >= 0;
-                    out += "    if (mr_lane == 0u && mr_cin != 0ull) { mr_cvf[" + std::to_string(2 * j) + "] = 1; if ((" + cvacc + " & mr_cin) != mr_cin) mr_cvf[" + std::to_string(2 * j + 1) + "] = 1; }\n";
+                    if (rowscan) out += "    if ((" + cvacc + " & mr_cin) == mr_cin) mr_rwcv |= " + std::to_string(1u << j) + "u;\n";
+                    else out +="    if (mr_lane == 0u && mr_cin != 0ull) { mr_cvf[" + std::to_string(2 * j) + "] = 1; if ((" + cvacc + " & mr_cin) != mr_cin) mr_cvf[" + std::to_string(2 * j + 1) + "] = 1; }\n";
                 }
                 ktab_block.clear();
                 if (rbool) be = racc; else e = racc;
@@ -803,6 +809,11 @@ struct Emitter {
                     const uint32_t bit = rp->reds[id].leaf_bit[rp->leaf[i]];
                     const std::string hit = rp->reds[id].boolean ? (r.kind == BOOL ? r.b : "mr_ne0(" + dbl(&r, "m", i, 0) + ")")
                                                                  : "mr_ballot(__double_as_longlong(" + dbl(&r, "m", i, 0) + ") != 0ll)";
+                    if (rowscan) {
+                        char hex[32];
+                        snprintf(hex, sizeof hex, "0x%llxull", 1ull << (bit % 64));
+                        out += "    if (mr_any(" + hit + " & mr_cin)) mr_rwh" + std::to_string(bit / 64) + " |= " + hex + ";\n";
+                    } else
                     out += "    if (mr_any(" + hit + " & mr_cin) && mr_lane == 0u) mr_chit[" + std::to_string(bit) + "] = 1;\n";
                     if (leaf_taint || taint || r.taint) census_mark(census_bad, bit);
                 }

@@ -850,7 +850,8 @@ static std::string tile_end(bool defer)
 // scalar loads, a sky loop of its own ...) are history: DESIGN.md section 7.1, profiles/r2_ablations.jsonl.
 // the kernel itself, from `head` (its name and parameters) to its closing brace, into S.E.out: maray_jit_pixels, and with the
 // emitter's use_cover flag set maray_jit_pixels_cov (jit_source_cover)
-static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs &K, const std::string &head)
+// (strip_fetch: the strip's guard fetch where it is not strip_guard_fetch()'s -- maray_jit_pixels_rw, jit_source_rowwords)
+static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs &K, const std::string &head, const std::string *strip_fetch = nullptr)
 {
     Emitter &E = S.E;
     const GuardWords g(S.n_gwords, S.sub);
@@ -861,7 +862,7 @@ static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs 
         E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
     };
     std::string &s = E.out;
-    s += head + S.texture_loads() + strip_guard_fetch(g) +
+    s += head + S.texture_loads() + (strip_fetch ? *strip_fetch : strip_guard_fetch(g)) +
          "    const bool mr_wide = rgb64 == nullptr;                                   // wide variants: element e of lane l is pixel x0 + 4 l + e, else x0 + 64 e + l\n"
          "    const unsigned mr_xl = mr_wide ? 4u * mr_lane : mr_lane, mr_xs = mr_wide ? 1u : 64u;\n"
          "    const unsigned mr_src = (mr_lane * 4u) / 3u, mr_shift = ((mr_lane * 4u) % 3u) * 8u;   // RGB8 packing of one 64-pixel run\n"
@@ -1169,6 +1170,181 @@ std::string jit_source_cover(const maray_program &P, CoverPlan *plan_out, int mi
         throw Error{MARAY_E_INTERNAL, "the cover kernels disagree about the constant table"};
     s += cover_apply_kernel(cs.plan);
     if (plan_out) *plan_out = cs.plan;
+    return S.splice_constants(MR_STORE_RUN);
+}
+
+// ---- maray_jit_rowscan, maray_jit_pixels_rw ------------------------------------------------------------------------------------
+// The row words of a program: a rectangle's guard words refined row by row.  The cover's words say what holds
+// on EVERY row of a rectangle; a shape whose edge is horizontal in the middle of a band leaves its rectangles mixed although
+// each single row is all inside or all outside.  maray_jit_rowscan forms, per (rectangle, row), the band's words without the
+// eligible leaf bits whose leaf is 0 on the row and with the cover bits of the ORs whose untainted leaves cover the row -- the
+// census's rule and the cover's, unchanged, one row at a time; maray_jit_pixels_rw reads them for the rectangles whose last
+// word carries the ROW FLAG, one more free bit of that word (cover_free_bits), set by maray_jit_rowscan_apply (rowwords.hip)
+// where enough rows differ from the band.
+//
+// Only for programs whose rectangles are one pass wide (64 pixels: a pass of the scan sees all of its (rectangle, row) and
+// needs no flags in memory) and whose words are fetched per strip (<= GW_INLINE_MAX): the others stay on the kernels above.
+// "" when the program gets no row words: no reduction, no eligible bit, no spare bit for the flag.
+namespace {
+// the strip's guard fetch of maray_jit_pixels_rw: strip_guard_fetch()'s, then each lane learns from its rectangle's last word
+// whether the rectangle is flagged (one cross-lane read), and where some lane's is (a ballot: wave-uniform) those lanes take
+// their word of this row from mr_rwords.  Row words are stored without the flag: it reaches no bit test.  A strip without a
+// flagged rectangle executes no load.
+std::string strip_guard_fetch_rw(const GuardWords &g, uint32_t flag_bit)
+{
+    const uint32_t fb = flag_bit % 64;
+    char hex[24];
+    snprintf(hex, sizeof hex, "0x%xu", 1u << (fb % 32));
+    return "    const unsigned long long mr_gbase0 = (unsigned long long)(gbits + ((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0) * " + g.tw + "u);\n"
+           "    const unsigned mr_gn = (n_tx - tile0 < tiles ? n_tx - tile0 : tiles) * " + g.tw + "u;       // <= 64: the host bounds `tiles`\n"
+           "    unsigned long long mr_gv = mr_lane < mr_gn ? ((const unsigned long long *)mr_gbase0)[mr_lane] : 0ull;\n"
+           "    {   // row words: lane i holds word i % " + g.nw + " of rectangle i / " + g.nw + " of the strip; the flag sits in that rectangle's last word\n"
+           "        const unsigned mr_rwr = mr_lane / " + g.nw + "u, mr_rwl = mr_rwr * " + g.nw + "u + " + std::to_string(g.n - 1) + "u;\n"
+           "        const unsigned mr_rwf = (unsigned)__builtin_amdgcn_ds_bpermute((int)((mr_rwl & 63u) * 4u), (int)(unsigned)(mr_gv" + (fb >= 32 ? " >> 32" : "") + "));\n"
+           "        const bool mr_rwt = mr_lane < mr_gn && (mr_rwf & " + hex + ") != 0u;\n"
+           "        if (mr_ballot(mr_rwt) != 0ull) {                                      // wave-uniform: some rectangle of the strip has row words\n"
+           "            if (mr_rwt) mr_gv = mr_rwords[(((size_t)(row_base + r) * n_tx + tile0) * " + std::to_string(g.sub) + "u + mr_rwr) * " + g.nw + "u + (mr_lane - mr_rwr * " + g.nw + "u)];\n"
+           "        }\n"
+           "    }\n" +
+           (g.sub > 1 ? "    const unsigned long long mr_gnz = mr_ballot(mr_gv != 0ull);            // which of the strip's words have a bit set\n" : "");
+}
+
+struct RowWordsSetup { CoverSetup cs; std::vector<uint64_t> eligible; int32_t flag_bit = -1; };
+
+RowWordsSetup rowwords_setup(const maray_program &P, const JitKnobs &K)
+{
+    RowWordsSetup rs;
+    const uint32_t n_gwords = jit_guard_words(P, K);
+    const GuardGeom geom = jit_guard_geom(P, K);
+    if (!n_gwords || n_gwords > GW_INLINE_MAX || geom.gw != 64u || geom.gh < 2u) return rs;
+    if (jit_source_census(P, &rs.eligible).empty() || rs.eligible.size() != n_gwords) { rs.eligible.clear(); return rs; }
+    rs.cs = cover_setup(P, K);
+    // the flag: the free bit behind the cover bits, if the last word has one more
+    const uint32_t n_cover = (uint32_t)rs.cs.plan.reds.size();
+    std::vector<int32_t> bits(n_cover + 1, -1);
+    const uint32_t n_pos = jit_guard_plan(P).n_pos;
+    if (cover_free_bits(n_pos, n_gwords, n_cover + 1, bits.data()) == n_cover + 1) rs.flag_bit = bits[n_cover];
+    for (uint32_t k = 0; k < n_cover; k++) if (rs.cs.plan.reds[k].bit != bits[k]) rs.flag_bit = -1;     // (the cover's bits are the first granted)
+    return rs;
+}
+}   // namespace
+
+RowWordsPlan jit_rowwords_plan(const maray_program &P)
+{
+    validate_program(P);
+    const RowWordsSetup rs = rowwords_setup(P, jit_knobs());
+    RowWordsPlan rp;
+    if (rs.flag_bit < 0) return rp;
+    rp.flag_bit = rs.flag_bit; rp.n_words = (uint32_t)rs.eligible.size(); rp.n_cover = (uint32_t)rs.cs.plan.reds.size();
+    return rp;
+}
+
+std::string jit_source_rowwords(const maray_program &P, RowWordsPlan *plan_out, int min_waves)
+{
+    if (plan_out) *plan_out = RowWordsPlan();
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    const RowWordsSetup rs = rowwords_setup(P, K);
+    if (rs.flag_bit < 0) return "";
+    const CoverSetup &cs = rs.cs;
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    if (!g.in_sgprs || g.sub != 4 || S.reductions.empty() || jit_wide_general(P, S.n_gwords, K)) return "";
+    E.cover_bit = cs.bit_of_red;
+    E.census_row_params = row_param_mask(P);
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; row words: the guard words of a rectangle, refined row by row; the row flag is bit " + std::to_string(rs.flag_bit) + "\n" +
+         PIXELS_PROLOGUE;
+    const size_t ktab0 = E.ktab_vals.size();
+    const char tail[] = "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw)";
+    std::string head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_pixels_rw(");
+    head.replace(head.find(tail), sizeof tail - 1, "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw, const unsigned long long *__restrict__ mr_rwords)");
+    const std::string fetch = strip_guard_fetch_rw(g, (uint32_t)rs.flag_bit);
+    E.use_cover = true;
+    pixels_kernel(S, P, K, head, &fetch);
+    E.use_cover = false;
+    // maray_jit_rowscan: the constant table and the label numbers start over, so that its section is that kernel's text too
+    const std::vector<double> table = E.ktab_vals;
+    E.ktab_vals.resize(ktab0);
+    E.ktab_block.clear();
+    E.red_serial = 0;
+    head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_rowscan(");
+    head.replace(head.find(tail), sizeof tail - 1, "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw, unsigned long long *__restrict__ mr_rwords, unsigned char *__restrict__ mr_changed)");
+    // the leaf bits of the reductions, per word: a rectangle without one has nothing to refine
+    std::vector<uint64_t> redmask(g.n, 0);
+    for (const RedPlan::Red &red : S.reductions.reds) for (uint32_t b : red.leaf_bit) if (b / 64 < g.n) redmask[b / 64] |= 1ull << (b % 64);
+    auto hex64 = [](uint64_t v) { char h[32]; snprintf(h, sizeof h, "0x%llxull", (unsigned long long)v); return std::string(h); };
+    std::string lane_mask = "    unsigned long long mr_rwm = 0ull;\n    switch (mr_lane % " + g.nw + "u) {\n", any_red, decl;
+    for (uint32_t j = 0; j < g.n; j++) {
+        const std::string k = std::to_string(j);
+        lane_mask += "    case " + k + ": mr_rwm = " + hex64(redmask[j]) + "; break;\n";
+        any_red += std::string(j ? " | " : "") + "(gq" + k + " & " + hex64(redmask[j]) + ")";
+        decl += "    mr_mask mr_rwh" + k + " = 0ull;\n";
+    }
+    s += "\n" + head + S.texture_loads() + strip_guard_fetch(g) +
+         "    (void)rgb8; (void)rgb64;\n" + lane_mask + "    }\n"
+         "    if (mr_ballot((mr_gv & mr_rwm) != 0ull) == 0ull) return;                  // no rectangle of the strip holds a leaf bit of a reduction\n"
+         "    for (unsigned t = 0; t < tiles; t++) {\n"
+         "    const unsigned x0 = (tile0 + t) * 256u;\n"
+         "    if (x0 >= w) break;\n"
+         "/*MR_KBASE*/" + tile_guard_fetch(g) +
+         sky_test(g) + "    continue;\n    }\n"
+         "    _Pragma(\"unroll 1\") for (unsigned e = 0; e < 4u; e++) {\n" + PIXELS_PASS_TABLES + pass_guard_words(g) +
+         "    const unsigned xw = x0 + 64u * e, x = xw + mr_lane;\n"
+         "    const double X = (double)x;\n"
+         "    double o0 = 0.0, o1 = 0.0, o2 = 0.0;\n"
+         "    float mr_defer = 0.0f;\n"
+         "    (void)X; (void)mr_defer;\n"
+         "    const mr_mask mr_cin = mr_ballot(x < w);                                 // the lanes inside the picture\n"
+         "    if (mr_cin == 0ull) continue;                                            // no pixel of the rectangle on this row: the band's words stand\n"
+         "    if ((" + any_red + ") == 0ull) continue;                                 // nothing to refine\n" +
+         decl +
+         "    unsigned mr_rwcv = 0u;\n";
+    {   // (the variant of a tile without a guard bit: emitted and dropped, as in jit_source_census)
+        const size_t keep = s.size();
+        E.td = "mr_d"; E.tm = "mr_m"; E.assume_guards_zero = true; E.rplan = nullptr;
+        E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+        s.resize(keep);
+    }
+    E.census = true; E.cover = true; E.rowscan = true;
+    E.td = "double"; E.tm = "mr_mask"; E.assume_guards_zero = false; E.rplan = &S.reductions;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    E.census = false; E.cover = false; E.rowscan = false;
+    s += "    (void)o0; (void)o1; (void)o2;\n"
+         "    // the row's words: the band's, without the eligible bits of leaves that are 0 on the row ...\n";
+    std::string differ, stores;
+    for (uint32_t j = 0; j < g.n; j++) {
+        const std::string k = std::to_string(j);
+        s += "    mr_mask mr_rw" + k + " = gq" + k + " & (mr_rwh" + k + " | " + hex64(~rs.eligible[j]) + ");\n";
+        differ += std::string(j ? " || " : "") + "mr_rw" + k + " != gq" + k;
+        stores += "        mr_rwq[" + k + "] = mr_rw" + k + ";\n";
+    }
+    s += "    // ... and, where the untainted leaves of an OR cover the row, with its cover bit in place of its own eligible leaf bits\n";
+    for (uint32_t j = 0; j < cs.plan.reds.size(); j++) {
+        const CoverPlan::Red &red = cs.plan.reds[j];
+        std::vector<uint64_t> clear(g.n, 0);
+        for (size_t k = 0; k < red.leaf_bit.size(); k++) if (red.leaf_eligible[k]) clear[red.leaf_bit[k] / 64] |= 1ull << (red.leaf_bit[k] % 64);
+        s += "    if ((mr_rwcv & " + std::to_string(1u << j) + "u) != 0u) {\n";
+        for (uint32_t wd = 0; wd < g.n; wd++) {
+            const uint64_t set = (uint32_t)red.bit / 64 == wd ? 1ull << ((uint32_t)red.bit % 64) : 0ull;
+            if (clear[wd] || set) s += "        mr_rw" + std::to_string(wd) + " = (mr_rw" + std::to_string(wd) + " & " + hex64(~clear[wd]) + ") | " + hex64(set) + ";\n";
+        }
+        s += "    }\n";
+    }
+    s += "    if (mr_lane == 0u) {                                                     // idempotent plain stores, one lane\n"
+         "        const size_t mr_rwi = ((size_t)(row_base + r) * n_tx + tile0 + t) * 4u + e;      // (row of the call, rectangle)\n"
+         "        unsigned long long *mr_rwq = mr_rwords + mr_rwi * " + g.nw + "u;\n" + stores +
+         "        mr_changed[((((size_t)((row_base + r) >> __builtin_ctz(yrows)) * n_tx + tile0 + t) * 4u + e) * yrows) + ((row_base + r) & (yrows - 1u))] = (" + differ + ") ? 1 : 0;\n"
+         "    }\n"
+         "    }\n"
+         "    }\n}\n";
+    if (E.ktab_vals.size() != table.size() || memcmp(E.ktab_vals.data(), table.data(), table.size() * sizeof(double)) != 0)
+        throw Error{MARAY_E_INTERNAL, "the row-word kernels disagree about the constant table"};
+    if (plan_out) { plan_out->flag_bit = rs.flag_bit; plan_out->n_words = g.n; plan_out->n_cover = (uint32_t)cs.plan.reds.size(); }
     return S.splice_constants(MR_STORE_RUN);
 }
 

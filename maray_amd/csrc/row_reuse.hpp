@@ -70,6 +70,8 @@ struct RowReuse {
         bool order = false;         // ... and the launch order computed from its guard bits
         bool cover = false;         // ... and the third table, in which a cover bit stands for the leaves of an OR that is 1 on every pixel of a rectangle (maray_jit_cover); set with or after `census`, withdrawn wherever it is
         bool census = false;        // ... and the second table of guard words the census made of them (maray_jit_census): without the bits of leaves that are zero on every pixel of a rectangle
+        bool rowwords = false;      // ... and the fourth table and the row words (maray_jit_rowscan, rowwords.hpp): set behind the cover (or the census, for a program without cover bits), withdrawn wherever `census` is
+        size_t rw_bytes = 0;        // device bytes of the row-word tables admitted for the set (rowwords_admit); they stay with its tables
         uint32_t launches = 0;      // launches that used the set under this key: the second one (the first that found it filled) computes the order
         uint64_t stamp = 0;         // last use (kept sets: least recently used goes first)
         size_t bytes = 0;           // kept sets: device bytes accounted to the set (0 = not in use)
@@ -105,6 +107,27 @@ struct RowReuse {
     // The cover (maray_jit_cover) reads the census'd words: due on the launch that takes the census or any later one that finds
     // the set through its census and not yet covered.  The caller sets Set::cover once the kernels are enqueued.
     bool cover_due(int s, bool matched) const { return enabled && matched && sets[s].keyed && sets[s].census && !sets[s].cover; }
+
+    // The row scan (maray_jit_rowscan) reads the cover's words: due on the launch that takes the cover or any later one that
+    // finds the set covered and not yet scanned; for a program without cover bits (has_cover == false) behind the census
+    // instead.  The caller sets Set::rowwords once the kernels are enqueued.
+    bool rowwords_due(int s, bool matched, bool has_cover) const {
+        return enabled && matched && sets[s].keyed && sets[s].census && (sets[s].cover || !has_cover) && !sets[s].rowwords;
+    }
+
+    // The row-word tables of set s, `bytes` of device memory, count against the budget of the kept sets: false when they do
+    // not fit -- the set then takes no row words; nothing is evicted for them.  Bytes admitted once stay admitted (the tables
+    // stay allocated with the set and go with it: drop(), or a take-over in place(), which keeps tables and accounting);
+    // only growth is added.  The scratch's tables are held to the same bound but, like its other tables, not accounted.
+    bool rowwords_admit(int s, size_t bytes) {
+        const size_t more = bytes > sets[s].rw_bytes ? bytes - sets[s].rw_bytes : 0;
+        const bool kept = s > 0 && sets[s].bytes;
+        const size_t add = kept ? more : bytes;             // (the scratch's tables are not in kept_bytes: all of them count here)
+        if (add > max_bytes || kept_bytes + add > max_bytes) return false;
+        if (kept) { sets[s].bytes += more; kept_bytes += more; }
+        sets[s].rw_bytes += more;
+        return true;
+    }
 
     bool was_seen(uint64_t h) const {
         for (uint64_t v : seen) if (v == h) return true;
@@ -157,7 +180,8 @@ struct RowReuse {
         sets[s].order = false;
         sets[s].census = false;
         sets[s].cover = false;
-        sets[s].launches = 0;                           // (touch() by filled() counts this launch)
+        sets[s].rowwords = false;
+        sets[s].launches = 0;                          // (touch() by filled() counts this launch)
         sets[s].key = key;
         return s;
     }
