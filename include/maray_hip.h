@@ -492,12 +492,17 @@ int maray_hip_debug_cover_words(maray_ctx *c, uint64_t *words, size_t cap, size_
  * kernels' source ("" when it gets none; free with maray_free).  Neither needs a GPU.
  * maray_hip_debug_row_words (test access): of the set the most recent launch used, the fourth table (like
  * maray_hip_debug_cover_words) and the row words, n_gwords per (row of the call, rectangle); *n_xbits = *n_rwords = 0 for a set
- * that has been through no scan; *used = 1 when that launch ran maray_jit_pixels_rw. */
+ * that has been through no scan; *used = 1 when that launch ran maray_jit_pixels_rw.
+ * maray_hip_debug_row_sets (test access): the kept sets of ROW tables of a MARAY_BACKEND_JIT context: the set the most recent
+ * launch used (0 = the scratch, -1 before any launch), how many sets are kept, the bytes accounted to them, their budget
+ * (MARAY_ROW_KEPT_BYTES), and the device bytes the kept sets' tables hold (every table's capacity times its element size).
+ * Host state only: it waits for nothing and changes nothing.  MARAY_E_ARG for an interpreter's context. */
 int maray_hip_rowscan_count(const maray_ctx *c, uint64_t *rowscan_launches);
 int maray_jit_rowwords_flag(const maray_program *prog, int32_t *flag_bit);
 int maray_jit_source_rowwords(const maray_program *prog, char **src_out);
 int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t *n_xbits, uint64_t *rwords, size_t rcap, size_t *n_rwords,
                               uint32_t *words_per_rect, int *used);
+int maray_hip_debug_row_sets(const maray_ctx *c, int32_t *set, uint32_t *kept_sets, uint64_t *kept_bytes, uint64_t *budget_bytes, uint64_t *held_bytes);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/
 enum {                         /* RenderMethod (src/lib.rs:1155-1173), extended */

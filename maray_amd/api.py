@@ -205,6 +205,7 @@ def lib():
         'maray_jit_rowwords_flag': (C.c_int, [C.POINTER(Program), C.POINTER(C.c_int32)]),
         'maray_jit_source_rowwords': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
         'maray_hip_debug_row_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32), C.POINTER(C.c_int)]),
+        'maray_hip_debug_row_sets': (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(u32), u64p, u64p, u64p]),
         'maray_hip_ctx_free': (None, [vp]),
         'maray_hip_render_rows': (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
         'maray_hip_render_tiles': (C.c_int, [vp, u32, u32, C.POINTER(u32), u32, vp, TILE_FN, vp]),
@@ -835,6 +836,15 @@ class Context:
         xb, rw = np.zeros(nx.value, np.uint64), np.zeros(nr.value, np.uint64)
         _check(lib().maray_hip_debug_row_words(self._h, xb.ctypes.data, nx.value, C.byref(nx), rw.ctypes.data, nr.value, C.byref(nr), C.byref(per), C.byref(used)))
         return xb.reshape(-1, per.value), rw.reshape(-1, per.value), bool(used.value)
+
+    def debug_row_sets(self):
+        """Test access (maray_hip_debug_row_sets): (set, kept_sets, kept_bytes, budget, held_bytes) of a MARAY_BACKEND_JIT context:
+        the set of ROW tables the last launch used (0 = the scratch, -1 before any launch), how many sets are kept, the bytes
+        accounted to them, their budget, and the device bytes the kept sets' tables hold.  Waits for nothing."""
+        s, n = C.c_int32(), C.c_uint32()
+        kept, budget, held = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().maray_hip_debug_row_sets(self._h, C.byref(s), C.byref(n), C.byref(kept), C.byref(budget), C.byref(held)))
+        return s.value, n.value, kept.value, budget.value, held.value
 
     def debug_guard_words(self):
         """Test access (maray_hip_debug_guard_words): the guard words of the set the last launch used, (rectangles, words per

@@ -1737,6 +1737,16 @@ int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t
     });
 }
 
+int maray_hip_debug_row_sets(const maray_ctx *c, int32_t *set, uint32_t *kept_sets, uint64_t *kept_bytes, uint64_t *budget_bytes, uint64_t *held_bytes)
+{
+    return guard([&] {
+        REQUIRE(c && c->backend && set && kept_sets && kept_bytes && budget_bytes && held_bytes, "null argument");
+        int s = -1;
+        c->backend->debug_row_sets(&s, kept_sets, kept_bytes, budget_bytes, held_bytes);
+        *set = s;
+    });
+}
+
 const char *maray_hip_kernel_name(const maray_ctx *c) { return (c && c->backend) ? c->backend->kernel_name() : ""; }
 
 int maray_hip_launch_counts(const maray_ctx *c, uint64_t *row_passes, uint64_t *order_kernels)

@@ -54,6 +54,9 @@ struct Backend {
     // a set that has been through no row scan
     virtual uint64_t rowscan_count() const { return 0; }
     virtual size_t debug_row_words(uint64_t *, size_t, uint64_t *, size_t, size_t *, uint32_t *, int *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
+    // The kept sets of ROW tables (maray_hip_debug_row_sets): the set the last launch used (-1 before any), how many sets are
+    // kept, the bytes accounted to them, the budget, and the device bytes their tables hold.  Host state only: no wait.
+    virtual void debug_row_sets(int *, uint32_t *, uint64_t *, uint64_t *, uint64_t *) const { throw Error{MARAY_E_ARG, "this context keeps no sets of ROW tables"}; }
     // The values of the program's parameters (n = its count, every value inside its range: checked by the caller) for the
     // launches enqueued after this call; kept on the host until then.  A launch copies changed values to the device on its
     // own stream, in front of its ROW pass.

@@ -203,6 +203,9 @@ struct FilterBackend final : Backend {
     size_t debug_row_words(uint64_t *xb, size_t xcap, uint64_t *rw, size_t rcap, size_t *n_rwords, uint32_t *per_rect, int *used) override {
         return inner->debug_row_words(xb, xcap, rw, rcap, n_rwords, per_rect, used);
     }
+    void debug_row_sets(int *set, uint32_t *kept_sets, uint64_t *kept_bytes, uint64_t *budget, uint64_t *held) const override {
+        inner->debug_row_sets(set, kept_sets, kept_bytes, budget, held);
+    }
 };
 
 }   // namespace

@@ -856,6 +856,19 @@ struct JitBackend final : Backend {
         *n_rwords = nr;
         return n;
     }
+    void debug_row_sets(int *set, uint32_t *kept_sets, uint64_t *kept_bytes, uint64_t *budget, uint64_t *held) const override {
+        *set = cur_set;
+        *kept_sets = (uint32_t)reuse.kept_sets;
+        *kept_bytes = reuse.kept_bytes;
+        *budget = reuse.max_bytes;
+        uint64_t n = 0;
+        for (int s = 1; s < RowReuse::N_SETS; s++) {
+            const RowTables &t = tabs[s];
+            n += t.yvals_cap * sizeof(double) + t.order_cap * sizeof(unsigned) + t.hits_cap + t.cflags_cap + t.changed_cap +
+                 (t.gbits_cap + t.cbits_cap + t.vbits_cap + t.rwords_cap + t.xbits_cap) * sizeof(unsigned long long);
+        }
+        *held = n;
+    }
     size_t debug_guard_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, false); }
     size_t debug_census_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true); }
     // the ROW pass's and the second bounds' words of the set the last launch used, or (census) the words that launch read

@@ -29,6 +29,19 @@ def test_every_declared_symbol_is_exported():
     assert not missing, missing
 
 
+def test_the_row_sets_accessor_is_declared_exported_and_bound():
+    """maray_hip_debug_row_sets (test access to a context's kept sets of ROW tables) is in the header, in the library and in the
+    binding, next to the other debug accessors."""
+    names = declared_functions()
+    debug = [n for n in names if n.startswith('maray_hip_debug_')]
+    assert debug == ['maray_hip_debug_census_words', 'maray_hip_debug_cover_words', 'maray_hip_debug_guard_words', 'maray_hip_debug_row_sets',
+                     'maray_hip_debug_row_words']
+    L = M.lib()
+    for n in debug:
+        assert getattr(L, n).restype is C.c_int and getattr(L, n).argtypes, n
+    assert len(L.maray_hip_debug_row_sets.argtypes) == 6 and hasattr(M.Context, 'debug_row_sets')
+
+
 def test_product_does_not_link_or_load_the_oracle():
     import subprocess
     out = subprocess.run(['ldd', M.lib_path()], capture_output=True, text=True).stdout

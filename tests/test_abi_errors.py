@@ -94,6 +94,7 @@ def test_null_arguments_are_errors_not_crashes():
     assert L.maray_hip_ctx_create(0, None, None, 0, None, None) == -1
     assert L.maray_hip_render_rows(None, 4, 4, 0, 4, None, None) == -1
     assert L.maray_png_write(None, None, 0, 0) == -1
+    assert L.maray_hip_debug_row_sets(None, None, None, None, None, None) == -1
     L.maray_scene_free(None); L.maray_tape_free(None); L.maray_hip_ctx_free(None); L.maray_free(None)
 
 
