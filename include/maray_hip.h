@@ -502,6 +502,20 @@ int maray_jit_rowwords_flag(const maray_program *prog, int32_t *flag_bit);
 int maray_jit_source_rowwords(const maray_program *prog, char **src_out);
 int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t *n_xbits, uint64_t *rwords, size_t rcap, size_t *n_rwords,
                               uint32_t *words_per_rect, int *used);
+/* The pre-pass (MARAY_BACKEND_JIT, for the programs that get row words): maray_jit_pixels_pp is maray_jit_pixels_rw with one
+ * addition on the fast RGB8 path.  A rectangle whose guard words -- of the row at hand, where it has row words -- are zero
+ * apart from cover bits has no shape-dependent pixel; a busy tile with such a rectangle renders those in one pass four pixels
+ * per lane and runs its narrow passes over the other rectangles only.  The module is built beside the row-word module by the
+ * launch that builds that one; where it is in place it renders every set that maray_jit_pixels_cov or maray_jit_pixels_rw
+ * rendered.  MARAY_JIT_PREPASS=0 in the environment when the context is created: none of it (rasters are identical either
+ * way; not part of a code key).
+ * maray_hip_prepass_count: launches of maray_jit_pixels_pp the context has enqueued.  maray_jit_source_prepass: the kernel's
+ * source ("" when the program gets none; free with maray_free); needs no GPU.
+ * maray_hip_deferred_count (test access): the 256-pixel tiles the most recent launch of a MARAY_BACKEND_JIT context handed to
+ * the interpreter (a Sin whose argument is huge); waits for the context's work.  0 for other contexts. */
+int maray_hip_deferred_count(maray_ctx *c, uint64_t *deferred_tiles);
+int maray_hip_prepass_count(const maray_ctx *c, uint64_t *prepass_launches);
+int maray_jit_source_prepass(const maray_program *prog, char **src_out);
 int maray_hip_debug_row_sets(const maray_ctx *c, int32_t *set, uint32_t *kept_sets, uint64_t *kept_bytes, uint64_t *budget_bytes, uint64_t *held_bytes);
 
 /* ---- render façade: gen_to_image / gen (src/lib.rs:1177-1213) -----------------*/

@@ -204,6 +204,9 @@ def lib():
         'maray_hip_rowscan_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         'maray_jit_rowwords_flag': (C.c_int, [C.POINTER(Program), C.POINTER(C.c_int32)]),
         'maray_jit_source_rowwords': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
+        'maray_hip_prepass_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_hip_deferred_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        'maray_jit_source_prepass': (C.c_int, [C.POINTER(Program), C.POINTER(vp)]),
         'maray_hip_debug_row_words': (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32), C.POINTER(C.c_int)]),
         'maray_hip_debug_row_sets': (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(u32), u64p, u64p, u64p]),
         'maray_hip_ctx_free': (None, [vp]),
@@ -579,6 +582,16 @@ class Tape:
         finally:
             lib().maray_free(p)
 
+    @property
+    def jit_source_prepass(self):
+        """Source of maray_jit_pixels_pp; '' when the program gets no pre-pass."""
+        p = C.c_void_p()
+        _check(lib().maray_jit_source_prepass(C.byref(self.program), C.byref(p)))
+        try:
+            return C.string_at(p).decode()
+        finally:
+            lib().maray_free(p)
+
     def refine_arrays(self):
         """(consts, ops, n_slots) of the REFINE section as numpy copies; None when the program has none."""
         r = self.refine
@@ -824,6 +837,20 @@ class Context:
         """maray_jit_rowscan launches this context has enqueued so far (maray_hip_rowscan_count)."""
         n = C.c_uint64()
         _check(lib().maray_hip_rowscan_count(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def prepass_count(self):
+        """Launches of maray_jit_pixels_pp this context has enqueued so far (maray_hip_prepass_count)."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_prepass_count(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def deferred_count(self):
+        """Tiles the most recent launch deferred to the interpreter (maray_hip_deferred_count); waits for the context's work."""
+        n = C.c_uint64()
+        _check(lib().maray_hip_deferred_count(self._h, C.byref(n)))
         return n.value
 
     def debug_row_words(self):

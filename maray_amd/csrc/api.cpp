@@ -1728,6 +1728,29 @@ int maray_jit_source_rowwords(const maray_program *prog, char **src_out)
     });
 }
 
+int maray_hip_prepass_count(const maray_ctx *c, uint64_t *prepass_launches)
+{
+    return guard([&] { REQUIRE(c && c->backend && prepass_launches, "null argument"); *prepass_launches = c->backend->prepass_count(); });
+}
+
+int maray_hip_deferred_count(maray_ctx *c, uint64_t *deferred_tiles)
+{
+    return guard([&] { REQUIRE(c && c->backend && deferred_tiles, "null argument"); *deferred_tiles = c->backend->deferred_count(); });
+}
+
+int maray_jit_source_prepass(const maray_program *prog, char **src_out)
+{
+    return guard([&] {
+        REQUIRE(prog && src_out, "null argument");
+        const maray_program loaded = load_program(prog);
+        validate_program(loaded);
+        const std::string s = jit_source_prepass(loaded);
+        *src_out = (char *)malloc(s.size() + 1);
+        REQUIRE(*src_out, "out of memory");
+        memcpy(*src_out, s.c_str(), s.size() + 1);
+    });
+}
+
 int maray_hip_debug_row_words(maray_ctx *c, uint64_t *xbits, size_t xcap, size_t *n_xbits, uint64_t *rwords, size_t rcap, size_t *n_rwords,
                               uint32_t *words_per_rect, int *used)
 {

@@ -53,6 +53,10 @@ struct Backend {
     // last launch used (maray_hip_debug_row_words): returns the words of xbits and *n_rwords, copies at most the caps; 0 and 0 for
     // a set that has been through no row scan
     virtual uint64_t rowscan_count() const { return 0; }
+    // launches of maray_jit_pixels_pp enqueued so far (maray_hip_prepass_count)
+    virtual uint64_t prepass_count() const { return 0; }
+    // tiles the most recent launch deferred to the interpreter (maray_hip_deferred_count, test access); waits for the context's work
+    virtual uint64_t deferred_count() { return 0; }
     virtual size_t debug_row_words(uint64_t *, size_t, uint64_t *, size_t, size_t *, uint32_t *, int *) { throw Error{MARAY_E_ARG, "this context keeps no guard words"}; }
     // The kept sets of ROW tables (maray_hip_debug_row_sets): the set the last launch used (-1 before any), how many sets are
     // kept, the bytes accounted to them, the budget, and the device bytes their tables hold.  Host state only: no wait.
@@ -135,6 +139,12 @@ std::string jit_source_rowwords(const maray_program &prog, RowWordsPlan *plan = 
 // first launch that wants it, never when a context is created
 struct JitRowWordsCode { std::vector<char> code; int32_t flag_bit = -1; };
 std::shared_ptr<const JitRowWordsCode> jit_code_rowwords(const maray_program &prog);
+// maray_jit_pixels_pp (jit_source.cpp): maray_jit_pixels_rw with a wide pre-pass of a busy tile's leafless rectangles; "" when
+// the program gets none (no row words, or a cover bit outside the last guard word)
+std::string jit_source_prepass(const maray_program &prog, int min_waves = 0);
+// its code object (null when the source is empty): a module and a cache entry of its own (<key>.mrpp), built beside jit_code_rowwords'
+struct JitPrepassCode { std::vector<char> code; };
+std::shared_ptr<const JitPrepassCode> jit_code_prepass(const maray_program &prog);
 std::string jit_source_samples(const maray_program &prog, uint32_t k, int min_waves = 0);   // supersampling PIXEL kernel (maray_jit_pixels_ss), k = 2, 4, 8
 std::shared_ptr<const std::vector<char>> jit_code_samples(const maray_program &prog, uint32_t k);   // its code object: built once, kept like jit_code_for's
 void jit_compile(const std::string &src, std::vector<char> &code, std::string &log);     // hiprtc, gfx950; throws Error

@@ -200,6 +200,8 @@ struct FilterBackend final : Backend {
     uint64_t cover_count() const override { return inner->cover_count(); }
     size_t debug_cover_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return inner->debug_cover_words(words, cap, per_rect); }
     uint64_t rowscan_count() const override { return inner->rowscan_count(); }
+    uint64_t prepass_count() const override { return inner->prepass_count(); }
+    uint64_t deferred_count() override { return inner->deferred_count(); }
     size_t debug_row_words(uint64_t *xb, size_t xcap, uint64_t *rw, size_t rcap, size_t *n_rwords, uint32_t *per_rect, int *used) override {
         return inner->debug_row_words(xb, xcap, rw, rcap, n_rwords, per_rect, used);
     }

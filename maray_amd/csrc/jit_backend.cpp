@@ -117,7 +117,17 @@ struct JitBackend final : Backend {
     size_t set_rw_n[RowReuse::N_SETS] = {};         // row words each set's last scan covered
     hipDeviceptr_t d_par_rw = nullptr;
     uint64_t par_rw_serial = 0;
-    bool last_rw = false;               // the most recent launch ran maray_jit_pixels_rw
+    bool last_rw = false;               // the most recent launch ran maray_jit_pixels_rw (or maray_jit_pixels_pp over a set with row words)
+    // maray_jit_pixels_pp (jit_source_prepass): maray_jit_pixels_rw with a wide pre-pass of a busy tile's leafless rectangles.  Asked
+    // for beside the row-word module (rowwords_module); where it is in place it takes the launches of maray_jit_pixels_cov (over
+    // vbits: no row flag is set there, so no row word is read) and of maray_jit_pixels_rw (over xbits and rwords)
+    std::shared_ptr<const JitPrepassCode> code_pp;
+    hipModule_t mod_pp = nullptr;
+    hipFunction_t f_pix_pp = nullptr;
+    bool pp_on = true;                  // MARAY_JIT_PREPASS=0: none of this (read once, when the context is created; in no code key)
+    uint64_t n_prepass = 0;             // launches that ran maray_jit_pixels_pp
+    hipDeviceptr_t d_par_pp = nullptr;
+    uint64_t par_pp_serial = 0;
     // the program, kept for the lazy build (P's arrays are not the context's to keep)
     std::vector<double> own_consts, own_ranges;
     std::vector<uint64_t> own_row_ops, own_pix_ops;
@@ -165,6 +175,7 @@ struct JitBackend final : Backend {
         if (mod_census) (void)hipModuleUnload(mod_census);
         if (mod_cover) (void)hipModuleUnload(mod_cover);
         if (mod_rw) (void)hipModuleUnload(mod_rw);
+        if (mod_pp) (void)hipModuleUnload(mod_pp);
         for (hipEvent_t e : rw_ev) if (e) (void)hipEventDestroy(e);
         (void)hipFree(d_rw_n);
         if (h_rw_n) (void)hipHostFree(h_rw_n);
@@ -257,6 +268,7 @@ struct JitBackend final : Backend {
         P = prog;
         P.consts = nullptr; P.row_ops = nullptr; P.pix_ops = nullptr;
         if (const char *e_ = getenv("MARAY_JIT_ROW_WORDS")) if (e_[0] == '0') rw_on = false;
+        if (const char *e_ = getenv("MARAY_JIT_PREPASS")) if (e_[0] == '0') pp_on = false;
         // two hooks for tests and measurements, taken only when the whole string is a number in range: the threshold of
         // maray_jit_rowscan_apply (1 .. 128 rows), and the byte budget of the kept sets, row words included (row_reuse.hpp)
         auto number = [](const char *name, unsigned long long lo, unsigned long long hi, unsigned long long *v) {
@@ -405,6 +417,45 @@ struct JitBackend final : Backend {
         par_rw_serial = par_serial;
     }
 
+    // the pre-pass module's table, likewise
+    void send_params_pp(hipStream_t st) {
+        if (!d_par_pp || par_pp_serial == par_serial) return;
+        double *slot = ring.take();
+        const size_t bytes = param_values.size() * sizeof(double);
+        memcpy(slot, param_values.data(), bytes);
+        HIP_TRY(hipMemcpyHtoDAsync(d_par_pp, slot, bytes, st));
+        ring.sent(st);
+        par_pp_serial = par_serial;
+    }
+
+    // The pre-pass module, from the build rowwords_module started beside the row-word module's.  A build or a load that fails
+    // leaves the context on maray_jit_pixels_cov / maray_jit_pixels_rw and says so once on stderr.
+    void prepass_module(std::future<std::shared_ptr<const JitPrepassCode>> &build) {
+        hipModule_t m = nullptr;
+        try {
+            std::shared_ptr<const JitPrepassCode> c = build.get();
+            if (!c) return;                             // the program gets none
+            hipFunction_t fp = nullptr;
+            hipDeviceptr_t par = nullptr;
+            HIP_TRY(hipModuleLoadData(&m, c->code.data()));
+            HIP_TRY(hipModuleGetFunction(&fp, m, "maray_jit_pixels_pp"));
+            if (P.n_params) {
+                size_t bytes = 0;
+                HIP_TRY(hipModuleGetGlobal(&par, &bytes, m, "mr_par_tab"));
+                if (bytes != (size_t)P.n_params * sizeof(double)) throw Error{MARAY_E_INTERNAL, "parameter table of a module has another size than the program"};
+            }
+            code_pp = c; mod_pp = m; f_pix_pp = fp; d_par_pp = par;
+            par_pp_serial = 0;
+        } catch (const Error &e) {
+            if (m) (void)hipModuleUnload(m);
+            (void)hipGetLastError();
+            fprintf(stderr, "maray: no pre-pass kernel for this context (launches go on without it): %s\n", e.msg.c_str());
+        } catch (const std::exception &e) {            // (out of the build's thread: no memory, no thread)
+            if (m) (void)hipModuleUnload(m);
+            fprintf(stderr, "maray: no pre-pass kernel for this context (launches go on without it): %s\n", e.what());
+        }
+    }
+
     // The row-word module: built (a helper process, or read from the cache) and loaded by the first launch that is due a row
     // scan -- that launch waits for it; until then, and for a program that gets none, launches are what they were.  Asked for
     // once.  The context's handles are set only when everything is in place; a build or a load that fails leaves the context
@@ -419,8 +470,13 @@ struct JitBackend final : Backend {
             maray_program Q = P;
             Q.consts = own_consts.data(); Q.row_ops = own_row_ops.data(); Q.pix_ops = own_pix_ops.data();
             Q.param_ranges = own_ranges.empty() ? nullptr : own_ranges.data();
-            std::shared_ptr<const JitRowWordsCode> c = jit_code_rowwords(Q);
-            if (!c || (uint32_t)c->flag_bit / 64 != n_gwords - 1) { rw_on = false; return; }       // the program gets none
+            // the pre-pass module beside it: two helper processes, one wait
+            std::future<std::shared_ptr<const JitPrepassCode>> pp_build;
+            if (pp_on) pp_build = std::async(std::launch::async, [&Q] { return jit_code_prepass(Q); });
+            std::shared_ptr<const JitRowWordsCode> c;
+            try { c = jit_code_rowwords(Q); }
+            catch (...) { if (pp_build.valid()) pp_build.wait(); throw; }
+            if (!c || (uint32_t)c->flag_bit / 64 != n_gwords - 1) { if (pp_build.valid()) pp_build.wait(); rw_on = false; return; }       // the program gets none
             hipFunction_t fs = nullptr, fp = nullptr;
             hipDeviceptr_t par = nullptr;
             HIP_TRY(hipModuleLoadData(&m, c->code.data()));
@@ -435,6 +491,7 @@ struct JitBackend final : Backend {
             HIP_TRY(hipHostMalloc((void **)&hn, RowReuse::N_SETS * sizeof(unsigned), hipHostMallocDefault));
             code_rw = c; mod_rw = m; f_rowscan = fs; f_pix_rw = fp; d_rw_n = dn; h_rw_n = hn; d_par_rw = par;
             par_rw_serial = 0;          // behind whatever the context holds: sent in front of the module's first kernel
+            if (pp_build.valid()) prepass_module(pp_build);
         } catch (const Error &e) {
             if (hn) (void)hipHostFree(hn);
             (void)hipFree(dn);
@@ -732,8 +789,11 @@ struct JitBackend final : Backend {
         const unsigned long long *gwords = use_rw ? T.xbits : use_cov ? T.vbits : reuse.sets[set].census ? T.cbits : T.gbits;
         // (the order reads the words this launch reads: vbits only for a set whose apply kernel is known to have set a bit)
         const unsigned long long *owords = gwords;
-        if (use_cov) send_params_cover(st);
-        if (use_rw) send_params_rw(st);
+        const bool use_pp = f_pix_pp && (use_rw || use_cov);
+        // (the table of the module whose kernel this launch runs, and of no other)
+        if (use_pp) { send_params_pp(st); n_prepass++; }
+        else if (use_cov) send_params_cover(st);
+        else if (use_rw) send_params_rw(st);
         last_cov = use_cov || (use_rw && reuse.sets[set].cover);
         last_rw = use_rw;
         const unsigned *row_order = nullptr;
@@ -767,9 +827,9 @@ struct JitBackend final : Backend {
             const unsigned long long *gb = gwords;               // indexed by the row of the whole call
             unsigned ntx = n_tx;
             unsigned rpw = 1;                                    // rows per wavefront: a parameter the kernel still has (jit_source.cpp, PIXELS_PROLOGUE)
-            const unsigned long long *rwp = T.rwords;            // (maray_jit_pixels_rw alone has the parameter)
+            const unsigned long long *rwp = T.rwords;            // (maray_jit_pixels_rw and maray_jit_pixels_pp alone have the parameter)
             void *args[] = {&p8, &p64, &yv, &d_tex, &fl, &tile_base, &gb, &ntx, &ww, &yy0, &n_yvals, &tiles, &blk_rows, &blk_stride, &row_base, &yrows, &row_order, &rows, &rpw, &rwp};
-            HIP_TRY(hipModuleLaunchKernel(use_rw ? f_pix_rw : use_cov ? f_pix_cov : f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
+            HIP_TRY(hipModuleLaunchKernel(use_pp ? f_pix_pp : use_rw ? f_pix_rw : use_cov ? f_pix_cov : f_pix, gx, rows, 1, 256, 1, 1, 0, st, args, nullptr));
         }
         if (has_sin) slow->render_flagged(w, rb, d8, d64, st, d_flags, T.yvals);   // no-op unless a tile was deferred
     }
@@ -842,6 +902,15 @@ struct JitBackend final : Backend {
     uint64_t cover_count() const override { return n_cover; }
     size_t debug_cover_words(uint64_t *words, size_t cap, uint32_t *per_rect) override { return debug_words(words, cap, per_rect, true, true); }
     uint64_t rowscan_count() const override { return n_rowscan; }
+    uint64_t prepass_count() const override { return n_prepass; }
+    uint64_t deferred_count() override {
+        if (!has_sin || !d_flags || !have_last) return 0;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(last_stream));
+        unsigned n = 0;
+        HIP_TRY(hipMemcpy(&n, d_flags, sizeof n, hipMemcpyDeviceToHost));      // the work list's count: {count, tile, ...}
+        return n;
+    }
     size_t debug_row_words(uint64_t *xb, size_t xcap, uint64_t *rw, size_t rcap, size_t *n_rwords, uint32_t *per_rect, int *used) override {
         if (!n_gwords || cur_set < 0 || !tabs[cur_set].gbits) throw Error{MARAY_E_ARG, "no guard words: a program without guards, or no launch yet"};
         HIP_TRY(hipSetDevice(device));

@@ -220,7 +220,9 @@ std::string program_name(const maray_program &prog)
 {
     std::string salt = key_salt() + "|" + maray_build_id;
     std::vector<std::string> knobs;
-    for (char **e = environ; e && *e; e++) if (!strncmp(*e, "MARAY_JIT_", 10)) knobs.push_back(*e);
+    // (MARAY_JIT_PREPASS decides only whether a context asks for the pre-pass module: no text depends on it, and with it in
+    // the name a knob-off context would build every other module of the program again under another name)
+    for (char **e = environ; e && *e; e++) if (!strncmp(*e, "MARAY_JIT_", 10) && strncmp(*e, "MARAY_JIT_PREPASS=", 18)) knobs.push_back(*e);
     std::sort(knobs.begin(), knobs.end());
     for (const std::string &kn : knobs) salt += "|" + kn;
     const uint32_t counts[8] = {prog.version, prog.n_consts, prog.n_row_ops, prog.n_row_slots, prog.n_yvals, prog.n_pix_ops, prog.n_pix_slots, prog.n_app};
@@ -777,6 +779,56 @@ std::shared_ptr<const JitRowWordsCode> jit_code_rowwords(const maray_program &pr
             if (!path.empty()) blob_write(dir, path, blob);
         }
         if (out->code.empty() || out->flag_bit < 0 || out->flag_bit >= 64 * 1024) out.reset();       // nothing to launch
+        mine.set_value(out);
+    } catch (...) {
+        mine.set_exception(std::current_exception());
+        std::lock_guard<std::mutex> lk(m);
+        built.erase(key);                               // a failed build is not remembered (the waiters still see its error)
+    }
+    return fut.get();
+}
+
+// The pre-pass module of a program (jit_source_prepass: maray_jit_pixels_pp): a seventh module, kept like the row words' -- in
+// the process and on disk under a key of its own (<key>.mrpp: the code object, one byte that says whether there is one, and a
+// checksum) made of the program's name.  Asked for beside the row-word module by the launch that asks for that one
+// (JitBackend::rowwords_module).  MARAY_JIT_PREPASS is in no key and in no name (program_name leaves it out): it decides whether a context ever asks.
+std::shared_ptr<const JitPrepassCode> jit_code_prepass(const maray_program &prog)
+{
+    static std::mutex m;
+    static std::map<std::string, std::shared_future<std::shared_ptr<const JitPrepassCode>>> built;
+    std::string key;
+    {
+        const std::string name = program_name(prog) + "|prepass";
+        key = hex128(fnv1a(name.data(), name.size(), 0xcbf29ce484222325ull), fnv1a(name.data(), name.size(), 0x84222325cbf29ce4ull));
+    }
+    std::promise<std::shared_ptr<const JitPrepassCode>> mine;
+    std::shared_future<std::shared_ptr<const JitPrepassCode>> fut;
+    bool build = false;
+    {
+        std::lock_guard<std::mutex> lk(m);
+        auto it = built.find(key);
+        if (it != built.end()) fut = it->second;
+        else {
+            if (built.size() > 32) built.clear();
+            fut = mine.get_future().share(); built.emplace(key, fut); build = true;
+        }
+    }
+    if (!build) return fut.get();
+    try {
+        auto out = std::make_shared<JitPrepassCode>();
+        const std::string dir = cache_dir(), path = dir.empty() ? "" : dir + "/" + key + ".mrpp";
+        std::vector<char> blob;
+        if (!path.empty() && blob_read(path, blob) && blob.size() >= 1) {       // code object + 1 / nothing + 0 (the program gets none)
+            blob.resize(blob.size() - 1);
+            out->code.swap(blob);
+        } else {
+            const std::string src = jit_source_prepass(prog);
+            if (!src.empty()) compile_aside(src, "prepass", "PRE-PASS", out->code);
+            blob = out->code;
+            blob.push_back(out->code.empty() ? 0 : 1);
+            if (!path.empty()) blob_write(dir, path, blob);
+        }
+        if (out->code.empty()) out.reset();             // nothing to launch
         mine.set_value(out);
     } catch (...) {
         mine.set_exception(std::current_exception());

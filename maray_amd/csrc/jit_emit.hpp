@@ -291,6 +291,13 @@ struct Emitter {
     // picture sets its bit in mr_rwh<word>, a reduction whose untainted leaves cover the row sets bit j (its rank among those
     // with a cover bit) of mr_rwcv.  A pass is one rectangle wide, so it sees all of its (rectangle, row).
     bool rowscan = false;
+    // PIXEL: the pre-pass of maray_jit_pixels_pp (jit_source_prepass): the section emitted as for assume_guards_zero, four pixels
+    // per lane, for the lanes of a tile's leafless rectangles.  pp_root_or, per root op of a boolean reduction with a cover bit:
+    // the lane mask (an mr_m by name) of the rectangles whose bit is set, ORed into the root's value -- on those lanes the
+    // narrow pass takes MR_ALL.  pp_keep: the lanes whose pixels the pre-pass keeps; a Sin that may defer its tile sees 0.0
+    // elsewhere (quiet_arg), so that a leafy rectangle's lanes, which a narrow pass overwrites, defer nothing.
+    std::map<uint32_t, std::string> pp_root_or;
+    std::string pp_keep;
     int32_t cover_of(int32_t id) const { return (cover || use_cover) && id >= 0 && (size_t)id < cover_bit.size() ? cover_bit[id] : -1; }
     explicit Emitter(const maray_program &p) : P(p) {}
 
@@ -532,7 +539,7 @@ struct Emitter {
             // anyway, and without this nearly every tile of a scene of textured shapes was re-rendered by the interpreter
             // (1,000 triangles: 2.2 ms of the frame's 2.4).
             auto quiet_arg = [&](const std::string &x) -> std::string {
-                std::string m;
+                std::string m = pp_keep;
                 for (const Open &o : open) if (!o.mask.empty()) m += (m.empty() ? "" : " & ") + o.mask;
                 return m.empty() ? x : "mr_sel0(" + m + ", " + x + ")";
             };
@@ -650,6 +657,11 @@ struct Emitter {
             }
             case MARAY_OP_TEXDIM: e = "mr_texdim(tex, " + std::to_string(aux) + "u)"; break;
             default: throw Error{MARAY_E_ARG, "invalid opcode"};
+            }
+            if (!pp_root_or.empty() && pp_root_or.count(i)) {
+                // (a root that the wide section carries as a number is 0 or 1 all the same: as a mask, value != 0)
+                if (be.empty()) { be = "mr_ne0(" + e + ")"; e.clear(); }
+                be = m_or(be, pp_root_or[i]);
             }
             if (role == RedPlan::INNER || role == RedPlan::ROOT) {
                 // an OR of the tree: its operands are parts of the tree (nothing to do) or free leaves (OR-ed in at the root)

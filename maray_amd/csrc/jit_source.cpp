@@ -851,7 +851,16 @@ static std::string tile_end(bool defer)
 // the kernel itself, from `head` (its name and parameters) to its closing brace, into S.E.out: maray_jit_pixels, and with the
 // emitter's use_cover flag set maray_jit_pixels_cov (jit_source_cover)
 // (strip_fetch: the strip's guard fetch where it is not strip_guard_fetch()'s -- maray_jit_pixels_rw, jit_source_rowwords)
-static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs &K, const std::string &head, const std::string *strip_fetch = nullptr)
+// (pp: the wide pre-pass of a busy tile's leafless rectangles -- maray_jit_pixels_pp, jit_source_prepass; everything it adds
+// to the text stands between PP_OPEN and PP_CLOSE)
+namespace {
+struct PrepassPlan { std::vector<std::pair<uint32_t, uint32_t>> roots; };       // (root op of a boolean reduction, its cover bit in the last guard word)
+const char PP_OPEN[] = "    /*mr_pp{*/\n", PP_CLOSE[] = "    /*mr_pp}*/\n";
+}   // namespace
+static std::string prepass_tile(PixelSetup &S, const maray_program &P, const GuardWords &g, const PrepassPlan &pp, bool defer);
+
+static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs &K, const std::string &head, const std::string *strip_fetch = nullptr,
+                          const PrepassPlan *pp = nullptr)
 {
     Emitter &E = S.E;
     const GuardWords g(S.n_gwords, S.sub);
@@ -883,12 +892,97 @@ static void pixels_kernel(PixelSetup &S, const maray_program &P, const JitKnobs 
         s += wide_open(g);
         section("mr_d", "mr_m", false, nullptr);
         s += wide_close(defer) + tile_end(defer);
+    } else if (pp) {
+        // narrow_open()'s text with the pre-pass behind its first line (mr_fast) and the skip of the leafless passes at the head
+        // of its loop.  The pre-pass's section is emitted AFTER the narrow one and put in front of it: the narrow section's
+        // label numbers are then maray_jit_pixels_rw's
+        const std::string open = narrow_open(g);
+        const size_t nl = open.find('\n'), lp = open.find("e++) {\n");
+        if (nl == std::string::npos || lp == std::string::npos || lp < nl) throw Error{MARAY_E_INTERNAL, "the narrow loop's text is not what the pre-pass is spliced into"};
+        const size_t line1 = nl + 1, loop = lp + 7;
+        s += open.substr(0, line1);
+        const size_t at = s.size();
+        s += open.substr(line1, loop - line1) + PP_OPEN + "    if (((mr_ppleafy >> e) & 1u) == 0u) continue;      // its pixels are the pre-pass's\n" + PP_CLOSE + open.substr(loop);
+        section("double", "mr_mask", false, &S.reductions);
+        s += narrow_close(defer) + tile_end(defer);
+        std::string rest;
+        rest.swap(s);
+        const std::string tile = prepass_tile(S, P, g, *pp, defer);      // (appends its section to s, which is E.out)
+        s = rest;
+        s.insert(at, tile);
     } else {
         s += narrow_open(g);
         section("double", "mr_mask", false, &S.reductions);
         s += narrow_close(defer) + tile_end(defer);
     }
     s += "    }\n}\n";
+}
+
+// The pre-pass of a tile of maray_jit_pixels_pp, between narrow_open()'s mr_fast and its loop: which of the tile's four
+// rectangles are leafy (mr_ppleafy, from the strip's ballot mr_ppnz), and where one is not, the section four pixels per lane as
+// for a tile without a guard bit, with the cover bits' lanes ORed into their reductions' roots.
+static std::string prepass_tile(PixelSetup &S, const maray_program &P, const GuardWords &g, const PrepassPlan &pp, bool defer)
+{
+    Emitter &E = S.E;
+    const std::string N = std::to_string(g.n);
+    char hex[32];
+    snprintf(hex, sizeof hex, "0x%llxull", (1ull << g.n) - 1ull);
+    std::string t = std::string(PP_OPEN) +
+        "    unsigned mr_ppleafy = 15u;                                             // bit e: pass e runs (a tile off the fast path: all four)\n"
+        "    if (mr_fast && mr_wide) {\n"
+        "        const unsigned long long mr_ppt = mr_ppnz >> (t * " + g.tw + "u);\n"
+        "        mr_ppleafy = ";
+    for (uint32_t e = 0; e < 4; e++)
+        t += std::string(e ? " | " : "") + "(((mr_ppt >> " + std::to_string(e * g.n) + "u) & " + hex + ") != 0ull ? " + std::to_string(1u << e) + "u : 0u)";
+    t += ";\n"
+         "    }\n"
+         "    if (mr_ppleafy != 15u) {\n";
+    if (!pp.roots.empty())
+        t += "    // lane l is in rectangle l / 16 of the tile (mr_wide): its rectangle's last word, where the cover bits are\n"
+             "    const unsigned mr_ppsrc = ((((t * 4u + (mr_lane >> 4)) * " + N + "u + " + std::to_string(g.n - 1) + "u) & 63u) * 4u);\n";
+    bool half[2] = {false, false};
+    for (const auto &r : pp.roots) half[(r.second % 64) >= 32] = true;
+    if (half[0]) t += "    const unsigned mr_ppw0 = (unsigned)__builtin_amdgcn_ds_bpermute((int)mr_ppsrc, (int)(unsigned)mr_gv);\n";
+    if (half[1]) t += "    const unsigned mr_ppw1 = (unsigned)__builtin_amdgcn_ds_bpermute((int)mr_ppsrc, (int)(unsigned)(mr_gv >> 32));\n";
+    E.pp_root_or.clear();
+    for (size_t k = 0; k < pp.roots.size(); k++) {
+        const uint32_t b = pp.roots[k].second % 64;
+        snprintf(hex, sizeof hex, "0x%xu", 1u << (b % 32));
+        const std::string name = "mr_ppcv" + std::to_string(k);
+        t += "    const mr_m " + name + "(mr_ballot((mr_ppw" + (b >= 32 ? "1" : "0") + " & " + hex + ") != 0u));      // the lanes of the rectangles this OR covers\n";
+        E.pp_root_or[pp.roots[k].first] = name;
+    }
+    t += "    const mr_m mr_ppk(mr_ballot(((mr_ppleafy >> (mr_lane >> 4)) & 1u) == 0u));      // the lanes whose pixels are kept\n"
+         "    (void)mr_ppk;\n" + wide_open(g);
+    std::string &s = E.out;
+    s.clear();
+    const bool ktab = E.ktab;
+    E.ktab = false;             // literals: the constant table stays maray_jit_pixels_rw's, entry for entry
+    E.pp_keep = defer ? "mr_ppk" : "";
+    E.td = "mr_d"; E.tm = "mr_m"; E.assume_guards_zero = true; E.rplan = nullptr;
+    E.section(P.pix_ops, P.n_pix_ops, P.n_pix_slots, true, "v");
+    E.ktab = ktab; E.pp_keep.clear(); E.pp_root_or.clear(); E.assume_guards_zero = false;
+    t += s;
+    s.clear();
+    t += defer_pass(defer) +
+         "    const unsigned p0 = mr_cast_u8(o0.a) | (mr_cast_u8(o1.a) << 8) | (mr_cast_u8(o2.a) << 16);\n"
+         "    const unsigned p1 = mr_cast_u8(o0.b) | (mr_cast_u8(o1.b) << 8) | (mr_cast_u8(o2.b) << 16);\n"
+         "    const unsigned p2 = mr_cast_u8(o0.c) | (mr_cast_u8(o1.c) << 8) | (mr_cast_u8(o2.c) << 16);\n"
+         "    const unsigned p3 = mr_cast_u8(o0.d) | (mr_cast_u8(o1.d) << 8) | (mr_cast_u8(o2.d) << 16);\n"
+         "    if (mr_ppleafy == 0u) {                                                // no narrow pass: the tile leaves from the registers\n"
+         "        mr_u3 d;\n"
+         "        d.a = p0 | (p1 << 24); d.b = (p1 >> 8) | (p2 << 16); d.c = (p2 >> 16) | (p3 << 8);\n"
+         "        *(mr_u3 *)(rgb8 + (row_px + xa) * 3) = d;\n" +
+         tile_end(defer) +
+         "        continue;\n"
+         "    }\n"
+         "    mr_u4 mr_ppq;\n"
+         "    mr_ppq.a = p0; mr_ppq.b = p1; mr_ppq.c = p2; mr_ppq.d = p3;\n"
+         "    *(mr_u4 *)&mr_tp[mr_wv * 256u + 4u * mr_lane] = mr_ppq;            // what the narrow epilogue reads back; the leafy passes overwrite their 64 entries\n"
+         "    __builtin_amdgcn_wave_barrier();                                     // same wavefront: LDS keeps its order\n"
+         "    }\n"
+         "    }\n" + PP_CLOSE;
+    return t;
 }
 
 std::string jit_source(const maray_program &P, int min_waves)
@@ -1348,6 +1442,80 @@ std::string jit_source_rowwords(const maray_program &P, RowWordsPlan *plan_out, 
     return S.splice_constants(MR_STORE_RUN);
 }
 
+// ---- maray_jit_pixels_pp -----------------------------------------------------------------------------------------------------------
+// Source of the pre-pass module: maray_jit_pixels_pp, whose text is maray_jit_pixels_rw's plus the lines
+// between PP_OPEN and PP_CLOSE, every one of which ends up carrying "mr_pp".  A rectangle whose guard words are zero apart
+// from cover bits is LEAFLESS: a narrow pass over it enters no leaf, computes every row-guarded region as +0.0, every
+// uncovered reduction as its free leaves and every covered OR as MR_ALL -- and costs its table copies, its six v_readlane,
+// the skeleton of its reductions, its conversions and its LDS write all the same.  On the fast RGB8 path a busy tile with a
+// leafless rectangle renders those rectangles in ONE wide pre-pass, the section as for a tile without a guard bit with the
+// covered rectangles' lanes ORed in at the roots, leaves the packed pixels where the narrow passes leave theirs, and the
+// narrow loop runs the leafy passes only.  Exact for the sky variant's reasons: OR on masks is associative and commutative,
+// a clear bit means +0.0 on the whole rectangle, an evaluator may ignore any SKIP op.
+// For the programs that get row words (rowwords_setup) whose cover bits and row flag sit in the last guard word; "" otherwise.
+std::string jit_source_prepass(const maray_program &P, int min_waves)
+{
+    validate_program(P);
+    const JitKnobs K = jit_knobs();
+    const RowWordsSetup rs = rowwords_setup(P, K);
+    if (rs.flag_bit < 0) return "";
+    const CoverSetup &cs = rs.cs;
+    PixelSetup S(P, K, min_waves);
+    Emitter &E = S.E;
+    const GuardWords g(S.n_gwords, S.sub);
+    if (!g.in_sgprs || g.sub != 4 || S.reductions.empty() || jit_wide_general(P, S.n_gwords, K)) return "";
+    if ((uint32_t)rs.flag_bit / 64 != g.n - 1) return "";
+    // per word: the bits that make a rectangle leafy -- all but the cover bits and, in words that come from the band's table,
+    // the row flag (row words are stored without it)
+    PrepassPlan pp;
+    std::vector<uint64_t> leafy(g.n, ~0ull);
+    leafy[g.n - 1] &= ~(1ull << ((uint32_t)rs.flag_bit % 64));
+    for (uint32_t id = 0; id < S.reductions.reds.size() && id < cs.bit_of_red.size(); id++) {
+        const int32_t bit = cs.bit_of_red[id];
+        if (bit < 0) continue;
+        if ((uint32_t)bit / 64 != g.n - 1 || !S.reductions.reds[id].boolean) return "";
+        pp.roots.emplace_back(S.reductions.reds[id].root, (uint32_t)bit);
+        leafy[g.n - 1] &= ~(1ull << ((uint32_t)bit % 64));
+    }
+    E.cover_bit = cs.bit_of_red;
+    E.census_row_params = row_param_mask(P);
+    std::string &s = E.out;
+    s += "// generated by libmaray_hip (jit_source.cpp) from a v" + std::to_string(P.version) + " tape: PIXEL section, " +
+         std::to_string(P.n_pix_ops) + " ops; row words: the guard words of a rectangle, refined row by row; the row flag is bit " + std::to_string(rs.flag_bit) + "\n"
+         "// mr_pp: with a wide pre-pass of a busy tile's leafless rectangles\n" +
+         PIXELS_PROLOGUE;
+    const char tail[] = "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw)";
+    std::string head = pixels_head(S.min_waves);
+    head.replace(head.find("maray_jit_pixels("), 17, "maray_jit_pixels_pp(");
+    head.replace(head.find(tail), sizeof tail - 1, "const unsigned *__restrict__ row_order, unsigned rows, unsigned rpw, const unsigned long long *__restrict__ mr_rwords)");
+    std::string fetch = strip_guard_fetch_rw(g, (uint32_t)rs.flag_bit) + PP_OPEN +
+                        "    unsigned long long mr_ppm = 0ull;                                      // per lane (word lane % " + g.nw + " of its rectangle): the bits that make a rectangle leafy\n"
+                        "    switch (mr_lane % " + g.nw + "u) {\n";
+    for (uint32_t j = 0; j < g.n; j++) {
+        char hex[32];
+        snprintf(hex, sizeof hex, "0x%llxull", (unsigned long long)leafy[j]);
+        fetch += "    case " + std::to_string(j) + ": mr_ppm = " + hex + "; break;\n";
+    }
+    fetch += "    }\n"
+             "    const unsigned long long mr_ppnz = mr_ballot((mr_gv & mr_ppm) != 0ull);      // which of the strip's words hold such a bit\n" + std::string(PP_CLOSE);
+    E.use_cover = true;
+    pixels_kernel(S, P, K, head, &fetch, &pp);
+    E.use_cover = false;
+    const std::string text = S.splice_constants(MR_STORE_RUN);
+    // every line between the sentinels carries the marker
+    std::string out;
+    bool inside = false;
+    for (size_t at = 0; at < text.size();) {
+        const size_t nl = text.find('\n', at), end = nl == std::string::npos ? text.size() : nl;
+        std::string line = text.substr(at, end - at);
+        if (line.find("/*mr_pp{*/") != std::string::npos) inside = true;
+        if (inside && line.find("mr_pp") == std::string::npos) line += "      // mr_pp";
+        if (line.find("/*mr_pp}*/") != std::string::npos) inside = false;
+        out += line + "\n";
+        at = end + 1;
+    }
+    return out;
+}
 
 // ---- maray_jit_pixels_ss ---------------------------------------------------------------------------------------------------------
 static const char SAMPLES_PROLOGUE[] =
