@@ -224,10 +224,11 @@ int maray_scene_supersample(maray_scene *s, uint32_t k);   /* X -> X/k - (k-1)/(
 
 /* ---- reconstruction filter (what turns the samples of a supersampled render into pixels) ---------------------------
  * `filter` (maray_ctx_opts.filter, maray_gen_opts.filter) is MARAY_FILTER_BOX, the in-kernel mean described above and the
- * default, or MARAY_FILTER_TENT, a tent (Bartlett) filter two output pixels wide whose footprint overlaps the neighbouring
- * pixels'.  TENT needs samples = k in {2, 4, 8}: TENT with samples 0 or 1 is MARAY_E_ARG, any other filter value is
- * MARAY_E_ARG.  A TENT context is created like a box one, from the SUPERSAMPLED program (maray_scene_supersample(s, k), then
- * lower), and every render entry point takes output geometry.
+ * default, MARAY_FILTER_TENT, a tent (Bartlett) filter two output pixels wide whose footprint overlaps the neighbouring
+ * pixels', or MARAY_FILTER_CATROM, a Catmull-Rom filter four pixels wide (after the tent, below).  TENT and CATROM both need
+ * samples = k in {2, 4, 8}: either with samples 0 or 1 is MARAY_E_ARG, and so is any other filter value (2 among them).  A
+ * TENT or CATROM context is created like a box one, from the SUPERSAMPLED program (maray_scene_supersample(s, k), then lower),
+ * and every render entry point takes output geometry.  The tent:
  *   - s(a, b, c) is the cast (`as u8`) sample of channel c at integer sample index (a, b) of the k w x k h sample raster:
  *     what a plain context of the same program renders;
  *   - per axis the footprint of pixel p is the 2k sample indices k p + u, u = -k/2 .. 3k/2 - 1, with the integer weights
@@ -248,8 +249,37 @@ int maray_scene_supersample(maray_scene *s, uint32_t k);   /* X -> X/k - (k-1)/(
  * stream and freed with the context; the device-pointer forms return without a device synchronise.  A band holds about
  * 128 MiB of samples; MARAY_FILTER_BAND_ROWS=<output rows>, read when the context is created, overrides that (measurements,
  * tests).  maray_hip_ctx_set_params passes through; the shutter entry points average tent-filtered frames; maray_hip_time_rows
- * / _blocks time launches plus filter; maray_hip_kernel_name is the inner kernel's name + "+maray_filter_tent<k>". */
-enum { MARAY_FILTER_BOX = 0, MARAY_FILTER_TENT = 1 };
+ * / _blocks time launches plus filter; maray_hip_kernel_name is the inner kernel's name + "+maray_filter_tent<k>".
+ *
+ * MARAY_FILTER_CATROM = 3 is the Catmull-Rom filter, the cubic BC-spline with B = 0, C = 1/2: four output pixels wide, with
+ * negative lobes that keep edges sharp where box and tent only average.  The value 2 is unassigned and stays MARAY_E_ARG.
+ * CATROM needs samples = k in {2, 4, 8} like TENT (0 or 1: MARAY_E_ARG), and CATROM together with MARAY_TRANSFER_SRGB is not
+ * built: MARAY_E_ARG, reported before a device is looked for.  f64 planes and over-limit sizes are refused exactly as for TENT.
+ * With s(a, b, c) as above:
+ *   - per axis the footprint of pixel p is the 4k sample indices k p + u, u = -3k/2 .. 5k/2 - 1;
+ *   - with n = |2u + 1 - k| (always odd, so never equal to D or 2D) and D = 2k the integer weights are
+ *       e(u) =  3 n^3 - 5 n^2 D + 2 D^3             for n < D,
+ *       e(u) = -  n^3 + 5 n^2 D - 8 n D^2 + 4 D^3   for D < n < 2D,
+ *     which is 2 D^3 CatmullRom(n / D) exactly (k = 2: -3 -9 29 111 111 29 -9 -3).  Their sum per axis is 16 k^4 = 256 / 4096 /
+ *     65536, a power of two; each residue class of u modulo k sums to 16 k^3 = 128 / 1024 / 8192 (the partition of unity: a
+ *     constant image comes out unchanged); the extremes of e are 111 / -9, 987 / -75, 8115 / -605;
+ *   - indices are clamped to the IMAGE, as for the tent -- never to a launch's rows, a band or a tile;
+ *   - out(px, py, c) = min(max((SUM_u SUM_v e(u) e(v) s(clamp(k px + u), clamp(k py + v), c) + W/2) >> log2 W, 0), 255),
+ *     W = (16 k^4)^2: a shift by 16 / 24 / 32.  The sum is signed and >> is an arithmetic shift; which way it rounds a
+ *     negative sum cannot show, because every negative result is clamped to 0.
+ * All arithmetic is integer, so the picture is the same whatever the launch order, band size, tile cut or device split.  The
+ * widths, from the sums of the positive and of the negative weights (k = 2 / 4 / 8):
+ *   - a horizontal partial sum lies in -6,120 .. 71,400 / -89,760 .. 1,134,240 / -1,403,520 .. 18,115,200: 26 bits signed
+ *     at k = 8;
+ *   - the full sum lies in -3,427,200 .. 20,138,880 / -798,504,960 .. 5,076,695,040 / -199,412,121,600 .. 1,294,628,782,080:
+ *     25 / 33 / 41 bits of magnitude, one more with the sign.  At k = 4 and 8 a 32-bit accumulator is WRONG, signed or unsigned.
+ * Output rows [y0, y1) read the sample rows [k y0 - 3k/2, k y1 + 3k/2) clipped to [0, k h): every entry point renders that
+ * halo itself -- per row range, per row block, per host tile, per gen_to_image tile and worker.
+ * How it runs: the tent's wrapper and bands (above) with that halo and maray_filter_catrom<k> in place of the tent's kernel:
+ * 32-bit horizontal sums in LDS, 64-bit vertical sums at k = 4 and 8.  The band budget, MARAY_FILTER_BAND_ROWS, set_params,
+ * the shutter entry points (a frame is the Catmull-Rom-filtered frame) and the timing entry points work as for the tent;
+ * maray_hip_kernel_name is the inner kernel's name + "+maray_filter_catrom<k>". */
+enum { MARAY_FILTER_BOX = 0, MARAY_FILTER_TENT = 1, MARAY_FILTER_CATROM = 3 };      /* (2 is unassigned: MARAY_E_ARG) */
 /* The filter kernel on its own (measurements): average ms of one pass over a w x rows output image (k w x k rows samples in
  * scratch of the call's own, whatever they hold). */
 int maray_hip_time_filter(int device, uint32_t w, uint32_t rows, uint32_t k, int reps, float *ms_avg);
@@ -288,7 +318,8 @@ enum { MARAY_TRANSFER_NONE = 0, MARAY_TRANSFER_SRGB = 1 };
 /* The two tables of a transfer; needs no device.  NONE: the identity (decode[v] = thresholds[v] = v); SRGB: D and T as above,
  * thresholds[0] = 0.  Any other transfer, or a null pointer: MARAY_E_ARG. */
 int maray_transfer_table(uint32_t transfer, uint16_t decode[256], uint16_t thresholds[256]);
-/* maray_hip_time_filter for any reduce kernel: (TENT, NONE) is maray_filter_tent<k>, (BOX, SRGB) maray_filter_box_lin<k>, (TENT,
+/* maray_hip_time_filter for any reduce kernel: (CATROM, NONE) is maray_filter_catrom<k> (CATROM with SRGB: MARAY_E_ARG, not
+ * built), (TENT, NONE) is maray_filter_tent<k>, (BOX, SRGB) maray_filter_box_lin<k>, (TENT,
  * SRGB) maray_filter_tent_lin<k>; (BOX, NONE) has no kernel of its own (the reduce is inside the pixel kernel): MARAY_E_ARG.
  * The measurement entry points fill their own sample buffers with one byte value, 0x5A; with MARAY_TIME_RANDOM_BYTES=1 in the
  * environment (read at each call) with pseudo-random bytes: for the SRGB kernels the best and the worst case of their LDS
@@ -542,7 +573,7 @@ typedef struct maray_gen_opts {
     uint32_t shutter;        /* n frames averaged over the scene's parameter spans (maray_scene_shutter_values; n in {0, 1, 2, 4,
                                 ..., 64}).  0, 1 or no span above 0: the plain render, exactly.  The program and its contexts are
                                 the plain render's: spans and n are not part of their name */
-    uint32_t filter;         /* MARAY_FILTER_* ("reconstruction filter"); TENT needs samples in {2, 4, 8}; programs and contexts
+    uint32_t filter;         /* MARAY_FILTER_* ("reconstruction filter"); TENT and CATROM need samples in {2, 4, 8}; programs and contexts
                                 are kept per (k, filter) */
     uint32_t encoder;        /* MARAY_ENCODER_* (offset 24): who writes maray_gen's PNG; see "device PNG encoder" below.  Any other value:
                                 MARAY_E_ARG.  maray_gen_to_image checks the word and otherwise ignores it */
@@ -562,8 +593,8 @@ int maray_gen_to_image(const maray_scene *s, const maray_texture *tex, uint32_t 
  * it in a loop (examples/test*.rs) pays the lowering and the context creation once, not per frame.  This frees them. */
 void maray_gen_cache_clear(void);
 /* What is kept, one line per idle context: "<program key> device <d> kernel <name> hint_mpixels <n>" (NUL-terminated,
- * cut to cap; " samples <k>" follows for k > 1, " filter tent" after that for MARAY_FILTER_TENT and " transfer srgb" last for
- * MARAY_TRANSFER_SRGB).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
+ * cut to cap; " samples <k>" follows for k > 1, " filter tent" / " filter catrom" after that for MARAY_FILTER_TENT /
+ * MARAY_FILTER_CATROM and " transfer srgb" last for MARAY_TRANSFER_SRGB).  Under MARAY_BACKEND_AUTO a kept interpreter context is replaced when a later call renders more than
  * the call it was chosen for; contexts are kept per physical device. */
 int maray_gen_cache_info(char *out, size_t cap);
 /* gen: render and write a PNG (progress callback prints "%.2f %%" to stderr

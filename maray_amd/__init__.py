@@ -4,7 +4,7 @@ A thin ctypes binding over libmaray_hip.so (C ABI in include/maray_hip.h).
 The compute path is the HIP library; there is no Python or CPU fallback: every
 render call raises MarayError when the library or a gfx950 device is missing.
 """
-from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, ENCODER_DEVICE, ENCODER_HOST, FILTER_BOX, FILTER_TENT, TRANSFER_NONE, TRANSFER_SRGB, Context, CtxOpts, GenOpts, MarayError, PinnedRaster, Program, Scene, Tape, device_count, gen,
+from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, ENCODER_DEVICE, ENCODER_HOST, FILTER_BOX, FILTER_CATROM, FILTER_TENT, TRANSFER_NONE, TRANSFER_SRGB, Context, CtxOpts, GenOpts, MarayError, PinnedRaster, Program, Scene, Tape, device_count, gen,
                   gen_cache_clear, gen_cache_info, gen_to_image, image_read, lib, lib_path, png_bytes_to_host, png_encode_device, png_read, png_write, time_filter,
                   time_png_encode, time_shutter_reduce, transfer_table, var_id, version,
                   apng_encode_device, frame_delta, gen_animation, time_frame_delta,
@@ -15,7 +15,7 @@ from .api import (BACKEND_AUTO, BACKEND_JIT, BACKEND_TAPE, BACKEND_TAPE_SMEM, EN
                   ycc_frame_bytes)
 
 __all__ = ['Scene', 'Tape', 'Context', 'PinnedRaster', 'MarayError', 'gen', 'gen_to_image', 'gen_cache_clear', 'gen_cache_info', 'device_count', 'lib', 'lib_path',
-           'png_read', 'png_write', 'image_read', 'version', 'var_id', 'Program', 'BACKEND_TAPE', 'BACKEND_TAPE_SMEM', 'BACKEND_JIT', 'BACKEND_AUTO', 'FILTER_BOX', 'FILTER_TENT',
+           'png_read', 'png_write', 'image_read', 'version', 'var_id', 'Program', 'BACKEND_TAPE', 'BACKEND_TAPE_SMEM', 'BACKEND_JIT', 'BACKEND_AUTO', 'FILTER_BOX', 'FILTER_TENT', 'FILTER_CATROM',
            'time_filter', 'ENCODER_HOST', 'ENCODER_DEVICE', 'GenOpts', 'png_encode_device', 'time_png_encode', 'png_bytes_to_host',
            'TRANSFER_NONE', 'TRANSFER_SRGB', 'CtxOpts', 'transfer_table', 'time_shutter_reduce',
            'frame_delta', 'apng_encode_device', 'gen_animation', 'time_frame_delta',

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 OP_COUNT = 20
 BACKEND_TAPE, BACKEND_TAPE_SMEM, BACKEND_JIT, BACKEND_AUTO = 0, 1, 2, 3
 REPORT_NONE, REPORT_ROW, REPORT_DURATION_MS = 0, 1, 2
-FILTER_BOX, FILTER_TENT = 0, 1
+FILTER_BOX, FILTER_TENT, FILTER_CATROM = 0, 1, 3        # (2 is unassigned: refused)
 ENCODER_HOST, ENCODER_DEVICE = 0, 1
 ENCODER_DYNAMIC = 0x100                 # a flag on ENCODER_DEVICE: dynamic-Huffman codes (MARAY_ENCODER_DYNAMIC)
 CODES_FIXED, CODES_DYNAMIC = 0, 1       # MARAY_PNG_CODES_*
@@ -648,7 +648,9 @@ class Context:
     """Device context: tape + constants + textures resident in HBM.  samples=k > 1: renders the program's raster in k x k
     blocks and writes their means (RGB8 only); every render call then takes output geometry.  filter=FILTER_TENT (needs
     samples 2, 4 or 8): the samples are reduced by a tent filter two pixels wide instead (include/maray_hip.h,
-    "reconstruction filter").  transfer=TRANSFER_SRGB: box, tent and shutter average linear light, not bytes ("transfer")."""
+    "reconstruction filter"); filter=FILTER_CATROM (samples 2, 4 or 8; not with TRANSFER_SRGB): by a Catmull-Rom filter four
+    pixels wide, whose negative lobes keep edges sharp.  transfer=TRANSFER_SRGB: box, tent and shutter average linear light,
+    not bytes ("transfer")."""
 
     def __init__(self, tape, textures=None, device=0, backend=BACKEND_TAPE, hint_mpixels=0, samples=0, filter=FILTER_BOX,
                  transfer=TRANSFER_NONE):
@@ -904,7 +906,8 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
                  transfer=TRANSFER_NONE):
     """`gen_to_image` (src/lib.rs:1177-1195) with RenderMethod::Hip → HxWx3 uint8 (into `out` when given).
     samples=k: anti-aliased, k x k samples per pixel averaged (include/maray_hip.h, supersampling); filter=FILTER_TENT: reduced
-    by a tent filter two pixels wide instead of the box (needs samples 2, 4 or 8).
+    by a tent filter two pixels wide instead of the box (needs samples 2, 4 or 8); filter=FILTER_CATROM: by a Catmull-Rom
+    filter four pixels wide (samples 2, 4 or 8; not with transfer=TRANSFER_SRGB).
     params={name_or_id: value}: sets these declared parameters of the scene first (Scene.declare_param); the scene's
     program and contexts are found again whatever the values.
     shutter=n, spans={name_or_id: span}: motion blur, the integer mean of n frames whose parameters cover their spans around
@@ -934,7 +937,7 @@ def gen_to_image(scene, size=None, textures=None, backend=BACKEND_AUTO, n_device
 def gen(scene, path, textures=None, backend=BACKEND_AUTO, n_devices=0, report_kind=REPORT_NONE, report_value=0, samples=0, shutter=0, filter=FILTER_BOX,
         encoder=ENCODER_HOST, transfer=TRANSFER_NONE):
     """`gen` (src/lib.rs:1199-1213): render and write a PNG (samples=k: anti-aliased; shutter=n: motion blur over the scene's
-    parameter spans; filter=FILTER_TENT: the tent reconstruction filter; transfer=TRANSFER_SRGB: averaged in linear light; as
+    parameter spans; filter=FILTER_TENT / FILTER_CATROM: the tent / Catmull-Rom reconstruction filter; transfer=TRANSFER_SRGB: averaged in linear light; as
     gen_to_image).  encoder=ENCODER_DEVICE: the PNG's
     zlib stream is built on the devices and no raster crosses to the host (include/maray_hip.h, "device PNG encoder");
     ENCODER_DEVICE | ENCODER_DYNAMIC: with dynamic-Huffman codes, the same pixels in a smaller file."""
@@ -1112,7 +1115,8 @@ def png_bytes_to_host():
 
 def time_filter(w, rows, k, device=0, reps=10, filter=FILTER_TENT, transfer=TRANSFER_NONE):
     """Average ms of maray_filter_tent<k> alone over a w x rows output image (maray_hip_time_filter); with
-    transfer=TRANSFER_SRGB of maray_filter_tent_lin<k> or, filter=FILTER_BOX, maray_filter_box_lin<k> (maray_hip_time_filter_ex)."""
+    transfer=TRANSFER_SRGB of maray_filter_tent_lin<k> or, filter=FILTER_BOX, maray_filter_box_lin<k>; with filter=FILTER_CATROM
+    of maray_filter_catrom<k> (maray_hip_time_filter_ex)."""
     ms = C.c_float()
     if filter == FILTER_TENT and transfer == TRANSFER_NONE:
         _check(lib().maray_hip_time_filter(device, w, rows, k, reps, C.byref(ms)))

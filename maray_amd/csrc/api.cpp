@@ -647,14 +647,16 @@ int maray_hip_ctx_create_refined(int device, const maray_program *prog, const ma
         uint32_t samples = opts && opts->samples ? opts->samples : 1u;
         REQUIRE(samples == 1 || samples == 2 || samples == 4 || samples == 8, "samples must be 0, 1, 2, 4 or 8");
         const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
-        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT, "unknown filter");
+        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT || filter == MARAY_FILTER_CATROM, "unknown filter");
         REQUIRE(filter != MARAY_FILTER_TENT || samples > 1, "the tent filter needs samples = 2, 4 or 8");
+        REQUIRE(filter != MARAY_FILTER_CATROM || samples > 1, "the Catmull-Rom filter needs samples = 2, 4 or 8");
         const uint32_t transfer = opts ? opts->transfer : (uint32_t)MARAY_TRANSFER_NONE;
         REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
-        // a tent context is a plain back-end of the (supersampled) program behind the filter's wrapper (filter_backend.cpp); so
+        REQUIRE(filter != MARAY_FILTER_CATROM || transfer == MARAY_TRANSFER_NONE, "the Catmull-Rom filter in linear light (MARAY_TRANSFER_SRGB) is not built");
+        // a tent or Catmull-Rom context is a plain back-end of the (supersampled) program behind the filter's wrapper (filter_backend.cpp); so
         // is every MARAY_TRANSFER_SRGB context: its box reduce is a kernel of the wrapper's, not the in-kernel one
         const uint32_t k = samples;
-        const bool wrapped = filter == MARAY_FILTER_TENT || transfer == MARAY_TRANSFER_SRGB;
+        const bool wrapped = filter == MARAY_FILTER_TENT || filter == MARAY_FILTER_CATROM || transfer == MARAY_TRANSFER_SRGB;
         if (wrapped) samples = 1;
         Backend *b = nullptr;
         switch (backend) {
@@ -868,10 +870,13 @@ int maray_hip_time_filter_ex(int device, uint32_t w, uint32_t rows, uint32_t k, 
 {
     return guard([&] {
         REQUIRE(ms_avg, "null argument");
-        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT, "unknown filter");
+        REQUIRE(filter == MARAY_FILTER_BOX || filter == MARAY_FILTER_TENT || filter == MARAY_FILTER_CATROM, "unknown filter");
         REQUIRE(transfer == MARAY_TRANSFER_NONE || transfer == MARAY_TRANSFER_SRGB, "unknown transfer");
-        REQUIRE(filter == MARAY_FILTER_TENT || transfer == MARAY_TRANSFER_SRGB, "the plain box reduce has no kernel of its own");
-        *ms_avg = transfer == MARAY_TRANSFER_SRGB ? filter_time_lin(device, w, rows, k, filter, reps) : filter_time_tent(device, w, rows, k, reps);
+        REQUIRE(filter != MARAY_FILTER_CATROM || transfer == MARAY_TRANSFER_NONE, "the Catmull-Rom filter in linear light (MARAY_TRANSFER_SRGB) is not built");
+        REQUIRE(filter != MARAY_FILTER_BOX || transfer == MARAY_TRANSFER_SRGB, "the plain box reduce has no kernel of its own");
+        *ms_avg = transfer == MARAY_TRANSFER_SRGB ? filter_time_lin(device, w, rows, k, filter, reps)
+                : filter == MARAY_FILTER_CATROM   ? filter_time_catrom(device, w, rows, k, reps)
+                                                  : filter_time_tent(device, w, rows, k, reps);
     });
 }
 

@@ -1,6 +1,6 @@
 // cli.cpp — `maray` command line (product code).  Mirrors examples/maray.rs:
 //   maray -c N -i in.maray -o out.png [-t tex.png ...]        (:9-47)
-// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), --filter {box,tent} (how the samples become
+// plus --gpus N, --backend {tape,tape-smem,jit}, -s/--samples k (anti-aliasing), --filter {box,tent,catrom} (how the samples become
 // pixels), -p NAME=VALUE[:LO:HI] (a scene parameter:
 // the free variable `var(NAME)` gets VALUE at render time) and --animate NAME=FROM:TO:FRAMES (one image per value, all from
 // the one program and the contexts the first frame set up), --shutter NAME=SPAN / --shutter-samples N (motion blur: every
@@ -32,7 +32,8 @@ static void usage()
             "      --gpus <n>               Number of MI355X devices (default: all)\n"
             "      --backend <b>            auto | jit | tape | tape-smem (default: auto)\n"
             "  -s, --samples <k>            Anti-aliasing: k x k samples per pixel, box-filtered; k = 1, 2, 4 or 8 (default: 1)\n"
-            "      --filter <f>             box | tent (default: box); tent is two pixels wide and needs -s 2, 4 or 8\n"
+            "      --filter <f>             box | tent | catrom (default: box); tent is two pixels wide, catrom (Catmull-Rom) four\n"
+            "                               with negative lobes; both need -s 2, 4 or 8, and catrom does not go with --linear\n"
             "  -p, --param <name=v[:lo:hi]> Value of the scene's free variable `name` (repeatable); lo:hi = the range it is\n"
             "                               declared with (default: any value)\n"
             "      --animate <name=a:b:n>   n images, `name` going from a to b in equal steps; --output needs a `%%d`\n"
@@ -135,7 +136,8 @@ int main(int argc, char **argv)
             const std::string f = val();
             if (f == "box") go.filter = MARAY_FILTER_BOX;
             else if (f == "tent") go.filter = MARAY_FILTER_TENT;
-            else { fprintf(stderr, "Error: --filter takes box or tent, not `%s`\n", f.c_str()); usage(); return 2; }
+            else if (f == "catrom") go.filter = MARAY_FILTER_CATROM;
+            else { fprintf(stderr, "Error: --filter takes box, tent or catrom, not `%s`\n", f.c_str()); usage(); return 2; }
         }
         else if (a == "--linear") linear = true;
         else if (a == "--apng") apng = true;
@@ -231,6 +233,12 @@ int main(int argc, char **argv)
     }
     if (input.empty() || output.empty()) { usage(); return 2; }
     if (go.filter == MARAY_FILTER_TENT && go.samples < 2) { fprintf(stderr, "Error: --filter tent needs -s 2, 4 or 8\n"); usage(); return 2; }
+    if (go.filter == MARAY_FILTER_CATROM && go.samples < 2) { fprintf(stderr, "Error: --filter catrom needs -s 2, 4 or 8\n"); usage(); return 2; }
+    if (go.filter == MARAY_FILTER_CATROM && linear) {
+        fprintf(stderr, "Error: --filter catrom does not go with --linear: the Catmull-Rom filter in linear light is not built\n");
+        usage();
+        return 2;
+    }
     if (png_codes_given && go.encoder != MARAY_ENCODER_DEVICE && !apng) {
         fprintf(stderr, "Error: --png-codes chooses the device encoder's codes: it needs --encoder device or --apng\n");
         usage();

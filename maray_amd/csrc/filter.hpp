@@ -35,6 +35,21 @@ struct TentArgs {
 void filter_tent(uint32_t k, const TentArgs &a, hipStream_t st);      // enqueues one pass; throws Error
 float filter_time_tent(int device, uint32_t w, uint32_t rows, uint32_t k, int reps);     // maray_hip_time_filter
 
+// Sample rows a filter's footprint reaches beyond [k y0, k y1) on either side: the box none, the tent k/2, Catmull-Rom 3k/2.
+constexpr uint32_t filter_halo(uint32_t filter, uint32_t k)
+{
+    return filter == MARAY_FILTER_CATROM ? 3 * k / 2 : filter == MARAY_FILTER_TENT ? k / 2 : 0;
+}
+
+// MARAY_FILTER_CATROM (catrom.hip): maray_filter_catrom<K>, one pass with TentArgs as above but for the halo, which is 3k/2
+// rows: the band must cover [k oy0 - 3k/2, k (oy0 + n_out) + 3k/2) clipped to [0, sh).  Its footprint is 12k bytes of a row
+// from an aligned dword on: FILTER_PAD covers it as it covers the tent's.  A block's tile depends on k (32-bit sums in LDS);
+// never lower than FILTER_TILE_H, so a band the tent's kernel takes in one pass this one takes too.
+constexpr uint32_t catrom_tile_w(uint32_t k) { return k == 8 ? 32 : 64; }
+constexpr uint32_t catrom_tile_h(uint32_t k) { return k == 2 ? 16 : 8; }
+void filter_catrom(uint32_t k, const TentArgs &a, hipStream_t st);    // enqueues one pass; throws Error
+float filter_time_catrom(int device, uint32_t w, uint32_t rows, uint32_t k, int reps);   // maray_hip_time_filter_ex
+
 // The reduces in linear light (include/maray_hip.h, "transfer"; linear.hip): maray_filter_box_lin<K> and
 // maray_filter_tent_lin<K>, one pass each with TentArgs as above.  The box has no halo: its band covers [k oy0, k (oy0 + n_out)).
 // Blocks loop over tiles of rows, so a pass takes any number of rows.
@@ -43,7 +58,8 @@ float filter_time_lin(int device, uint32_t w, uint32_t rows, uint32_t k, uint32_
 
 // The context behind MARAY_FILTER_TENT and behind MARAY_TRANSFER_SRGB: takes over `inner`, a plain (samples = 1) back-end of
 // the (supersampled) program on `device`.  k = 1 (SRGB only): nothing to filter, launches pass through; the wrapper is there
-// for the shutter's linear reduce.  Throws Error (then `inner` is still the caller's).
+// for the shutter's linear reduce.  Also the context behind MARAY_FILTER_CATROM (transfer NONE only, k = 2, 4, 8).  Throws
+// Error (then `inner` is still the caller's).
 Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params, uint32_t filter = MARAY_FILTER_TENT,
                              uint32_t transfer = MARAY_TRANSFER_NONE);
 

@@ -8,6 +8,7 @@
 // Also the context behind MARAY_TRANSFER_SRGB ("transfer"): the same wrapper with the reduces of linear.hip -- the tent in
 // linear light, the box as a kernel of the wrapper's on bands without halo, and the shutter's linear reduce; with samples <= 1
 // there is nothing to filter and every launch is the inner back-end's.
+// And the context behind MARAY_FILTER_CATROM: the tent's bands with a halo of 3k/2 rows and maray_filter_catrom<k> (catrom.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -35,9 +36,10 @@ struct FilterBackend final : Backend {
     uint32_t k = 2;
     // What turns a band into rows: (TENT, NONE) maray_filter_tent<k>; under MARAY_TRANSFER_SRGB (include/maray_hip.h, "transfer")
     // maray_filter_tent_lin<k> or, for BOX, maray_filter_box_lin<k> on a band without halo.  k = 1 (SRGB only) filters nothing:
-    // launches go straight to `inner`, and only the shutter's reduce differs.
+    // launches go straight to `inner`, and only the shutter's reduce differs.  (CATROM, NONE): maray_filter_catrom<k>.
     uint32_t filter = MARAY_FILTER_TENT, transfer = MARAY_TRANSFER_NONE;
     bool tent() const { return filter == MARAY_FILTER_TENT; }
+    bool catrom() const { return filter == MARAY_FILTER_CATROM; }
     bool lin() const { return transfer == MARAY_TRANSFER_SRGB; }
     Backend *inner = nullptr;           // renders the sample raster: the program's plain context
     std::string name;
@@ -104,7 +106,7 @@ struct FilterBackend final : Backend {
         const uint32_t sw = k * w, sh = k * h, step = band_rows(w);
         const size_t row_bytes = (size_t)sw * 3;
         const uint32_t block_rows = std::max(1u, std::min(rb.block_rows, rb.n_rows));
-        const uint32_t halo = tent() ? k / 2 : 0;           // (the box reads sample rows [k y0, k y1) and no others)
+        const uint32_t halo = filter_halo(filter, k);       // (the box reads sample rows [k y0, k y1) and no others)
         grow(scratch, scratch_cap, ((size_t)k * std::min(step, block_rows) + 2 * halo) * row_bytes + 2 * FILTER_PAD);
         for (uint32_t r0 = 0; r0 < rb.n_rows; r0 += block_rows) {
             const uint32_t rows = std::min(block_rows, rb.n_rows - r0);
@@ -115,6 +117,7 @@ struct FilterBackend final : Backend {
                 inner->render_device(sw, sh, RowBlocks::range(s0, s1), scratch + FILTER_PAD, nullptr, st);
                 const TentArgs a{scratch + FILTER_PAD, d8 + ((size_t)r0 + (o0 - by0)) * w * 3, w, sw, sh, s0, s1 - s0, o0, o1 - o0};
                 if (lin()) filter_lin(filter, k, a, st);
+                else if (catrom()) filter_catrom(k, a, st);
                 else filter_tent(k, a, st);
             }
         }
@@ -214,17 +217,19 @@ struct FilterBackend final : Backend {
 
 Backend *make_filter_backend(int device, Backend *inner, uint32_t k, uint32_t n_params, uint32_t filter, uint32_t transfer)
 {
-    const bool lin = transfer == MARAY_TRANSFER_SRGB, tent = filter == MARAY_FILTER_TENT;
-    // what has a kernel here: the tent for k = 2, 4, 8; under SRGB also the box, and k = 1 (the shutter's reduce alone)
-    if (!inner || (!lin && transfer != MARAY_TRANSFER_NONE) || (!tent && (filter != MARAY_FILTER_BOX || !lin)) ||
-        !(filter_samples_ok(k) || (k == 1 && lin && !tent)))
+    const bool lin = transfer == MARAY_TRANSFER_SRGB, tent = filter == MARAY_FILTER_TENT, catrom = filter == MARAY_FILTER_CATROM;
+    // what has a kernel here: the tent for k = 2, 4, 8; under SRGB also the box, and k = 1 (the shutter's reduce alone);
+    // Catmull-Rom for k = 2, 4, 8 without a transfer
+    if (!inner || (!lin && transfer != MARAY_TRANSFER_NONE) || (!tent && !(catrom && !lin) && (filter != MARAY_FILTER_BOX || !lin)) ||
+        !(filter_samples_ok(k) || (k == 1 && lin && !tent && !catrom)))
         throw Error{MARAY_E_INTERNAL, "filter context: bad arguments"};
     std::unique_ptr<FilterBackend> b(new FilterBackend());
     b->init(device, k, n_params);
     b->filter = filter; b->transfer = transfer;
     b->name = std::string(inner->kernel_name()) +
               (k == 1 ? std::string("+maray_shutter_reduce_lin")
-                      : std::string(tent ? "+maray_filter_tent" : "+maray_filter_box") + (lin ? "_lin<" : "<") + std::to_string(k) + ">");
+                      : std::string(catrom ? "+maray_filter_catrom" : tent ? "+maray_filter_tent" : "+maray_filter_box") + (lin ? "_lin<" : "<") +
+                            std::to_string(k) + ">");
     b->inner = inner;       // (last: a throw above leaves `inner` with the caller)
     return b.release();
 }

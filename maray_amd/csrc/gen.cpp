@@ -223,7 +223,7 @@ extern "C" int maray_gen_cache_info(char *out, size_t cap)
             for (auto &kv : e->idle)
                 t += e->key + " device " + std::to_string(kv.first) + " kernel " + maray_hip_kernel_name(kv.second.ctx) + " hint_mpixels " +
                      std::to_string(kv.second.hint_mpixels) + (e->samples > 1 ? " samples " + std::to_string(e->samples) : std::string()) +
-                     (e->filter == MARAY_FILTER_TENT ? " filter tent" : "") + (e->transfer == MARAY_TRANSFER_SRGB ? " transfer srgb" : "") + "\n";
+                     (e->filter == MARAY_FILTER_TENT ? " filter tent" : e->filter == MARAY_FILTER_CATROM ? " filter catrom" : "") + (e->transfer == MARAY_TRANSFER_SRGB ? " transfer srgb" : "") + "\n";
     }
     snprintf(out, cap, "%s", t.c_str());
     return MARAY_OK;
@@ -247,6 +247,7 @@ static int gen_program_key(const maray_scene *s, const maray_texture *tex, uint3
     key = buf;
     if (samples > 1) key += "/s" + std::to_string(samples);      // (k = 1 keeps the key it always had)
     if (filter == MARAY_FILTER_TENT) key += "/tent";             // (box keeps its key: the two are kept side by side)
+    if (filter == MARAY_FILTER_CATROM) key += "/catrom";
     if (transfer == MARAY_TRANSFER_SRGB) key += "/srgb";         // (and so does NONE)
     return MARAY_OK;
 }
@@ -271,8 +272,11 @@ static int gen_run(const maray_scene *s, const maray_texture *tex, uint32_t n_te
     if ((uint64_t)w * samples > MARAY_DOMAIN_MAX || (uint64_t)h * samples > MARAY_DOMAIN_MAX)
         return fail_with(MARAY_E_LIMIT, "supersampled image exceeds " + std::to_string(MARAY_DOMAIN_MAX) + " samples in x or y");
     const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
-    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT) return fail_with(MARAY_E_ARG, "unknown filter");
+    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT && filter != MARAY_FILTER_CATROM) return fail_with(MARAY_E_ARG, "unknown filter");
     if (filter == MARAY_FILTER_TENT && samples == 1) return fail_with(MARAY_E_ARG, "the tent filter needs samples = 2, 4 or 8");
+    if (filter == MARAY_FILTER_CATROM && samples == 1) return fail_with(MARAY_E_ARG, "the Catmull-Rom filter needs samples = 2, 4 or 8");
+    if (filter == MARAY_FILTER_CATROM && transfer != MARAY_TRANSFER_NONE)
+        return fail_with(MARAY_E_ARG, "the Catmull-Rom filter in linear light (MARAY_TRANSFER_SRGB) is not built");
     uint32_t shutter = opts && opts->shutter ? opts->shutter : 1u;
     if (shutter > 64 || (shutter & (shutter - 1))) return fail_with(MARAY_E_ARG, "shutter must be 0, 1, 2, 4, 8, 16, 32 or 64");
     if (!w || !h) return MARAY_OK;
@@ -546,8 +550,11 @@ static int gen_animation(const maray_scene *s, const maray_texture *tex, uint32_
     const uint32_t samples = opts && opts->samples ? opts->samples : 1u;
     if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail_with(MARAY_E_ARG, "samples must be 0, 1, 2, 4 or 8");
     const uint32_t filter = opts ? opts->filter : (uint32_t)MARAY_FILTER_BOX;
-    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT) return fail_with(MARAY_E_ARG, "unknown filter");
+    if (filter != MARAY_FILTER_BOX && filter != MARAY_FILTER_TENT && filter != MARAY_FILTER_CATROM) return fail_with(MARAY_E_ARG, "unknown filter");
     if (filter == MARAY_FILTER_TENT && samples == 1) return fail_with(MARAY_E_ARG, "the tent filter needs samples = 2, 4 or 8");
+    if (filter == MARAY_FILTER_CATROM && samples == 1) return fail_with(MARAY_E_ARG, "the Catmull-Rom filter needs samples = 2, 4 or 8");
+    if (filter == MARAY_FILTER_CATROM && transfer != MARAY_TRANSFER_NONE)
+        return fail_with(MARAY_E_ARG, "the Catmull-Rom filter in linear light (MARAY_TRANSFER_SRGB) is not built");
     const uint32_t shutter = opts && opts->shutter ? opts->shutter : 1u;
     if (shutter > 64 || (shutter & (shutter - 1))) return fail_with(MARAY_E_ARG, "shutter must be 0, 1, 2, 4, 8, 16, 32 or 64");
     if (opts && opts->n_devices > 1) return fail_with(MARAY_E_ARG, "an animation is rendered and encoded on one device: n_devices must be 0 or 1");
